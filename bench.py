@@ -321,6 +321,33 @@ PER_RANK = {}
 CLOCK_WARM_MS = 100.0     # --clock-warm-ms
 CLOCK_WARM = {}           # the steady-clock pass of the last timed_steps() (reported BESIDE the protocol figure)
 _MID = {"ev": None}       # the event split_mark() records inside the step being timed
+DUMP = {"on": False, "prefix": "", "arrays": {}}     # --dump-outputs: host copies of what the timed steps computed
+DUMP_CAP_BYTES = 64 << 20
+DUMP_ROWS = 32768         # rows kept of a larger output: a fixed, seeded sample (the same rows in every run with the same sizes)
+
+
+def keep_output(name, x, rows=DUMP_ROWS):
+    """--dump-outputs: record an output buffer of the step as it stands after timed_steps() (= what its last timed step
+    wrote) under `<workload>_<name>`, as float64 (float32 stays float32).  An output of more than `rows` rows keeps a
+    seeded sample of `rows` of them, in order."""
+    if not DUMP["on"]:
+        return
+    import torch
+
+    if x.shape[0] > rows:
+        idx = np.sort(np.random.default_rng(0).choice(x.shape[0], rows, replace=False))
+        x = x[torch.from_numpy(idx).to(x.device)] if torch.is_tensor(x) else x[idx]
+    a = x.detach().cpu().numpy() if torch.is_tensor(x) else np.asarray(x)
+    DUMP["arrays"][DUMP["prefix"] + name] = np.ascontiguousarray(a, dtype=np.float32 if a.dtype == np.float32 else np.float64)
+
+
+def write_dump(dirname):
+    total = sum(a.nbytes for a in DUMP["arrays"].values())
+    if total > DUMP_CAP_BYTES:
+        raise RuntimeError(f"--dump-outputs: {total} bytes of outputs exceed the {DUMP_CAP_BYTES}-byte cap")
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in DUMP["arrays"].items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
 
 
 def split_mark():
@@ -463,6 +490,7 @@ def bench_convert(args, world, rank, variant="synthetic"):
         vc.fvconvert(g, Xd.t(), out=Yd.t())
 
     wall, kernel_ms = timed_steps(step, args.steps, args.warmup, world)
+    keep_output("y", Yd)                                            # (T,D): the converted frames
 
     clock_warm = dict(CLOCK_WARM)
     frames_per_s = world * T * args.steps / wall
@@ -739,6 +767,7 @@ def bench_estep(args, world, rank, variant="synthetic"):
     # one set of timed steps prices both parts: `kernel_ms` = start of the step to the mark (the E-step kernels),
     # `allreduce_ms` = the rest (the RCCL all-reduce of the packed statistics; no work with one rank and no process group)
     wall, step_ms = timed_steps(step, args.steps, args.warmup, world, split=True)
+    keep_output("stats", out_t, rows=1 << 20)                       # the packed, all-reduced statistics
     clock_warm = dict(CLOCK_WARM)
     kernel_ms = PER_RANK.pop("first_part_ms")
     allreduce_ms = step_ms - kernel_ms
@@ -902,6 +931,7 @@ def bench_estep_full(args, world, rank, variant="synthetic"):
         vc.dist.allreduce_sum_(out_t)
 
     wall, kernel_ms = timed_steps(step, args.steps, args.warmup, world)
+    keep_output("stats", out_t, rows=1 << 20)                       # the packed, all-reduced statistics
 
     clock_warm = dict(CLOCK_WARM)
     flop = 2 * M * Dj * (Dj + 1) + 2 * M * Dj
@@ -1041,6 +1071,7 @@ def bench_dtw(args, world, rank):
                                                    D, 0, 2, pd.data_ptr(), _lib.iptr(poff), torch.cuda.current_stream().cuda_stream))
 
     wall, kernel_ms = timed_steps(step, args.steps, args.warmup, world)
+    keep_output("paths", pd, rows=1 << 20)                          # every pair's warping path, concatenated (poff)
 
     clock_warm = dict(CLOCK_WARM)
     cells = float(np.sum(S * T))
@@ -1142,6 +1173,7 @@ def bench_traj(args, world, rank, gv=False):
                                                             _lib.iptr(yoff), torch.cuda.current_stream().cuda_stream))
 
     wall, kernel_ms = timed_steps(step, args.steps, args.warmup, world)
+    keep_output("y", Yd)                                            # (utterances * T, D): the converted trajectories
 
     clock_warm = dict(CLOCK_WARM)
     flops_per_utt = 2.0e9 + (epochs * T * 2.0 * (2 * D) ** 2 if gv else 0.0)
@@ -1448,7 +1480,12 @@ def main():
                          "no dense pass, no parity sample on the device, no host-pointer calls, no CPU baseline; implies --cpu-seconds 0 --pmc off")
     ap.add_argument("--verify-allreduce", action="store_true",
                     help="estep: rank 0 recomputes the statistics of every rank's frames in one process and compares")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the run, write what each workload's last timed step computed on rank 0 as DIR/<workload>_<output>.npy "
+                         "(float64; at most %d rows of a larger output, a fixed seeded sample; em_full is not dumped: its model "
+                         "advances with every untimed step as well)" % DUMP_ROWS)
     args = ap.parse_args()
+    DUMP["on"] = args.dump_outputs is not None
     global CLOCK_WARM_MS
     CLOCK_WARM_MS = max(args.clock_warm_ms, 0.0)
     if args.profile_run:
@@ -1490,6 +1527,7 @@ def main():
 
         import torch
 
+        DUMP["prefix"] = "convert_"
         out = bench_convert(args, world, rank)
         table = {"convert": summarize(out)}
         sub = copy.copy(args)
@@ -1499,12 +1537,14 @@ def main():
             torch.cuda.empty_cache()
             PER_RANK.clear()
             t0 = time.perf_counter()
+            DUMP["prefix"] = name + "_"
             table[name] = summarize(fns[name](sub, world, rank))
             table[name]["bench_wall_s"] = time.perf_counter() - t0
         PER_RANK.clear()
         PER_RANK.update(table["convert"]["per_rank"])
         out["workloads"] = table
     else:
+        DUMP["prefix"] = args.workload + "_"
         out = fns[args.workload](args, world, rank)
         table = {args.workload: out}
     if world > 1:
@@ -1545,6 +1585,8 @@ def main():
         out["probe_library"] = os.environ["LIBVCMI_PROBE"]      # an A/B or probe build, not the in-tree library
     if rank == 0:
         out["detail"] = write_detail(out, "bench_detail_%s_n%d.json" % (args.workload, world))
+        if DUMP["on"]:
+            write_dump(args.dump_outputs)
         print(compact_line(out, table), flush=True)
     import torch.distributed as dist
 

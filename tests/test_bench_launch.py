@@ -171,3 +171,37 @@ def test_traffic_tables_with_wrong_step_accounting_are_refused(tmp_path, monkeyp
     live["_meta"]["problems"]["void vcmi::k<1>"] = "7 launches in the FETCH_SIZE pass are not a multiple of the 3 steps"
     v, src = bench.pmc_traffic("x", "vcmi::k", 1.0, live=live)
     assert v is None and "not a multiple" in src["source"]
+
+
+def test_dump_outputs_keeps_a_fixed_sample_and_the_cap(tmp_path, monkeypatch):
+    """--dump-outputs: a large output keeps the same seeded rows in order, integers are written as float64, float32 stays
+    float32, files are named <workload>_<output>.npy, and more than the cap in all is refused."""
+    import numpy as np
+    import torch
+
+    sys.path.insert(0, ROOT)
+    import bench
+    monkeypatch.setitem(bench.DUMP, "on", True)
+    monkeypatch.setitem(bench.DUMP, "arrays", {})
+    monkeypatch.setitem(bench.DUMP, "prefix", "convert_")
+    y = torch.arange(100_000 * 4, dtype=torch.float64).reshape(100_000, 4)
+    bench.keep_output("y", y)
+    bench.keep_output("paths", torch.arange(5000, dtype=torch.int64), rows=1 << 20)
+    bench.keep_output("f", np.ones((3, 2), dtype=np.float32))
+    first = bench.DUMP["arrays"]["convert_y"].copy()
+    bench.keep_output("y", y)
+    assert np.array_equal(bench.DUMP["arrays"]["convert_y"], first)
+    assert first.shape == (bench.DUMP_ROWS, 4) and np.all(np.diff(first[:, 0]) > 0)
+    assert np.array_equal(first, y.numpy()[(first[:, 0] // 4).astype(np.int64)])
+    bench.write_dump(str(tmp_path / "d"))
+    assert sorted(os.listdir(tmp_path / "d")) == ["convert_f.npy", "convert_paths.npy", "convert_y.npy"]
+    p = np.load(tmp_path / "d" / "convert_paths.npy")
+    assert p.dtype == np.float64 and np.array_equal(p, np.arange(5000))
+    assert np.load(tmp_path / "d" / "convert_f.npy").dtype == np.float32
+    monkeypatch.setattr(bench, "DUMP_CAP_BYTES", first.nbytes)
+    try:
+        bench.write_dump(str(tmp_path / "e"))
+        raise AssertionError("the cap was not enforced")
+    except RuntimeError as e:
+        assert "cap" in str(e)
+    assert not os.path.exists(tmp_path / "e")
