@@ -192,7 +192,15 @@ int vcmi_estep_diag(const double *X, int64_t N, int Dj, int M, const double *w, 
  * own frames (16 chunks of 1024: at most a quarter without an owner -> the hard-assignment path); vcmi_estep_set_path pins
  * VCMI_ESTEP_HARD or VCMI_ESTEP_SOFT for the calling thread (training loops that must take the same path on every rank).
  * Log-densities of competing mixtures are evaluated term by term, (x - mu)^2 / var, wherever the expanded form's
- * rounding-error bound exceeds 1e-10 (variances near min_covar). */
+ * rounding-error bound exceeds 1e-10 (variances near min_covar).
+ * Accuracy, per mixture m (each of S0[m], S1[:,m], S2[:,m] relative to that mixture's own largest value -- the M-step divides by
+ * S0[m]), on every path, for a frame whose best log-density leads mixture m's by g nats:
+ *   variances >= 1e-3: relative 1e-9 for g <= 690; 744 <= g < 746.5: absolute 1e-320 (subnormal responsibilities);
+ *   g >= 746.5: the frame adds exactly 0 to mixture m;
+ *   tighter variances: relative 1e-9 for g < 36; beyond, the frame's contribution to m within e^-36 of its own weight;
+ *   loglik within 1e-9 relative.
+ * A model whose operands leave the FP32 range of the screen (var below ~1.5e-39, |mu / var| or a margin of 2^114 and more, a
+ * NaN parameter) settles no frame by it: every frame goes through the FP64 kernel. */
 enum { VCMI_ESTEP_AUTO = 0, VCMI_ESTEP_HARD = 1, VCMI_ESTEP_SOFT = 2 };
 int vcmi_estep_set_path(int path);
 int vcmi_estep_get_path(int *path);
@@ -204,7 +212,8 @@ int vcmi_estep_diag_dev(const double *dX, int64_t N, int Dj, int M, const double
  * sklearn.mixture.GMM(covariance_type="full") and :103 calls fit.  w (M); mu (Dj,M); sigma (Dj,Dj,M).
  * Statistics S0 (M), S1 (Dj,M), S2 (Dj,Dj,M) = sum_n gamma_nm x_n x_n', loglik; device layout
  * [S0 | S1 | S2 | loglik] of vcmi_estep_full_stats_len(Dj,M) doubles (one all-reduce).  VCMI_ERR_NOT_PD when a
- * covariance is not positive definite. */
+ * covariance is not positive definite.  Accuracy per mixture as vcmi_estep_diag's for ordinary models (frames whose
+ * responsibility in a mixture is exactly 0 are skipped by its statistics). */
 int64_t vcmi_estep_full_stats_len(int Dj, int M);
 int vcmi_estep_full(const double *X, int64_t N, int Dj, int M, const double *w, const double *mu, const double *sigma,
                     double *S0, double *S1, double *S2, double *loglik);

@@ -188,3 +188,149 @@ def mixed_call(ref, w, mu, sig, D, seed, ratio=9, min_frames=8192, **kw):
     X, cat = np.ascontiguousarray(X[order]), cat[order]
     _, best, second = _top2(ref.logdens(X))
     return X, cat >= 0, cat, best - second
+
+
+# ------------------------------------------------------------------------------------------------ E-step (diagonal / full)
+# The E-step kernels (csrc/estep_hard.hpp, estep.hip, estep_small.hpp, estep_wave.hpp) skip work or switch formulas where a
+# log-density crosses a line: 36 nats (kRefine: term-by-term re-evaluation), 745.2 (VCMI_ESTEP_EXP_SKIP, and where exp
+# underflows), 746 (the hard key).  estep_sentinel_call() builds calls whose frames sit on those lines and makes each decision
+# visible in the statistics of ONE mixture:
+#   background  far-apart mixtures owning the model's p(x) draws (>= 65,536 frames: the hard-assignment path is in play); mixture
+#               0 has 100x wider variances than the rest and owns the outliers and the shifted frames; mixture 1 has weight 0
+#               and sits 3 sigma from mixture 0 (frames whose nearest mixture has no weight);
+#   sentinels   one per gap class g, each a copy of its owner's variances and weight at 60 sigma along its own direction
+#               (orthonormal per owner): the class's frames lie on x_p -> mu_q with l_p - l_q bisected to g, and nothing else in
+#               the call comes within ~1000 nats of the sentinel -- its S0, S1, S2 are made of the responsibilities under test;
+#   triple      two sentinels q, r of one owner and a frame equidistant from all three (equal weights and variances);
+#   outliers    mu_0 + r sigma_0 z for r = 1e2, 1e3, 1e4 (every l ~ -1e8: the expanded form is off by ~1e-6, the refinement
+#               must fire) and draws of mixture 0 shifted by +-2000.
+ESTEP_GAPS = (0.0, 1.0, 20.0, 35.5, 36.5, 45.0, 300.0, 690.0, 744.0, 745.5, 746.5, 760.0)
+_SENT_SIGMAS = 60.0
+
+
+def estep_logdens(X, w, mu, var, dtype=np.longdouble):
+    """vco_estep_diag's log-densities, term by term, in `dtype` (frames (n, Dj), parameters [m][d]) -> (n, M)"""
+    w, mu, var, X = (np.asarray(a, dtype=dtype) for a in (w, mu, var, X))
+    with np.errstate(divide="ignore"):
+        cst = np.log(w) - 0.5 * (mu.shape[1] * np.log(dtype(2) * dtype(np.pi)) + np.log(var).sum(1))
+    out = np.empty((len(X), len(w)), dtype=dtype)
+    for i in range(0, len(X), 4096):
+        x = X[i:i + 4096]
+        out[i:i + 4096] = cst[None] - 0.5 * (((x[:, None, :] - mu[None]) ** 2) / var[None]).sum(2)
+    return out
+
+
+def estep_sentinel_call(Dj, M, seed, tight=False, nbg=65_536, per_class=8, ratio=9, base=None):
+    """-> dict(w, mu, var ([m][d]), X (N, Dj), cls (N,) -1 = p(x) draw / index into ESTEP_GAPS / len(ESTEP_GAPS) = triple /
+    len + 1 = outlier or shifted frame, sent (len(ESTEP_GAPS) + 1,) the sentinel of each class (the triple: its first one),
+    owner (same), gap (N,) the achieved l_owner - l_sentinel).  tight: variances 1e-7 .. 1e-2 and means ~10 (the refinement's
+    regime).  base: (w, mu, var) of the background (a trained model) instead of synthetic mixtures.  M counts every mixture;
+    classes that do not fit (M too small) are left out, from the triple on, then from the largest gap down."""
+    rng = np.random.default_rng(seed)
+    ncls = len(ESTEP_GAPS)
+    if base is not None:
+        bw, bmu, bvar = (np.array(a, dtype=np.float64) for a in base)
+        nb = len(bw)
+    else:
+        nb = max(3, M - ncls - 2)
+        lo, hi = (1e-7, 1e-2) if tight else (0.05, 1.0)
+        bvar = np.exp(rng.uniform(np.log(lo), np.log(hi), (nb, Dj)))
+        bmu = (10.0 if tight else 0.0) + np.sqrt(bvar.max()) * 40.0 * rng.standard_normal((nb, Dj))
+        bw = rng.dirichlet(4.0 * np.ones(nb))
+        bvar[0] = 100.0 * bvar[0]                               # the wide mixture
+        bw[1] = 0.0                                             # the weightless one, 3 sigma from the wide one
+        bmu[1] = bmu[0] + 3.0 * np.sqrt(bvar[0]) * rng.choice([-1.0, 1.0], Dj)
+        bw /= bw.sum()
+    room = M - nb
+    gaps = list(ESTEP_GAPS)
+    triple = room >= ncls + 2
+    while len(gaps) > room - (2 if triple else 0):
+        gaps.pop()
+    assert gaps, "no room for sentinels"
+    owners = [m for m in range(2 if base is None else 0, nb) if bw[m] > 0]
+    owners = [owners[i % len(owners)] for i in range(len(gaps) + (1 if triple else 0))]
+    w, mu, var = np.zeros(M), np.zeros((M, Dj)), np.ones((M, Dj))
+    w[:nb], mu[:nb], var[:nb] = bw, bmu, bvar
+    # sentinel directions: orthonormal per owner, in the owner's own metric (so ties are exact when var and w are copied)
+    dirs = {}
+    for p in set(owners):
+        k = owners.count(p) + 1
+        dirs[p] = list(np.linalg.qr(rng.standard_normal((Dj, k)))[0].T)
+    sent, q = [], nb
+    for p in owners:
+        sent.append(q)
+        u = dirs[p].pop()
+        w[q], var[q] = w[p], var[p]
+        # (offset and means on a grid of 2^-24: the mid-point of the tie class is exact, x - mu_p = mu_q - x)
+        mu[p] = np.ldexp(np.round(np.ldexp(mu[p], 24)), -24)
+        mu[q] = mu[p] + 2.0 * np.ldexp(np.round(np.ldexp(0.5 * _SENT_SIGMAS * np.sqrt(var[p]) * u, 24)), -24)
+        q += 1
+    if triple:
+        p = owners[-1]
+        u = dirs[p].pop()
+        w[q], var[q] = w[p], var[p]
+        mu[q] = mu[p] + _SENT_SIGMAS * np.sqrt(var[p]) * u
+        q += 1
+    Mu = q
+    w[Mu:] = 0.0                                                # (unused slots: weightless copies of mixture 0 far away)
+    mu[Mu:] = mu[0] + 1e3 * np.sqrt(var[0])
+    var[Mu:] = var[0]
+    # background draws
+    comp = rng.choice(nb, size=nbg, p=bw)
+    Xb = mu[comp] + rng.standard_normal((nbg, Dj)) * np.sqrt(var[comp])
+    Xs, cls, gap_out = [], [], []
+    for k, g in enumerate(gaps):
+        p, s = owners[k], sent[k]
+        if g == 0.0:                                            # exact tie: the mid-point of the means
+            X = np.repeat((0.5 * (mu[p] + mu[s]))[None], per_class, 0)
+            X[1:] += 1e-3 * np.sqrt(var[p]) * rng.standard_normal((per_class - 1, Dj)) * (mu[s] - mu[p] == 0)
+        else:
+            x0 = mu[p] + 0.5 * np.sqrt(var[p]) * rng.standard_normal((per_class, Dj))
+            seg = lambda t, x0=x0, s=s: x0 + t[:, None] * (mu[s] - x0)                     # noqa: E731
+
+            def pred(t, p=p, s=s, g=g, seg=seg):
+                L = estep_logdens(seg(t), w[[p, s]], mu[[p, s]], var[[p, s]])
+                return L[:, 0] - L[:, 1] >= g
+            t, _ = _bisect(pred, np.zeros(per_class), np.ones(per_class), 64)
+            X = seg(t)
+        L = estep_logdens(X, w[[p, s]], mu[[p, s]], var[[p, s]])
+        Xs.append(X)
+        cls.append(np.full(len(X), k))
+        gap_out.append(np.asarray(L[:, 0] - L[:, 1], dtype=np.float64))
+    if triple:
+        p, a, b = owners[-1], sent[-1], Mu - 1
+        # x = mu_p + alpha da + beta db equidistant from the three in the metric 1/var: two linear equations
+        S = np.sqrt(var[p])
+        da, db = (mu[a] - mu[p]) / S, (mu[b] - mu[p]) / S
+        G = np.array([[da @ da, da @ db], [da @ db, db @ db]])
+        al, be = np.linalg.solve(2.0 * G, np.array([da @ da, db @ db]))
+        X = np.repeat((mu[p] + S * (al * da + be * db))[None], per_class, 0)
+        Xs.append(X)
+        cls.append(np.full(per_class, ncls))
+        L = estep_logdens(X, w[[p, a]], mu[[p, a]], var[[p, a]])
+        gap_out.append(np.asarray(L[:, 0] - L[:, 1], dtype=np.float64))
+    # outliers and shifted frames (mixture 0 owns them)
+    per = max(per_class, 4)
+    Xo = [mu[0] + r * np.sqrt(var[0]) * rng.standard_normal((per, Dj)) / np.sqrt(Dj) for r in (1e2, 1e3, 1e4)]
+    d0 = mu[0] + rng.standard_normal((2 * per, Dj)) * np.sqrt(var[0])
+    Xo += [d0[:per] + 2000.0, d0[per:] - 2000.0, mu[1] + 0.1 * np.sqrt(var[0]) * rng.standard_normal((per, Dj))]
+    if base is None:
+        Xs += Xo
+        cls += [np.full(len(x), ncls + 1) for x in Xo]
+        gap_out += [np.full(len(x), np.nan) for x in Xo]
+    Xa = np.concatenate(Xs)
+    ca = np.concatenate(cls)
+    ga = np.concatenate(gap_out)
+    # the adversarial frames scattered among the p(x) draws, in a fixed random order
+    n = len(Xa)
+    pos = np.sort(rng.choice(nbg + n, n, replace=False))
+    X = np.empty((nbg + n, Dj))
+    c = np.full(nbg + n, -1)
+    gg = np.full(nbg + n, np.nan)
+    mask = np.zeros(nbg + n, bool)
+    mask[pos] = True
+    perm = rng.permutation(n)
+    X[mask], c[mask], gg[mask] = Xa[perm], ca[perm], ga[perm]
+    X[~mask] = Xb
+    return dict(w=w, mu=mu, var=var, X=np.ascontiguousarray(X), cls=c, gap=gg, sent=np.array(sent), owner=np.array(owners),
+                gaps=np.array(gaps), Mu=Mu, nb=nb)

@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 from conftest import load_golden, relerr
+from test_gpu_estep_adversarial import per_mixture_err
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-9
@@ -326,6 +327,7 @@ def test_hard_assignment_path_all_frames_owned(vc, N, Dj, M, sep, zw):
     assert all(np.array_equal(p, q) for p, q in zip(a[:3], b[:3])) and a[3] == b[3]
     r0, r1, r2, rl = co.estep_diag(X, w, mu, var)
     assert relerr(a[0], r0) < TOL and relerr(a[1], r1.T) < TOL and relerr(a[2], r2.T) < TOL
+    assert per_mixture_err(a[:3], (r0, r1.T, r2.T)).max() <= TOL, per_mixture_err(a[:3], (r0, r1.T, r2.T)).max()
     assert abs(a[3] - rl) < TOL * abs(rl)
     assert abs(a[0].sum() - N) < 1e-6
     if M <= 16:                                               # the library's own choice for one mixture tile: the FP64 kernel
@@ -360,6 +362,7 @@ def test_hard_assignment_path_mixed_frames(vc, N, Dj, M):
     assert all(np.array_equal(p, q) for p, q in zip(a[:3], b[:3])) and a[3] == b[3]
     r0, r1, r2, rl = co.estep_diag(X, w, mu, var)
     assert relerr(a[0], r0) < TOL and relerr(a[1], r1.T) < TOL and relerr(a[2], r2.T) < TOL
+    assert per_mixture_err(a[:3], (r0, r1.T, r2.T)).max() <= TOL, per_mixture_err(a[:3], (r0, r1.T, r2.T)).max()
     assert abs(a[3] - rl) < TOL * abs(rl)
 
 
@@ -449,6 +452,7 @@ def test_hard_assignment_path_tight_variances(vc, Dj, M):
     assert abs(a[3] - o[3]) < 1e-10 * abs(o[3])
     r0, r1, r2, rl = co.estep_diag(X, w, mu, var)
     assert relerr(a[0], r0) < TOL and relerr(a[1], r1.T) < TOL and relerr(a[2], r2.T) < TOL
+    assert per_mixture_err(a[:3], (r0, r1.T, r2.T)).max() <= TOL, per_mixture_err(a[:3], (r0, r1.T, r2.T)).max()
     assert abs(a[3] - rl) < TOL * abs(rl)
     assert abs(a[3] - rl) <= abs(o[3] - rl) + 1e-13 * abs(rl), (a[3] - rl, o[3] - rl)
 
@@ -472,6 +476,7 @@ def test_hard_assignment_path_a_handful_of_shared_frames(vc):
     assert abs(a[3] - o[3]) < 1e-12 * abs(o[3])
     r0, r1, r2, rl = co.estep_diag(X, w, mu, var)
     assert relerr(a[0], r0) < TOL and relerr(a[1], r1.T) < TOL and relerr(a[2], r2.T) < TOL
+    assert per_mixture_err(a[:3], (r0, r1.T, r2.T)).max() <= TOL, per_mixture_err(a[:3], (r0, r1.T, r2.T)).max()
     assert abs(a[3] - rl) < TOL * abs(rl)
     assert abs(a[0].sum() - N) < 1e-6
 
@@ -499,6 +504,7 @@ def test_small_models_take_the_small_workgroups(vc, Dj, M, N):
     new, again, old = run(0), run(0), run(_lib.DBG_ESTEP_NO_SMALL)
     for got in (new, old):
         assert relerr(got[0], r[0]) < TOL and relerr(got[1], r[1].T) < TOL and relerr(got[2], r[2].T) < TOL
+        assert per_mixture_err(got[:3], (r[0], r[1].T, r[2].T)).max() <= TOL, per_mixture_err(got[:3], (r[0], r[1].T, r[2].T)).max()
         assert abs(got[3] - r[3]) < TOL * abs(r[3])
     assert abs(new[0].sum() - N) < 1e-9 * N
     assert all(np.array_equal(a, b) for a, b in zip(new[:3], again[:3])) and new[3] == again[3]      # a function of the data alone
@@ -526,6 +532,7 @@ def test_small_model_on_the_reference_model_and_its_paths(vc, joint_model):
         finally:
             vc.estep_set_path(vc.ESTEP_AUTO)
         assert relerr(S0, r0) < TOL and relerr(S1, r1.T) < TOL and relerr(S2, r2.T) < TOL
+        assert per_mixture_err((S0, S1, S2), (r0, r1.T, r2.T)).max() <= TOL, per_mixture_err((S0, S1, S2), (r0, r1.T, r2.T)).max()
         assert abs(ll - rl) < TOL * abs(rl)
         if path == vc.ESTEP_HARD:                # (-1: the one-kernel path; otherwise the number of soft frames)
             assert 0 <= _lib.estep_last_soft() <= N

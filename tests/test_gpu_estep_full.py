@@ -70,7 +70,14 @@ def test_frame_lists_of_the_statistics_kernel(vc, N, Dj, M, lam_lo):
         _lib.debug_force(0)
     assert float((a - b).abs().max() / b.abs().max()) < 1e-12
     if N * M <= 600_000:
-        _check(vc.estep_full(X.T, w, mu.T, sg), co.estep_full(X, w, mu, sig), N)
+        ref = co.estep_full(X, w, mu, sig)
+        _check(vc.estep_full(X.T, w, mu.T, sg), ref, N)
+        # per mixture (the M-step divides by each S0[m]): lists on and off
+        from test_gpu_estep_adversarial import per_mixture_err
+        r = (ref[0], ref[1].T, np.transpose(ref[2], (2, 1, 0)))
+        for st in (a, b):
+            S0, S1, S2, _ = vc.unpack_full_stats(st.cpu().numpy(), Dj, M)
+            assert per_mixture_err((S0, S1, S2), r).max() <= TOL, per_mixture_err((S0, S1, S2), r).max()
 
 
 def test_zero_weight_and_not_pd(vc):

@@ -1038,6 +1038,7 @@ static int estep_device_run(const double *dX, int64_t N, int Dj, int M, const do
   if (N < 0 || Dj < 1 || M < 1) return fail(VCMI_ERR_DIM, "E-step: N=%lld Dj=%d M=%d invalid", (long long)N, Dj, M);
   if (!w || !mu || !var || !dstats || (N > 0 && !dX)) return fail(VCMI_ERR_ARG, "E-step: NULL argument");
   EstepScratch &sc = scratch();
+  sc.last_hard = false;            // (vcmi_debug_estep_last_soft: the groups and the generic kernels never take the hard path)
   const int64_t plen = (int64_t)M * (1 + 2 * Dj) + 1;
   for (int m = 0; m < M; ++m)
     for (int d = 0; d < Dj; ++d)

@@ -29,6 +29,12 @@ namespace vcmi {
 
 constexpr int kHardPiece = 256;        // hard frames per workgroup of the statistics kernel
 constexpr int kHardMaxM = 128;         // mixtures (the one-kernel path's limit; more go through the groups of estep_mfma_groups_launch)
+// Largest margin the key kernel trusts.  With NWmax < 2^114 every W operand is a finite float (|W_m| <= 2^12 NWmax), and with
+// E = NWmax |[x^2 ; x]| + NCmax < 2^114 every product and partial sum of l^ stays below 2^127 < FLT_MAX (|c_m| <= 2^12 E,
+// sum |W_m,i z_i| <= |W_m| |z| <= 2^12 E).  Beyond it an operand or a product can overflow FP32: l^ turns -inf or NaN, and a NaN
+// drops out of the best / second-best comparison -- a mixture with var < ~1.5e-39 (-1/(2 var) is -inf in FP32) could own a
+// frame that is then certified "hard" to another mixture.  Such frames are left soft.
+constexpr float kHardFinite = 0x1p114f;
 // W in bf16 for the key kernel: per mixture tile mt (16 mixtures) and instruction i (x dimensions 16 i .. 16 i + 15):
 // [hi 64 x 16 B | lo 64 x 16 B]; slot j of lane group g <-> j < 4: -1/(2 var) of dimension 16 i + 4 g + j (multiplies x^2),
 // j >= 4: mu / var of dimension 16 i + 4 g + (j - 4) (multiplies x).  Then per tile 48 floats: c (16), 2^-12 |W_m| (16, rounded
@@ -71,7 +77,7 @@ estep_hard_prep_kernel(const double *__restrict__ raw, const double *__restrict_
     const int mt = m >> 4, r = m & 15;
     float *cf = reinterpret_cast<float *>(W16 + (size_t)mt * C::TILE_BYTES + (size_t)C::NI * 2048);
     const double c = m < M ? cinit[m] : -INFINITY;
-    const bool dead = !(c > -INFINITY);
+    const bool dead = c == -INFINITY;                                 // (a NaN c is not dead: its margin below is infinite)
     double q = 0.0;
     if (!dead)
       for (int d = lane; d < dj; d += 64) {
@@ -81,7 +87,8 @@ estep_hard_prep_kernel(const double *__restrict__ raw, const double *__restrict_
 #pragma unroll
     for (int sh = 1; sh < 64; sh <<= 1) q += __shfl_xor(q, sh);
     if (lane == 0) {
-      auto up = [](double v) { return __uint_as_float(__float_as_uint((float)(v * (1.0 + 0x1p-20))) + 1u); };      // next float up (v >= 0)
+      // next float up (v >= 0); infinite for NaN and for anything at or beyond kHardFinite (the key kernel then settles no frame)
+      auto up = [](double v) { return v < (double)kHardFinite ? __uint_as_float(__float_as_uint((float)(v * (1.0 + 0x1p-20))) + 1u) : INFINITY; };
       cf[r] = dead ? -1e30f : (float)c;
       cf[16 + r] = dead ? 0.0f : up(sqrt(q) * 0x1p-12);
       cf[32 + r] = dead ? 0.0f : up(fabs(c) * 0x1p-12);
@@ -121,6 +128,7 @@ estep_hard_key_kernel(const unsigned char *__restrict__ W16, int M, int dj, cons
     nwmax = fmaxf(nwmax, __shfl_xor(nwmax, sh));
     ncmax = fmaxf(ncmax, __shfl_xor(ncmax, sh));
   }
+  if (!(nwmax < kHardFinite)) ncmax = INFINITY;                  // a W operand may not be a finite float: no frame is hard
   constexpr int kPasses = kGroupChunk / (16 * 2 * (kHardKeyThreads / 64));
   for (int64_t cu = blockIdx.x; cu < nrun; cu += gridDim.x) {
     const int64_t c = split ? cu / kPasses : cu;
@@ -249,12 +257,12 @@ estep_hard_key_kernel(const unsigned char *__restrict__ W16, int M, int dj, cons
           bm[f] = take ? om : bm[f];
           b1[f] = take ? o1 : b1[f];
         }
-        const float E = fmaf(nwmax, nxe[f], ncmax) * 1.000001f;
+        const float E = fmaf(nwmax, nxe[f], ncmax) * 1.000001f;       // (NaN or infinite where kHardFinite is not met)
         const float blo = b1[f] - E, hi2 = b2[f] + E;
         if (lgrp == 0 && fr < N) {
           // hard: every other mixture is certified more than 746 nats below the best one (exp underflows to exactly 0 below
           // -745.2; the margin also covers the 1e-7 the one-kernel path's own log-densities may be off), and the best is finite
-          const bool hard = bm[f] < M && blo > -1e29f && hi2 < blo - 746.0f;
+          const bool hard = bm[f] < M && blo > -1e29f && hi2 < blo - 746.0f && E < kHardFinite;
           const int k = hard ? bm[f] : M;
           if (key) key[fr] = k;
           atomicAdd(&hist[k], 1);
