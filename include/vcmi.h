@@ -238,6 +238,54 @@ int vcmi_gmm_em_estep_dev(vcmi_gmm_em *h, const double *dX, int64_t N, double *d
 int vcmi_gmm_em_mstep(vcmi_gmm_em *h, const double *dstats, void *stream, double *loglik);
 int vcmi_gmm_em_get(vcmi_gmm_em *h, double *w, double *mu, double *sigma);
 
+/* k-means -- sklearn 0.17 cluster.KMeans, what GMM(init_params="wmc") runs over all of X before the first E-step
+ * (bin/train_gmm.jl:84-89).  Centers (Dj,M) column-major, 1 <= Dj <= 256, 1 <= M <= 1024; every distance is the direct
+ * difference sum_d (x_d - c_d)^2 (sequential in d, FP64, no contraction); exact ties go to the smaller center index.
+ * dX is a dense (Dj,N) DEVICE block (leading dimension Dj).  The handle keeps mind2 (N doubles) and labels (N ints) of
+ * the last assignment or seeding pass, so the far / seed calls that follow must pass the same block.
+ * Footprint: 3 Dj M + 70 ceil(M/16) ceil(Dj/4) doubles, 12 bytes per frame, statistics partials of at most 128 MB.
+ * Summation is deterministic: fixed-order partials, no floating-point atomics.
+ *
+ * Lloyd iteration (per rank; what crosses ranks is marked):
+ *   vcmi_kmeans_assign_dev   local statistics [count (M) | sum x (Dj,M) | inertia] of vcmi_kmeans_stats_len doubles,
+ *                            asynchronous; dlabels (N int32, may be NULL) receives the labels.  -> ALL-REDUCE (sum)
+ *   vcmi_kmeans_update       centers = sum x / count; returns the summed inertia and the number of empty clusters
+ *                            (one synchronising read).  With no empty cluster it also returns the summed squared shift.
+ *   (n_empty > 0) vcmi_kmeans_far_dev  this rank's top-n_empty records [mind2, global frame index, x (Dj)] by mind2
+ *                            (ties: smaller index; `offset` = global index of the rank's first frame) -> ALL-GATHER
+ *                 vcmi_kmeans_relocate  the e-th empty cluster takes the e-th best of the ncand gathered records; shift
+ *   The handle tracks the centers of the lowest inertia (as sklearn's best_centers); vcmi_kmeans_restore_best makes them
+ *   current for the final relabelling pass.
+ * Greedy k-means++ (sklearn _k_init): the host draws every random number.
+ *   vcmi_kmeans_seed_commit  center c <- dcenter (Dj, device); mind2 = min(mind2, |x - c|^2) (c == 0: reset);
+ *                            *potential = local sum of mind2                                   -> ALL-GATHER (1 double)
+ *   vcmi_kmeans_seed_pick    idx[l] = first local frame whose inclusive prefix of mind2 reaches targets[l] (host values
+ *                            u_l * potential minus the potential of the ranks before); N - 1 past the end.  The rank that
+ *                            owns a pick sends that frame (Dj doubles) to the others.
+ *   vcmi_kmeans_seed_trials  local potential sum min(mind2, |x - cand_l|^2) of L <= 16 device candidates cand (Dj,L) in one
+ *                            pass                                                             -> ALL-REDUCE (L doubles)
+ * VCMI_ERR_ARG for non-finite frames or centers (reported by update / seed_commit), VCMI_ERR_DIM for bad shapes. */
+typedef struct vcmi_kmeans vcmi_kmeans;
+int64_t vcmi_kmeans_stats_len(int Dj, int M);
+int vcmi_kmeans_create(int Dj, int M, const double *centers0, vcmi_kmeans **out);
+int vcmi_kmeans_destroy(vcmi_kmeans *h);
+int vcmi_kmeans_set(vcmi_kmeans *h, const double *centers);
+int vcmi_kmeans_get(vcmi_kmeans *h, double *centers);
+int vcmi_kmeans_restore_best(vcmi_kmeans *h);
+int vcmi_kmeans_assign_dev(vcmi_kmeans *h, const double *dX, int64_t N, double *dstats, int *dlabels, void *stream);
+int vcmi_kmeans_update(vcmi_kmeans *h, const double *dstats, void *stream, double *shift, double *inertia, int *n_empty);
+int vcmi_kmeans_far_dev(vcmi_kmeans *h, const double *dX, int64_t N, int E, int64_t offset, double *drec, void *stream);
+int vcmi_kmeans_relocate(vcmi_kmeans *h, const double *dstats, const double *dcand, int64_t ncand, void *stream,
+                         double *shift);
+int vcmi_kmeans_seed_commit(vcmi_kmeans *h, const double *dX, int64_t N, int c, const double *dcenter, void *stream,
+                            double *potential);
+int vcmi_kmeans_seed_pick(vcmi_kmeans *h, int L, const double *targets, void *stream, int64_t *idx);
+int vcmi_kmeans_seed_trials(vcmi_kmeans *h, const double *dX, int64_t N, const double *dcand, int L, void *stream,
+                            double *potentials);
+/* copy of the handle's mind2 (direct-difference squared distance to the nearest center, N doubles) of the last assignment
+ * or seeding pass over a block of N frames, into the device buffer dmind2; asynchronous on `stream` */
+int vcmi_kmeans_mind2_dev(vcmi_kmeans *h, int64_t N, double *dmind2, void *stream);
+
 /* ---------------------------------------------------------------------------------------------
  * TrajectoryGMMMap -- src/trajectory_gmmmap.jl:3-110, vc src/common.jl:31-63, push_delta src/datasets.jl:6-13
  * ------------------------------------------------------------------------------------------- */

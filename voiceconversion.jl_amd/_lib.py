@@ -98,6 +98,20 @@ SIGNATURES = {
     "vcmi_gmm_em_estep_dev": (_int, [_vp, _vp, _i64, _vp, _vp]),
     "vcmi_gmm_em_mstep": (_int, [_vp, _vp, _vp, _dp]),
     "vcmi_gmm_em_get": (_int, [_vp, _dp, _dp, _dp]),
+    "vcmi_kmeans_stats_len": (_i64, [_int, _int]),
+    "vcmi_kmeans_create": (_int, [_int, _int, _dp, C.POINTER(_vp)]),
+    "vcmi_kmeans_destroy": (_int, [_vp]),
+    "vcmi_kmeans_set": (_int, [_vp, _dp]),
+    "vcmi_kmeans_get": (_int, [_vp, _dp]),
+    "vcmi_kmeans_restore_best": (_int, [_vp]),
+    "vcmi_kmeans_assign_dev": (_int, [_vp, _vp, _i64, _vp, _vp, _vp]),
+    "vcmi_kmeans_update": (_int, [_vp, _vp, _vp, _dp, _dp, C.POINTER(_int)]),
+    "vcmi_kmeans_far_dev": (_int, [_vp, _vp, _i64, _int, _i64, _vp, _vp]),
+    "vcmi_kmeans_relocate": (_int, [_vp, _vp, _vp, _i64, _vp, _dp]),
+    "vcmi_kmeans_seed_commit": (_int, [_vp, _vp, _i64, _int, _vp, _vp, _dp]),
+    "vcmi_kmeans_seed_pick": (_int, [_vp, _int, _dp, _vp, _ip]),
+    "vcmi_kmeans_seed_trials": (_int, [_vp, _vp, _i64, _vp, _int, _vp, _dp]),
+    "vcmi_kmeans_mind2_dev": (_int, [_vp, _i64, _vp, _vp]),
     "vcmi_traj_create": (_int, [_vp, _i64, C.POINTER(_vp)]),
     "vcmi_traj_destroy": (_int, [_vp]),
     "vcmi_traj_length": (_i64, [_vp]),

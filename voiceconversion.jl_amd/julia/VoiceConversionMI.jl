@@ -24,7 +24,9 @@ export DeviceMatrix, FrameByFrameConverter, TrajectoryConverter, GMMMapParam, GM
        align, align_mcep, push_delta, GVDataset,
        DTW, fit!, update!, set_template!, backward,
        predict_proba, predict_proba!, predict, predict!, diffgmm,
-       estep_diag, estep_full, estep_set_path, estep_get_path, ESTEP_AUTO, ESTEP_HARD, ESTEP_SOFT, GMMEM, estep!, mstep!, params, set_devices, device_count, set_prune!, convert_plan, pin!, unpin!, ispinned
+       estep_diag, estep_full, estep_set_path, estep_get_path, ESTEP_AUTO, ESTEP_HARD, ESTEP_SOFT, GMMEM, estep!, mstep!, params, KMeansState, kmeans_stats_len, kmeans_assign!, kmeans_update!, kmeans_far!,
+       kmeans_relocate!, kmeans_seed_commit!, kmeans_seed_pick, kmeans_seed_trials!, kmeans_mind2!, kmeans_restore_best!, kmeans_centers,
+       kmeans!, set_devices, device_count, set_prune!, convert_plan, pin!, unpin!, ispinned
 
 const libvcmi = get(ENV, "LIBVCMI", "libvcmi")
 
@@ -639,6 +641,109 @@ function params(em::GMMEM)
     w = Vector{Float64}(undef, em.M); μ = Matrix{Float64}(undef, em.Dj, em.M); Σ = Array{Float64,3}(undef, em.Dj, em.Dj, em.M)
     check(ccall((:vcmi_gmm_em_get, libvcmi), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}), em.h, w, μ, Σ))
     w, μ, Σ
+end
+
+# ------------------------------------------------------------------------------------- device k-means
+# sklearn 0.17 KMeans over every frame (what GMM(init_params="wmc") runs before the EM loop, bin/train_gmm.jl:84-89);
+# include/vcmi.h documents each call and what crosses ranks.  `dX` is a dense (Dj,N) device block, the other `d*`
+# arguments device buffers (e.g. from AMDGPU.jl).  The multi-rank driver (seeding, gathers) lives in the Python
+# package (kmeans.py); `kmeans!` below is the single-device Lloyd loop from given centers.
+mutable struct KMeansState
+    h::Ptr{Cvoid}
+    Dj::Int
+    M::Int
+    function KMeansState(centers::Matrix{Float64})
+        Dj, M = size(centers)
+        h = Ref{Ptr{Cvoid}}(C_NULL)
+        check(ccall((:vcmi_kmeans_create, libvcmi), Cint, (Cint, Cint, Ptr{Float64}, Ref{Ptr{Cvoid}}), Dj, M, centers, h))
+        km = new(h[], Dj, M)
+        finalizer(k -> ccall((:vcmi_kmeans_destroy, libvcmi), Cint, (Ptr{Cvoid},), k.h), km)
+        km
+    end
+end
+
+kmeans_stats_len(Dj::Integer, M::Integer) = ccall((:vcmi_kmeans_stats_len, libvcmi), Int64, (Cint, Cint), Dj, M)
+
+kmeans_assign!(km::KMeansState, dX::Ptr{Float64}, N::Integer, dstats::Ptr{Float64};
+               dlabels::Ptr{Cint}=Ptr{Cint}(C_NULL), stream::Ptr{Cvoid}=C_NULL) =
+    check(ccall((:vcmi_kmeans_assign_dev, libvcmi), Cint, (Ptr{Cvoid}, Ptr{Float64}, Int64, Ptr{Float64}, Ptr{Cint}, Ptr{Cvoid}),
+                km.h, dX, N, dstats, dlabels, stream))
+
+function kmeans_update!(km::KMeansState, dstats::Ptr{Float64}; stream::Ptr{Cvoid}=C_NULL)
+    shift = Ref{Float64}(0.0); inertia = Ref{Float64}(0.0); nempty = Ref{Cint}(0)
+    check(ccall((:vcmi_kmeans_update, libvcmi), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Cvoid}, Ref{Float64}, Ref{Float64}, Ref{Cint}),
+                km.h, dstats, stream, shift, inertia, nempty))
+    shift[], inertia[], Int(nempty[])
+end
+
+kmeans_far!(km::KMeansState, dX::Ptr{Float64}, N::Integer, E::Integer, offset::Integer, drec::Ptr{Float64};
+            stream::Ptr{Cvoid}=C_NULL) =
+    check(ccall((:vcmi_kmeans_far_dev, libvcmi), Cint, (Ptr{Cvoid}, Ptr{Float64}, Int64, Cint, Int64, Ptr{Float64}, Ptr{Cvoid}),
+                km.h, dX, N, E, offset, drec, stream))
+
+function kmeans_relocate!(km::KMeansState, dstats::Ptr{Float64}, dcand::Ptr{Float64}, ncand::Integer; stream::Ptr{Cvoid}=C_NULL)
+    shift = Ref{Float64}(0.0)
+    check(ccall((:vcmi_kmeans_relocate, libvcmi), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Int64, Ptr{Cvoid}, Ref{Float64}),
+                km.h, dstats, dcand, ncand, stream, shift))
+    shift[]
+end
+
+function kmeans_seed_commit!(km::KMeansState, dX::Ptr{Float64}, N::Integer, c::Integer, dcenter::Ptr{Float64};
+                             stream::Ptr{Cvoid}=C_NULL)
+    pot = Ref{Float64}(0.0)
+    check(ccall((:vcmi_kmeans_seed_commit, libvcmi), Cint,
+                (Ptr{Cvoid}, Ptr{Float64}, Int64, Cint, Ptr{Float64}, Ptr{Cvoid}, Ref{Float64}),
+                km.h, dX, N, c, dcenter, stream, pot))
+    pot[]
+end
+
+function kmeans_seed_pick(km::KMeansState, targets::Vector{Float64}; stream::Ptr{Cvoid}=C_NULL)
+    idx = Vector{Int64}(undef, length(targets))
+    check(ccall((:vcmi_kmeans_seed_pick, libvcmi), Cint, (Ptr{Cvoid}, Cint, Ptr{Float64}, Ptr{Cvoid}, Ptr{Int64}),
+                km.h, length(targets), targets, stream, idx))
+    idx                                           # 0-based frame indices of this block
+end
+
+function kmeans_seed_trials!(km::KMeansState, dX::Ptr{Float64}, N::Integer, dcand::Ptr{Float64}, L::Integer;
+                             stream::Ptr{Cvoid}=C_NULL)
+    pots = Vector{Float64}(undef, L)
+    check(ccall((:vcmi_kmeans_seed_trials, libvcmi), Cint,
+                (Ptr{Cvoid}, Ptr{Float64}, Int64, Ptr{Float64}, Cint, Ptr{Cvoid}, Ptr{Float64}),
+                km.h, dX, N, dcand, L, stream, pots))
+    pots
+end
+
+kmeans_mind2!(km::KMeansState, N::Integer, dmind2::Ptr{Float64}; stream::Ptr{Cvoid}=C_NULL) =
+    check(ccall((:vcmi_kmeans_mind2_dev, libvcmi), Cint, (Ptr{Cvoid}, Int64, Ptr{Float64}, Ptr{Cvoid}), km.h, N, dmind2, stream))
+
+kmeans_restore_best!(km::KMeansState) = check(ccall((:vcmi_kmeans_restore_best, libvcmi), Cint, (Ptr{Cvoid},), km.h))
+
+function kmeans_centers(km::KMeansState)
+    C = Matrix{Float64}(undef, km.Dj, km.M)
+    check(ccall((:vcmi_kmeans_get, libvcmi), Cint, (Ptr{Cvoid}, Ptr{Float64}), km.h, C))
+    C
+end
+
+"""kmeans!(km, dX, N, dstats, drec; max_iter=300, tol=0.0) -> (centers, n_iter): Lloyd from km's centers on one
+device until the summed squared shift is <= tol (an absolute value), then one relabelling pass.  dstats: kmeans_stats_len
+doubles, whose last entry holds the final inertia on return; drec: km.M * (km.Dj + 2) doubles (relocation records);
+dlabels (optional): N Cint, the final labels."""
+function kmeans!(km::KMeansState, dX::Ptr{Float64}, N::Integer, dstats::Ptr{Float64}, drec::Ptr{Float64};
+                 max_iter::Integer=300, tol::Float64=0.0, dlabels::Ptr{Cint}=Ptr{Cint}(C_NULL))
+    n_iter = 0
+    for it in 1:max_iter
+        n_iter = it
+        kmeans_assign!(km, dX, N, dstats)
+        shift, _, ne = kmeans_update!(km, dstats)
+        if ne > 0
+            kmeans_far!(km, dX, N, ne, 0, drec)
+            shift = kmeans_relocate!(km, dstats, drec, ne)
+        end
+        shift <= tol && break
+    end
+    kmeans_restore_best!(km)
+    kmeans_assign!(km, dX, N, dstats; dlabels=dlabels)
+    kmeans_centers(km), n_iter
 end
 
 end # module

@@ -4,9 +4,15 @@ optionally refined from a saved model, :92-99).
 
 The hot loop (E-step statistics, M-step, Cholesky whitening of every mixture) never leaves HBM; with a
 torch.distributed process group every rank holds a shard of the frames and the only exchange per iteration is ONE
-all-reduce of the packed statistics.  Initialisation (k-means on a subsample, as the old sklearn GMM's
-init_params="wmc" does on the CPU) is host-side numpy: it is not part of the hot path and, being random, is not
-something the reference pins either.
+all-reduce of the packed statistics.
+
+Initialisation.  The old sklearn GMM's init_params="wmc" runs KMeans over ALL of X (k-means++ seeding, n_init=10) and
+takes np.cov of all of X for every mixture.  Two initialisations are offered:
+  * init="subsample" (the default, unchanged): host-side numpy on a random subsample of rank 0's shard -- one plain
+    k-means++ seeding and 10 Lloyd iterations, np.cov of the same subsample.  An approximation of sklearn's, cheap
+    on the CPU.
+  * init="kmeans": sklearn's semantics on the device -- kmeans(X, M) over every frame of every rank (kmeans.py) and
+    cov(X) + min_covar I (ddof=1) over every frame, from the M=1 full E-step statistics (N, sum x, sum x x').
 """
 import ctypes as C
 
@@ -14,7 +20,8 @@ import numpy as np
 
 from . import _lib
 from ._arrays import current_stream_ptr, dev_matrix, jl_matrix, jl_vector
-from .estep import full_stats_len, unpack_full_stats
+from .estep import estep_full_dev, full_stats_len, unpack_full_stats
+from .kmeans import kmeans
 
 
 class EMState:
@@ -83,14 +90,30 @@ def kmeans_init(Xs, M, rng, n_iter=10):
     return Cn
 
 
+def data_covariance(X, group=None):
+    """cov(X) (ddof=1, as np.cov) over every frame of every rank, from the M=1 full E-step statistics."""
+    import torch.distributed as dist
+
+    Dj = X.shape[0]
+    st = estep_full_dev(X, np.ones(1), np.zeros((Dj, 1)), np.eye(Dj)[:, :, None])
+    if dist.is_available() and dist.is_initialized():
+        dist.all_reduce(st, group=group)
+    S0, S1, S2, _ = unpack_full_stats(st.cpu().numpy(), Dj, 1)
+    n, s1 = S0[0], S1[:, 0]
+    cv = (S2[:, :, 0] - np.outer(s1, s1) / n) / (n - 1.0)
+    return 0.5 * (cv + cv.T)
+
+
 def train_gmm(X, n_components=16, n_iter=200, n_init=2, min_covar=1e-7, tol=1e-3, refine=None, seed=0, group=None,
-              init_sample=50000):
+              init_sample=50000, init="subsample"):
     """train_gmm.jl's `gmm[:fit]`: X is this rank's (Dj,N) device-resident shard of the joint features.
 
     n_init random initialisations (k-means means, uniform weights, the data covariance + min_covar*I for every
     mixture -- the old sklearn GMM's init_params='wmc'), each run for at most n_iter EM iterations or until the mean
     log-likelihood per frame changes by less than tol; the best final log-likelihood wins.  refine=(w, mu, Sigma)
-    starts from a pretrained model instead (bin/train_gmm.jl:92-99, init_params='').
+    starts from a pretrained model instead (bin/train_gmm.jl:92-99, init_params='').  init="kmeans" takes the means from
+    kmeans over every frame of every rank and the covariance of every frame (see the module docstring); the default
+    "subsample" keeps the host-side subsample initialisation.
     Returns {"weights", "means" (Dj,M), "covars" (Dj,Dj,M), "n_components", "loglik" (per-frame history), "converged"}.
     """
     import torch
@@ -104,11 +127,19 @@ def train_gmm(X, n_components=16, n_iter=200, n_init=2, min_covar=1e-7, tol=1e-3
     if distributed:
         dist.all_reduce(ntot, group=group)
     ntot = float(ntot.item())
+    if init not in ("subsample", "kmeans"):
+        raise ValueError(f"train_gmm: init must be 'subsample' or 'kmeans', got {init!r}")
     rng = np.random.default_rng(seed)
+    cv_all = data_covariance(X, group) + min_covar * np.eye(Dj) if init == "kmeans" and refine is None else None
     best = None
-    for init in range(1 if refine is not None else max(1, int(n_init))):
+    for _ in range(1 if refine is not None else max(1, int(n_init))):
         if refine is not None:
             w0, mu0, sig0 = refine
+        elif init == "kmeans":
+            # every rank runs the same collective k-means and gets the same centers: nothing to broadcast
+            mu0 = kmeans(X, M, seed=int(rng.integers(2**31 - 1)), group=group)["centers"]
+            sig0 = np.repeat(cv_all[:, :, None], M, axis=2)
+            w0 = np.full(M, 1.0 / M)
         else:
             # rank 0 draws the initial model from its shard and every rank receives the same one
             pk = torch.empty(M * (1 + Dj + Dj * Dj), dtype=torch.float64, device=X.device)
@@ -143,4 +174,4 @@ def train_gmm(X, n_components=16, n_iter=200, n_init=2, min_covar=1e-7, tol=1e-3
     return {"weights": w, "means": mu, "covars": sigma, "n_components": M, "loglik": hist, "converged": converged}
 
 
-__all__ = ["EMState", "train_gmm", "kmeans_init", "unpack_full_stats"]
+__all__ = ["EMState", "train_gmm", "kmeans_init", "data_covariance", "unpack_full_stats"]
