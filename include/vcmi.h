@@ -362,6 +362,32 @@ int vcmi_parallel_dataset_dev(int64_t n, const double *const *src, const int64_t
                               int remove_silence, int ignore0th, int add_delta, int diff, double *dXY,
                               int64_t capacity_frames, int64_t *nframes, int64_t *counts);
 
+/* ---------------------------------------------------------------------------------------------
+ * Spectral envelopes into and out of vc: sp2mc, mc2sp, mc2b of MelGeneralizedCepstrums (third party)
+ * ------------------------------------------------------------------------------------------- */
+/* sp2mc(sp, order, alpha) -- call sites test/vc.jl:16, bin/vc.jl:71, bin/mcep.jl:50.  sp (K,T) power spectra (K = fftlen/2+1,
+ * 2 <= K <= 4097), mc (order+1,T), 1 <= order+1 <= 256, |alpha| < 1: per column c = irfft(log sp, 2(K-1)), c[0] /= 2,
+ * mc = freqt(c, order, alpha) over all 2(K-1) entries.  VCMI_ERR_ARG if an entry of sp is not positive and finite
+ * (Julia's log throws); the check rides on the kernel's own reads.
+ * mc2sp(mc, alpha, fftlen) -- call sites test/vc.jl:28, bin/vc.jl:87.  mc (D,T), 1 <= D <= 256, 2 <= fftlen <= 8193 (odd
+ * lengths included: the reference passes 2 size(sp,1) - 1), sp (fftlen/2+1,T): per column c = freqt(mc, fftlen/2, -alpha),
+ * c[0] *= 2, sp = exp(real(rfft(symmetric vector of c))).
+ * mc2b(mc, alpha) -- call sites test/diffvc.jl:33, bin/diffvc.jl:83.  mc, b (D,T): b[D-1] = mc[D-1],
+ * b[i] = mc[i] - alpha b[i+1].
+ * Host pointers: per-thread scratch, staged upload, kernel, download (like vcmi_mc2e).  `_dev` variants take DEVICE-RESIDENT
+ * matrices with leading dimensions (>= the column length), are asynchronous on `stream` and do NOT check the values of
+ * their input (a non-positive power gives NaN or -inf).  All six run on the calling thread's device: the device group of
+ * vcmi_set_devices is not used.  T = 0 is a no-op. */
+int vcmi_sp2mc(const double *sp, int K, int64_t T, int order, double alpha, double *mc);
+int vcmi_sp2mc_dev(const double *dsp, int64_t lds, int K, int64_t T, int order, double alpha,
+                   double *dmc, int64_t ldm, void *stream);
+int vcmi_mc2sp(const double *mc, int D, int64_t T, double alpha, int fftlen, double *sp);
+int vcmi_mc2sp_dev(const double *dmc, int64_t ldm, int D, int64_t T, double alpha, int fftlen,
+                   double *dsp, int64_t lds, void *stream);
+int vcmi_mc2b(const double *mc, int D, int64_t T, double alpha, double *b);
+int vcmi_mc2b_dev(const double *dmc, int64_t ldm, int D, int64_t T, double alpha,
+                  double *db, int64_t ldb, void *stream);
+
 /* GVDataset(path; ignore0th, add_delta, nmax) from in-memory feature matrices -- src/datasets.jl:134-183 (the file loop
  * is the caller's): per utterance tgt = fm[i] (D,T[i]) without row 1 (ignore0th), with push_delta (add_delta);
  * gv = var(tgt, 2) (corrected, Julia's default); an utterance whose variance has a NaN (T = 1) is skipped as the

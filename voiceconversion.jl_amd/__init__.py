@@ -21,3 +21,4 @@ from .train import EMState, train_gmm  # noqa: F401,E402
 from .kmeans import KMeansState, kmeans  # noqa: F401,E402
 from .gv import VarianceScaling, diffgmm, fvpostf, fvpostf_  # noqa: F401,E402
 from .datasets import GVDataset, ParallelDataset, align_mcep, mc2e  # noqa: F401,E402
+from .mgc import mc2b, mc2sp, sp2mc  # noqa: F401,E402

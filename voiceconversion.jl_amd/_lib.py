@@ -131,6 +131,12 @@ SIGNATURES = {
     "vcmi_variance_scaling_dev": (_int, [_vp, _i64, _int, _i64, _dp, _vp, _i64, _vp]),
     "vcmi_diffgmm": (_int, [_dp, _dp, _int, _int, _dp, _dp]),
     "vcmi_mc2e": (_int, [_dp, _int, _i64, C.c_double, _int, _dp]),
+    "vcmi_sp2mc": (_int, [_dp, _int, _i64, _int, C.c_double, _dp]),
+    "vcmi_sp2mc_dev": (_int, [_vp, _i64, _int, _i64, _int, C.c_double, _vp, _i64, _vp]),
+    "vcmi_mc2sp": (_int, [_dp, _int, _i64, C.c_double, _int, _dp]),
+    "vcmi_mc2sp_dev": (_int, [_vp, _i64, _int, _i64, C.c_double, _int, _vp, _i64, _vp]),
+    "vcmi_mc2b": (_int, [_dp, _int, _i64, C.c_double, _dp]),
+    "vcmi_mc2b_dev": (_int, [_vp, _i64, _int, _i64, C.c_double, _vp, _i64, _vp]),
     "vcmi_align_mcep": (_int, [_dp, _i64, _dp, _i64, _int, C.c_double, _int, C.c_double, _int, _dp, _dp, _ip]),
     "vcmi_parallel_dataset_dev": (_int, [_i64, _dpp, _ip, _dpp, _ip, _int, _int, C.c_double, _int, C.c_double, _int, _int, _int,
                                          _int, _vp, _i64, _ip, _ip]),

@@ -21,7 +21,7 @@ import LinearAlgebra
 export DeviceMatrix, FrameByFrameConverter, TrajectoryConverter, GMMMapParam, GMMMap, TrajectoryGMMMap, TrajectoryGVGMMMap,
        fvconvert, vc, ncomponents, dim,
        VarianceScaling, fvpostf!, fvpostf,
-       align, align_mcep, push_delta, GVDataset,
+       align, align_mcep, push_delta, GVDataset, sp2mc, mc2sp, mc2b,
        DTW, fit!, update!, set_template!, backward,
        predict_proba, predict_proba!, predict, predict!, diffgmm,
        estep_diag, estep_full, estep_set_path, estep_get_path, ESTEP_AUTO, ESTEP_HARD, ESTEP_SOFT, GMMEM, estep!, mstep!, params, KMeansState, kmeans_stats_len, kmeans_assign!, kmeans_update!, kmeans_far!,
@@ -582,6 +582,38 @@ function align_mcep(src::Matrix{Float64}, tgt::Matrix{Float64}, α::AbstractFloa
                 src, S, tgt, size(tgt, 2), D, α, fftlen, threshold, remove_silence ? 1 : 0, so, to, k))
     so[:, 1:k[]], to[:, 1:k[]]
 end
+
+# ---- spectral envelopes into and out of vc: MelGeneralizedCepstrums' sp2mc, mc2sp, mc2b (same argument order) --------
+# sp2mc(sp, order, α) -- test/vc.jl:16, bin/vc.jl:71, bin/mcep.jl:50: sp (K,T) power spectra, K = fftlen÷2+1 -> (order+1,T);
+# a non-positive or non-finite power throws, as Julia's log does
+function sp2mc(sp::Matrix{Float64}, order::Integer, α::AbstractFloat)
+    K, T = size(sp)
+    mc = Matrix{Float64}(undef, order + 1, T)
+    check(ccall((:vcmi_sp2mc, libvcmi), Cint, (Ptr{Float64}, Cint, Int64, Cint, Cdouble, Ptr{Float64}),
+                sp, K, T, order, α, mc))
+    mc
+end
+sp2mc(sp::Vector{Float64}, order::Integer, α::AbstractFloat) = vec(sp2mc(reshape(sp, length(sp), 1), order, α))
+
+# mc2sp(mc, α, fftlen) -- test/vc.jl:28, bin/vc.jl:87: mc (D,T) -> (fftlen÷2+1,T); fftlen may be odd (2 size(sp,1) - 1)
+function mc2sp(mc::Matrix{Float64}, α::AbstractFloat, fftlen::Integer)
+    D, T = size(mc)
+    sp = Matrix{Float64}(undef, fftlen ÷ 2 + 1, T)
+    check(ccall((:vcmi_mc2sp, libvcmi), Cint, (Ptr{Float64}, Cint, Int64, Cdouble, Cint, Ptr{Float64}),
+                mc, D, T, α, fftlen, sp))
+    sp
+end
+mc2sp(mc::Vector{Float64}, α::AbstractFloat, fftlen::Integer) = vec(mc2sp(reshape(mc, length(mc), 1), α, fftlen))
+
+# mc2b(mc, α) -- test/diffvc.jl:33, bin/diffvc.jl:83: MLSA filter coefficients, (D,T) -> (D,T)
+function mc2b(mc::Matrix{Float64}, α::AbstractFloat)
+    D, T = size(mc)
+    b = similar(mc)
+    check(ccall((:vcmi_mc2b, libvcmi), Cint, (Ptr{Float64}, Cint, Int64, Cdouble, Ptr{Float64}),
+                mc, D, T, α, b))
+    b
+end
+mc2b(mc::Vector{Float64}, α::AbstractFloat) = vec(mc2b(reshape(mc, length(mc), 1), α))
 
 # GVDataset(path; ignore0th, add_delta, nmax) -- src/datasets.jl:134-183, from in-memory feature matrices (loading the
 # `.jld` files stays with the caller): X = the (Dout, n) matrix of per-utterance variances var(tgt, 2)
