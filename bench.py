@@ -1,11 +1,19 @@
 #!/usr/bin/env python3
 """bench.py -- headline benchmark of the hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload all|convert|estep|estep_full|em_full|dtw|traj|trajgv]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--workload all|convert|estep|estep_full|em_full|dtw|traj|trajgv]
 
-The default (`all`) prints the headline line of configs[1] and, under `"workloads"`, the same measurement (ms_per_step,
-kernel_ms, roofline, parity against the oracle, cpu_baseline) for each of BASELINE configs[1..4]: convert, the diagonal
-E-step (with its all-reduce timed separately), DTW and the trajectory conversion -- K timed steps each.
+A plain run measures the headline and nothing else: set-up, W warm-up steps, K timed steps and the JSON line (`value`,
+`ms_per_step` and the roofline of those K steps).  With --dump-outputs it writes what the last timed step of every
+workload of the run computed: for the default (`all`) the other six workloads below then run as well, each its set-up,
+warm-up and timed steps only, and the line gains their `summary` rows.
+
+--full adds everything else, as one record: with the default (`all`), under `"workloads"`, the same measurement
+(ms_per_step, kernel_ms, roofline, parity against the oracle, cpu_baseline) for each of BASELINE configs[1..4]: convert,
+the diagonal E-step (with its all-reduce timed separately), DTW and the trajectory conversion -- K timed steps each; for
+every workload the steady-clock pass, the parity sample against the C oracle, the CPU baselines, the MFMA-count launch,
+HBM traffic (live PMC passes for the headline, otherwise the committed source-hash-stamped tables), for convert the
+dense pass and the host-pointer calls, and the detail file named in `detail`.
 
 Headline workload = BASELINE.json configs[1]: GMMMap fvconvert, D=40, M=64, T=10^6 synthetic frames per GPU
 (weak scaling: every rank converts its own shard of T frames; frames are independent, so there is no
@@ -14,8 +22,8 @@ HBM before the timed region.  For N>1 the driver launches this file through torc
 per GPU, RCCL); the timed region is bracketed by barrier + synchronize and the max over ranks is reported.
 
 Prints ONE JSON line on rank 0 with `roofline` (dominant kernel vs the FP64 MFMA roof, timed with HIP events
-on the launch stream) and `cpu_baseline` (the single-threaded C oracle -- a port of the reference's per-frame
-loop, src/common.jl:17-19 + src/gmmmap.jl:101-118 -- on a bounded sample of the same frames).
+on the launch stream) and, with --full, `cpu_baseline` (the single-threaded C oracle -- a port of the reference's
+per-frame loop, src/common.jl:17-19 + src/gmmmap.jl:101-118 -- on a bounded sample of the same frames).
 """
 import argparse
 import json
@@ -499,10 +507,10 @@ def bench_convert(args, world, rank, variant="synthetic"):
     # What the matrix pipe was actually given: the kernel counts its own v_mfma_f64_16x16x4 instructions (wave-uniform scalar
     # adds; vcmi_gmmmap_convert_plan) in one extra, untimed launch on the same frames; profiles/r04_clock/ holds the same
     # number from the SQ_INSTS_MFMA counter.
-    # (profiling runs, --cpu-seconds 0, launch nothing but the warm-up and the timed steps: the PMC passes count there)
+    # (plain runs and profiling runs launch nothing but the warm-up and the timed steps: the PMC passes count there)
     _, shape, active_frac, undecided_frac = g.convert_plan()
     issued_mfma, nreg = None, None
-    if not args.profile_run:
+    if args.full and not args.profile_run:
         g.prune_stats(True)
         step()
         torch.cuda.synchronize()
@@ -555,7 +563,7 @@ def bench_convert(args, world, rank, variant="synthetic"):
                                                          "them out without performing them (see `dense` for the FP64 figure)"})
     # HBM traffic of the kernel: PMC passes of this same command, run as child processes before the timed run (LIVE_PMC)
     # or, failing that, the committed passes if they were collected from the same library sources
-    if headline:
+    if headline and args.full:
         attach_traffic(out, "convert_traffic.json", kname, standard=(T == 1_000_000), live=LIVE_PMC.get("convert"),
                        algorithmic_bytes=2.0 * D * 8 * T)
         if out["roofline"].get("traffic") is not None:
@@ -569,7 +577,7 @@ def bench_convert(args, world, rank, variant="synthetic"):
                 out["roofline"]["SQ_INSTS_MFMA_per_launch"] = v["SQ_INSTS_MFMA_per_launch"]
     # The same K steps with nothing skipped (vcmi_gmmmap_set_prune(inf): every mixture's whitening and regression for every
     # frame, the dense loop the flop count of SURVEY 8(d) assumes), and the pruned output against it.
-    if (args.prune is None or args.prune < 1e300) and args.cpu_seconds > 0 and not args.profile_run:
+    if args.full and (args.prune is None or args.prune < 1e300) and args.cpu_seconds > 0 and not args.profile_run:
         g.set_prune(float("inf"))
         wall_d, kernel_ms_d = timed_steps(step, args.steps, args.warmup, world)
         ach_d = flops / (kernel_ms_d * 1e-3) / 1e12
@@ -587,7 +595,7 @@ def bench_convert(args, world, rank, variant="synthetic"):
             out["roofline"]["max_rel_diff_vs_dense_4096_frames"] = float((torch.linalg.norm(a - b, dim=1) / torch.linalg.norm(b, dim=1)).max())
         PER_RANK["wall_s"] = gather_over_ranks(wall, world)
         PER_RANK["kernel_ms"] = gather_over_ranks(kernel_ms, world)
-    if rank == 0:
+    if rank == 0 and args.full:
         from oracle import c_oracle as co
 
         ref = co.GMMMap(w, mu, sig)
@@ -608,7 +616,7 @@ def bench_convert(args, world, rank, variant="synthetic"):
         out["speedup_vs_cpu_baseline"] = frames_per_s / (n / dt)
     # (profiling runs pass --cpu-seconds 0: nothing but the warm-up and the timed launches may reach the kernel trace and
     # the PMC passes, so the host-pointer measurement and the strong CPU baseline below are skipped there)
-    if rank == 0 and args.cpu_seconds > 0 and headline:
+    if rank == 0 and args.full and args.cpu_seconds > 0 and headline:
         # the host-pointer (PCIe-inclusive) rate of the same call, measured -- never the reported `value`
         Xh = np.asfortranarray(X.T)
         vc.fvconvert(g, Xh)                                  # warm the library's staging buffers
@@ -754,7 +762,7 @@ def bench_estep(args, world, rank, variant="synthetic"):
     # earlier calls any more, so the warm-up steps below can no longer hide a path that mis-fires on its first calls)
     # (profiling runs launch nothing but the warm-up and the timed steps: the PMC passes count launches per step)
     cold_first_call_ms = second_call_ms = None
-    if not args.profile_run:
+    if args.full and not args.profile_run:
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         step_kernels()
@@ -777,8 +785,8 @@ def bench_estep(args, world, rank, variant="synthetic"):
     # step B skips k-steps whose responsibilities are all exactly zero, so the algorithmic flop count is not what is issued
     issued_mfma = None
     try:
-        if args.profile_run:
-            raise RuntimeError("profiling run: nothing but the warm-up and the timed steps is launched")
+        if args.profile_run or not args.full:
+            raise RuntimeError("plain or profiling run: nothing but the warm-up and the timed steps is launched")
         import ctypes as C
 
         from voiceconversion_jl_amd import _lib
@@ -845,10 +853,11 @@ def bench_estep(args, world, rank, variant="synthetic"):
     out["config"]["soft_frames_of_last_step"] = soft          # -1: the one-kernel path ran (the sample of the call's frames found few owners)
     out["cold_first_call_ms"] = cold_first_call_ms
     out["second_call_ms"] = second_call_ms
-    attach_traffic(out, "estep_fixture_traffic.json" if variant == "fixture" else "estep_traffic.json", prefixes,
-                   standard=(N == 1_250_000 and Dj == 80 and M == (32 if variant == "fixture" else 128)),
-                   live=LIVE_PMC.get("estep_fixture" if variant == "fixture" else "estep"), algorithmic_bytes=8.0 * Dj * N)
-    if rank == 0 and not args.profile_run:       # (the parity sample launches the kernel once more)
+    if args.full:
+        attach_traffic(out, "estep_fixture_traffic.json" if variant == "fixture" else "estep_traffic.json", prefixes,
+                       standard=(N == 1_250_000 and Dj == 80 and M == (32 if variant == "fixture" else 128)),
+                       live=LIVE_PMC.get("estep_fixture" if variant == "fixture" else "estep"), algorithmic_bytes=8.0 * Dj * N)
+    if rank == 0 and args.full and not args.profile_run:       # (the parity sample launches the kernel once more)
         from oracle import c_oracle as co
 
         n0 = 20000
@@ -936,7 +945,7 @@ def bench_estep_full(args, world, rank, variant="synthetic"):
     clock_warm = dict(CLOCK_WARM)
     flop = 2 * M * Dj * (Dj + 1) + 2 * M * Dj
     alg_tflops = flop * N / (kernel_ms * 1e-3) / 1e12
-    issued = full_estep_issued_mfma(step, N, Dj, M) if not args.profile_run else None
+    issued = full_estep_issued_mfma(step, N, Dj, M) if args.full and not args.profile_run else None
     iss_tflops = issued * MFMA_FLOP / (kernel_ms * 1e-3) / 1e12 if issued else None
     achieved = min(alg_tflops, iss_tflops) if iss_tflops else alg_tflops
     out = {"metric": "full-covariance GMM E-step frames/sec (Dj=%d, M=%d)" % (Dj, M), "value": world * N * args.steps / wall,
@@ -955,9 +964,10 @@ def bench_estep_full(args, world, rank, variant="synthetic"):
                         "issued_mfma_frac": (iss_tflops / FP64_PEAK_TFLOPS) if iss_tflops else None, "mfma_issued_per_step": issued,
                         "traffic": None,
                         "flop_per_frame": flop, "kernel_ms": kernel_ms}}
-    attach_traffic(out, "estep_full_fixture_traffic.json" if variant == "fixture" else "estep_full_traffic.json",
-                   ("gmmmap_mfma_kernel", "estep_full_stats_kernel", "estep_full_softmax_kernel"), standard=(N == 500_000 and Dj == 80))
-    if rank == 0 and not args.profile_run:       # (the parity sample launches the kernel once more)
+    if args.full:
+        attach_traffic(out, "estep_full_fixture_traffic.json" if variant == "fixture" else "estep_full_traffic.json",
+                       ("gmmmap_mfma_kernel", "estep_full_stats_kernel", "estep_full_softmax_kernel"), standard=(N == 500_000 and Dj == 80))
+    if rank == 0 and args.full and not args.profile_run:       # (the parity sample launches the kernel once more)
         from oracle import c_oracle as co
 
         n = 40000 if Dj <= 80 else 10000
@@ -999,7 +1009,7 @@ def bench_em_full(args, world, rank):
     clock_warm = dict(CLOCK_WARM)
     flop = 2 * M * Dj * (Dj + 1) + 2 * M * Dj
     alg_tflops = flop * N / (kernel_ms * 1e-3) / 1e12
-    issued = full_estep_issued_mfma(lambda: em.estep(Xd.t(), out=stats), N, Dj, M) if not args.profile_run else None
+    issued = full_estep_issued_mfma(lambda: em.estep(Xd.t(), out=stats), N, Dj, M) if args.full and not args.profile_run else None
     iss_tflops = issued * MFMA_FLOP / (kernel_ms * 1e-3) / 1e12 if issued else None
     achieved = min(alg_tflops, iss_tflops) if iss_tflops else alg_tflops
     out = {"metric": "full-covariance GMM EM iteration frames/sec (Dj=%d, M=64)" % Dj, "value": world * N * args.steps / wall,
@@ -1016,9 +1026,10 @@ def bench_em_full(args, world, rank):
                         "traffic": None,
                         "flop_per_frame": flop, "kernel_ms": kernel_ms},
            "loglik_monotone": bool(all(b >= a - 1e-6 * abs(a) for a, b in zip(hist, hist[1:])))}
-    attach_traffic(out, "em_full_traffic.json", ("gmmmap_mfma_kernel", "estep_full_stats_kernel", "estep_full_softmax_kernel"),
-                   standard=(N == 500_000 and Dj == 80))
-    if rank == 0 and args.cpu_seconds > 0:
+    if args.full:
+        attach_traffic(out, "em_full_traffic.json", ("gmmmap_mfma_kernel", "estep_full_stats_kernel", "estep_full_softmax_kernel"),
+                       standard=(N == 500_000 and Dj == 80))
+    if rank == 0 and args.full and args.cpu_seconds > 0:
         from oracle import c_oracle as co
 
         n = 40000 if Dj <= 80 else 10000          # the E-step is the iteration (the M-step is O(M Dj^2))
@@ -1095,10 +1106,11 @@ def bench_dtw(args, world, rank):
                                 "GEMM form, so the roof is one flop per lane-instruction = half the FMA/MFMA figure; "
                                 "`achieved` prices the whole step (forward + backward kernels) at 3*D+10 flop per cell",
                         "cells_per_s": cells / (kernel_ms * 1e-3), "kernel_ms": kernel_ms}}
-    attach_traffic(out, f"dtw{'' if D == 40 else '_d%d' % D}_traffic.json", "dtw_fused",
-                   fetch_factor={"dtw_fused_persistent_kernel": DTW_FUSED_FETCH_FACTOR, "dtw_fused_kernel": DTW_FUSED_FETCH_FACTOR, "": VECTOR_FETCH_FACTOR},
-                   standard=(n == 1000), live=LIVE_PMC.get("dtw"), algorithmic_bytes=float(np.sum((S + T) * D * 8 + T * 8)))
-    if rank == 0:
+    if args.full:
+        attach_traffic(out, f"dtw{'' if D == 40 else '_d%d' % D}_traffic.json", "dtw_fused",
+                       fetch_factor={"dtw_fused_persistent_kernel": DTW_FUSED_FETCH_FACTOR, "dtw_fused_kernel": DTW_FUSED_FETCH_FACTOR, "": VECTOR_FETCH_FACTOR},
+                       standard=(n == 1000), live=LIVE_PMC.get("dtw"), algorithmic_bytes=float(np.sum((S + T) * D * 8 + T * 8)))
+    if rank == 0 and args.full:
         from oracle import c_oracle as co
 
         t0 = time.perf_counter()
@@ -1196,11 +1208,12 @@ def bench_traj(args, world, rank, gv=False):
                         "note": "whole pipeline (4 kernels); the banded solve is a sequential block recurrence along each "
                                 "(sub-)sequence (latency-bound, see DESIGN 3.4: factorisation, then the back substitution as its "
                                 "own kernel); chunked conversion has the same number of block steps per CU, in shorter chains"}}
-    attach_traffic(out, ("trajgv" if gv else "traj") + "_traffic.json",
-                   ("gmmmap_mfma_kernel", "posterior_finish_kernel", "traj_g_mfma_kernel", "traj_solve_blk_kernel", "traj_backsub_blk_kernel",
-                    "traj_gv_kernel", "traj_gv2_kernel"), standard=(n == 256 and L <= 0), live=LIVE_PMC.get("trajgv" if gv else "traj"),
-                   algorithmic_bytes=8.0 * n * T * 3 * D)
-    if rank == 0:
+    if args.full:
+        attach_traffic(out, ("trajgv" if gv else "traj") + "_traffic.json",
+                       ("gmmmap_mfma_kernel", "posterior_finish_kernel", "traj_g_mfma_kernel", "traj_solve_blk_kernel", "traj_backsub_blk_kernel",
+                        "traj_gv_kernel", "traj_gv2_kernel"), standard=(n == 256 and L <= 0), live=LIVE_PMC.get("trajgv" if gv else "traj"),
+                       algorithmic_bytes=8.0 * n * T * 3 * D)
+    if rank == 0 and args.full:
         from oracle import c_oracle as co
 
         ref = co.TrajectoryGMMMap(co.GMMMap(w, mu, sig))
@@ -1451,16 +1464,22 @@ def main():
     ap.add_argument("--workload", default="all",
                     choices=["all", "convert", "convert_fixture", "convert_joint", "convert_broad", "estep", "estep_fixture", "estep_full", "estep_full_fixture", "em_full", "dtw", "traj", "trajgv",
                              "selftest"],
-                    help="all (default): the headline line of configs[1] plus a `workloads` table over configs[1..4]")
+                    help="all (default): the headline line of configs[1] (with --full or --dump-outputs, plus a `workloads` table over "
+                         "configs[1..4])")
     ap.add_argument("--dim", type=int, default=40, help="dtw: feature dimension (40 = BASELINE; 41 = order-40 mel-cepstra with c0)")
+    ap.add_argument("--full", action="store_true",
+                    help="measure and check everything besides the headline: the other workloads of `all` (run by a plain run only "
+                         "for --dump-outputs), the steady-clock pass, "
+                         "parity against the C oracle, CPU baselines, MFMA counts, HBM traffic, convert's dense pass and host-pointer "
+                         "calls, the N=1 cache an N>1 line quotes, and the detail file; a plain run does none of it")
     ap.add_argument("--pmc", default="auto", choices=["auto", "off"],
-                    help="auto: at N=1 measure the headline kernel's HBM traffic in this run (two rocprofv3 --pmc child passes, "
+                    help="with --full -- auto: at N=1 measure the headline kernel's HBM traffic in this run (two rocprofv3 --pmc child passes, "
                          "before this process touches the GPU); off: only the committed, source-hash-stamped passes")
     ap.add_argument("--prune", type=float, default=None,
                     help="convert: posterior pruning threshold in nats of the timed kernel (default: the library's own default, 46 = "
                          "regressions of mixtures with posterior < 1e-20 on a whole 16-frame tile are skipped; inf = every mixture "
                          "for every frame; the `dense` object of the line reports that loop as well)")
-    ap.add_argument("--cpu-seconds-sub", type=float, default=5.0, help="CPU budget of each non-headline workload's cpu_baseline")
+    ap.add_argument("--cpu-seconds-sub", type=float, default=5.0, help="with --full: CPU budget of each non-headline workload's cpu_baseline")
     ap.add_argument("--frames", type=int, default=1_000_000, help="frames per GPU (BASELINE: 10^6)")
     ap.add_argument("--pairs", type=int, default=1000, help="DTW pairs per GPU")
     ap.add_argument("--utts", type=int, default=256, help="trajectory utterances per GPU")
@@ -1468,18 +1487,18 @@ def main():
                     "(bin/vc.jl:18 default --T=100); 0 = whole 2000-frame utterances (BASELINE configs[4])")
     ap.add_argument("--mixtures", type=int, default=128, help="estep: number of mixtures (128 = BASELINE configs[2])")
     ap.add_argument("--dj", type=int, default=80, help="estep: joint feature dimension (80 = BASELINE; 32, 48, 64 and 160 also run the MFMA kernel; others the generic kernels)")
-    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="CPU time budget of the cpu_baseline sample")
+    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="with --full: CPU time budget of the cpu_baseline sample")
     ap.add_argument("--debug-force", type=int, default=0, help="A/B experiments: bit mask for the library's vcmi_debug_force test hook "
                     "(csrc/vcmi_common.hpp kDbg*: alternative launch strategies); the line is then marked `debug_force`")
     ap.add_argument("--clock-warm-ms", type=float, default=100.0,
-                    help="ms of untimed steps of the same workload enqueued ahead of the W warmup steps so that the timed steps run "
-                         "at the steady shader clock (see timed_steps); 0 = only the W warmup steps")
+                    help="with --full: ms of untimed steps of the same workload run after the protocol pass, ahead of the same K steps "
+                         "timed once more at the steady shader clock (see timed_steps); 0 = no steady-clock pass")
     ap.add_argument("--profile-run", action="store_true",
                     help="for the rocprofv3 passes (tools/pmc_traffic.py, tools/clock_pmc.py, tools/round_profiles.sh): launch NOTHING but "
-                         "the W warm-up and the K timed steps (and the steady-clock pass unless --clock-warm-ms 0) -- no MFMA-count launch, "
+                         "the W warm-up and the K timed steps (and, with --full, the steady-clock pass unless --clock-warm-ms 0) -- no MFMA-count launch, "
                          "no dense pass, no parity sample on the device, no host-pointer calls, no CPU baseline; implies --cpu-seconds 0 --pmc off")
     ap.add_argument("--verify-allreduce", action="store_true",
-                    help="estep: rank 0 recomputes the statistics of every rank's frames in one process and compares")
+                    help="estep, with --full: rank 0 recomputes the statistics of every rank's frames in one process and compares")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the run, write what each workload's last timed step computed on rank 0 as DIR/<workload>_<output>.npy "
                          "(float64; at most %d rows of a larger output, a fixed seeded sample; em_full is not dumped: its model "
@@ -1487,7 +1506,7 @@ def main():
     args = ap.parse_args()
     DUMP["on"] = args.dump_outputs is not None
     global CLOCK_WARM_MS
-    CLOCK_WARM_MS = max(args.clock_warm_ms, 0.0)
+    CLOCK_WARM_MS = max(args.clock_warm_ms, 0.0) if args.full else 0.0
     if args.profile_run:
         args.cpu_seconds, args.cpu_seconds_sub, args.pmc = 0.0, 0.0, "off"
 
@@ -1497,7 +1516,7 @@ def main():
         # no torchrun environment: start the ranks ourselves (child process), before any torch.cuda / HIP call
         sys.exit(self_launch(sys.argv[1:], args.gpus))
 
-    if args.gpus == 1 and args.pmc == "auto" and args.workload in ("all", "convert") and args.cpu_seconds > 0 \
+    if args.full and args.gpus == 1 and args.pmc == "auto" and args.workload in ("all", "convert") and args.cpu_seconds > 0 \
             and "WORLD_SIZE" not in os.environ:
         # before anything in this process has touched torch.cuda / HIP: the PMC passes are child processes
         t = measure_traffic_live("convert", ["--frames", str(args.frames)])
@@ -1521,7 +1540,9 @@ def main():
            "estep_fixture": lambda a, w, r: bench_estep(a, w, r, variant="fixture"),
            "estep_full_fixture": lambda a, w, r: bench_estep_full(a, w, r, variant="fixture"),
            "selftest": bench_selftest}
-    if args.workload == "all":
+    if args.workload == "all" and (args.full or DUMP["on"]):
+        # the other workloads of the default run: measured under --full; in a plain run only when --dump-outputs asks for
+        # what their timed steps computed (each then runs its warm-up and timed steps and nothing else)
         import copy
         import gc
 
@@ -1544,10 +1565,11 @@ def main():
         PER_RANK.update(table["convert"]["per_rank"])
         out["workloads"] = table
     else:
-        DUMP["prefix"] = args.workload + "_"
-        out = fns[args.workload](args, world, rank)
-        table = {args.workload: out}
-    if world > 1:
+        name = "convert" if args.workload == "all" else args.workload
+        DUMP["prefix"] = name + "_"
+        out = fns[name](args, world, rank)
+        table = {name: out}
+    if world > 1 and args.full:
         for k in ("cpu_baseline_strong", "speedup_vs_cpu_baseline", "host_inclusive"):
             out.pop(k, None)
         for name, d in table.items():            # an N > 1 line keeps the N = 1 CPU baseline, labelled as cached
@@ -1561,7 +1583,7 @@ def main():
             out["cpu_baseline"] = table["convert"]["cpu_baseline"]
         if rank == 0:
             out["n1_consistency"] = n1_consistency(table, world)
-    elif rank == 0 and args.workload != "selftest" and args.cpu_seconds > 0:
+    elif rank == 0 and args.full and args.workload != "selftest" and args.cpu_seconds > 0:
         have = {name: d["cpu_baseline"] for name, d in table.items() if isinstance(d.get("cpu_baseline"), dict) and "value" in d["cpu_baseline"]}
         if have:
             try:
@@ -1584,7 +1606,8 @@ def main():
     if os.environ.get("LIBVCMI_PROBE"):
         out["probe_library"] = os.environ["LIBVCMI_PROBE"]      # an A/B or probe build, not the in-tree library
     if rank == 0:
-        out["detail"] = write_detail(out, "bench_detail_%s_n%d.json" % (args.workload, world))
+        if args.full:
+            out["detail"] = write_detail(out, "bench_detail_%s_n%d.json" % (args.workload, world))
         if DUMP["on"]:
             write_dump(args.dump_outputs)
         print(compact_line(out, table), flush=True)

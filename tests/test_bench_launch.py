@@ -142,12 +142,22 @@ def test_the_one_stdout_line_stays_under_the_cap():
 
 
 def test_selftest_line_is_short_and_names_its_detail_file():
-    p = _run(["--gpus", "2", "--workload", "selftest", "--steps", "2"], {"VCMI_BENCH_BACKEND": "gloo"})
+    p = _run(["--gpus", "2", "--workload", "selftest", "--steps", "2", "--full"], {"VCMI_BENCH_BACKEND": "gloo"})
     assert p.returncode == 0, p.stderr[-2000:]
     line = [l for l in p.stdout.splitlines() if l.startswith("{")][0]
     assert len(line) < 2000
     out = json.loads(line)
     assert out["detail"] and os.path.exists(os.path.join(ROOT, out["detail"]) if not os.path.isabs(out["detail"]) else out["detail"])
+
+
+def test_plain_run_writes_no_detail_file():
+    """A plain run prints its line and nothing else; the detail file is one of the things --full adds."""
+    plain = _run(["--gpus", "1", "--workload", "selftest", "--steps", "2"], {})
+    full = _run(["--gpus", "1", "--workload", "selftest", "--steps", "2", "--full"], {})
+    assert plain.returncode == 0 and full.returncode == 0, (plain.stderr + full.stderr)[-2000:]
+    lines = [json.loads(l) for l in plain.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1 and "detail" not in lines[0] and lines[0]["allreduce_exact"] is True
+    assert json.loads([l for l in full.stdout.splitlines() if l.startswith("{")][0])["detail"]
 
 
 def test_traffic_tables_with_wrong_step_accounting_are_refused(tmp_path, monkeypatch):

@@ -29,7 +29,7 @@ def _bench(args, env_extra, timeout=600):
     return json.loads(lines[0])
 
 
-ESTEP = ["--workload", "estep", "--frames", "60000", "--steps", "2", "--warmup", "1", "--cpu-seconds", "0", "--verify-allreduce"]
+ESTEP = ["--workload", "estep", "--frames", "60000", "--steps", "2", "--warmup", "1", "--cpu-seconds", "0", "--verify-allreduce", "--full"]
 
 
 def test_one_rank_rccl_allreduce():
@@ -54,5 +54,5 @@ def test_two_ranks_rccl_one_per_gpu():
     out = _bench(["--gpus", "2"] + ESTEP, {})
     assert out["n_gpus"] == 2 and out["collective_backend"] == "nccl"
     assert out["allreduce_check"]["max_rel_err_vs_single_process"] <= 1e-12
-    conv = _bench(["--gpus", "2", "--frames", "200000", "--steps", "3", "--warmup", "1", "--cpu-seconds", "1"], {})
+    conv = _bench(["--gpus", "2", "--frames", "200000", "--steps", "3", "--warmup", "1", "--cpu-seconds", "1", "--full"], {})
     assert conv["n_gpus"] == 2 and conv["parity_max_rel_err_vs_oracle"] < 1e-9
