@@ -1,6 +1,7 @@
 """CPU: sanitizer builds.  GPU AddressSanitizer is not available on this pool, so the host side is
 checked here: the C oracle under ASan + UBSan against a golden case, and the host-only translation units of libvcmi
-(error plumbing, worker-thread copies, device groups) under ASan + UBSan and under ThreadSanitizer with a stress driver."""
+(error plumbing, worker-thread copies, device groups) under ASan + UBSan and under ThreadSanitizer with a stress driver,
+and the host-side model preparation of GMMMap (factor, profile, choose, every packer) under ASan + UBSan."""
 import os
 import subprocess
 
@@ -23,6 +24,11 @@ GROUP_CMD = ["g++", "-std=c++17", "-O1", "-g", "-fno-omit-frame-pointer", "-D__H
              "-I/opt/rocm/include", os.path.join(ROOT, "tests", "c", "devgroup_stress.cpp"),
              os.path.join(CSRC, "core.cpp"), os.path.join(CSRC, "devgroup.cpp")]
 
+# the host-side preparation of a GMMMap converter (csrc/gmmmap_prepare.cpp: pure host functions) over the shapes at which its
+# packers take another path; the driver checks every image's length against csrc/gmmmap_layout.hpp
+PREPARE_CMD = [os.path.join(ROOT, "tests", "c", "prepare_check.cpp") if a.endswith("host_stress.cpp") else a for a in COMMON] + [
+    os.path.join(CSRC, "gmmmap_prepare.cpp")]
+
 
 def _build_and_run(name, flags, env_extra, cmd=COMMON, ok="host_stress: ok"):
     os.makedirs(OUT, exist_ok=True)
@@ -41,6 +47,11 @@ def test_host_code_under_asan_ubsan():
 
 def test_host_code_under_tsan():
     _build_and_run("host_stress_tsan", ["-fsanitize=thread"], {"TSAN_OPTIONS": "halt_on_error=0 report_signal_unsafe=0"})
+
+
+def test_model_preparation_under_asan_ubsan():
+    _build_and_run("prepare_check_asan", ["-fsanitize=address,undefined"], {"ASAN_OPTIONS": "detect_leaks=0", "UBSAN_OPTIONS": "print_stacktrace=1"},
+                   cmd=PREPARE_CMD, ok="prepare_check: ok")
 
 
 def test_device_group_four_members_under_asan_ubsan():

@@ -33,8 +33,10 @@ __device__ __forceinline__ void split_bf16_pair(double a, double b, unsigned &hi
 #endif
 }
 #endif
+#if defined(__clang__)      // the matrix instructions' vector types (the CPU sanitizer build of the host files needs split_bf16 alone)
 typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
 typedef float f32x4_t __attribute__((ext_vector_type(4)));
 typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
+#endif
 
 }  // namespace vcmi

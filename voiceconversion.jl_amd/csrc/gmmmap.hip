@@ -1,5 +1,7 @@
-// gmmmap.hip -- GMM joint-density mapping on MI355X (gfx950): model preparation, the batched
-// fvconvert kernels (FP64 MFMA tile kernel + generic FP64 VALU kernel), posterior and argmax.
+// gmmmap.hip -- GMM joint-density mapping on MI355X (gfx950): the batched fvconvert kernels (FP64 MFMA tile kernel +
+// generic FP64 VALU kernel), posterior and argmax, their dispatch, the on-device p(x) preparation and the C entry points.
+// The host-side model preparation (factorisation, profile, the packers of every device image) is gmmmap_prepare.cpp;
+// what its packers and these kernels must agree on (row tiling, issue order, stage layouts) is gmmmap_layout.hpp.
 //
 // Replaces, for whole (D,T) matrices at once:
 //   GMMMap ctor / GMMMapParam / split_joint_gmm          reference src/gmmmap.jl:23-90
@@ -8,7 +10,7 @@
 //   predict_proba / predict                              reference src/gmm.jl:24-58
 //   vc(c::FrameByFrameConverter, fm)                     reference src/common.jl:7-26
 //
-// Math.  Per mixture m, prepared once on the host:
+// Math.  Per mixture m, prepared once on the host (gmmmap_prepare.cpp):
 //   A_m = Syx_m inv(Sxx_m)              b_m  = muy_m - A_m mux_m
 //   L_m L_m' = Hermitian(Sxx_m)         U_m  = inv(L_m)   (lower triangular)     cz_m = U_m mux_m
 //   lc_m = log w_m - (D log 2pi + 2 sum_i log L_m[i,i]) / 2
@@ -21,7 +23,6 @@
 // in HBM in issue order, 64 lanes x 8 B per step, so the global->LDS stage is a straight copy and every
 // ds_read_b64 is conflict-free.
 #include "vcmi_common.hpp"
-#include "host_linalg.hpp"
 #include "gmmmap_handle.hpp"
 #include "devgroup.hpp"
 #include "hostpipe.hpp"
@@ -35,73 +36,8 @@
 #include <atomic>
 #include <cmath>
 #include <cstdlib>
-#include <limits>
 
 namespace vcmi {
-
-// ------------------------------------------------------------------------------------------------
-// compile-time description of the row tiling for a padded dimension DP (multiple of 4)
-// ------------------------------------------------------------------------------------------------
-// UONLY: only the whitening rows U_m (log-density / posterior / argmax path: the regression rows are not staged)
-template <int DP, bool UONLY = false>
-struct Tiling {
-  static constexpr int KS = DP / 4;                       // k-steps covering all of x
-  static constexpr int NT = UONLY ? (DP + 15) / 16 : (2 * DP + 15) / 16;   // 16-row tiles over [U rows ; A rows]
-  static constexpr int NU = (DP + 15) / 16;               // tiles that contain at least one U row
-  __host__ __device__ static constexpr int steps(int t) {  // k-steps tile t needs
-    return (16 * t + 15 < DP) ? ((4 * (t + 1) < KS) ? 4 * (t + 1) : KS) : KS;
-  }
-  // MODE 3 (predict with early exit) stores the whitening tiles one after the other in REVERSE order (tile NU-1 first):
-  // rtile_off(i) = first fragment of the i-th tile in that order
-  __host__ __device__ static constexpr int tile_off(int t) {      // fragments before tile t in the k-step-major order of the U tiles
-    int n = 0;
-    for (int ks = 0; ks < KS; ++ks)
-      for (int u = 0; u < NU && u < NT; ++u)
-        if (ks < steps(u)) ++n;
-    return t >= NU ? n : 0;
-  }
-  // position of fragment (k-step ks, U tile t) in the k-step-major order of the U tiles (the order the packer writes them in)
-  __host__ __device__ static constexpr int ufrag_pos(int ks, int t) {
-    int n = 0;
-    for (int k = 0; k < ks; ++k)
-      for (int u = 0; u < NU && u < NT; ++u)
-        if (k < steps(u)) ++n;
-    for (int u = 0; u < t; ++u)
-      if (ks < steps(u)) ++n;
-    return n;
-  }
-  __host__ __device__ static constexpr int rtile_off(int i) {
-    int n = 0;
-    for (int u = 0; u < i; ++u) n += steps(NU - 1 - u);
-    return n;
-  }
-  __host__ __device__ static constexpr int nsteps() {
-    int n = 0;
-    for (int t = 0; t < NT; ++t) n += steps(t);
-    return n;
-  }
-  static constexpr int NSTEPS = nsteps();
-  // per-mixture block in doubles: [fragments NSTEPS*64 | cinit NT*16 | lc | pad], multiple of 32 doubles
-  static constexpr int CINIT_OFF = NSTEPS * 64;
-  static constexpr int LC_OFF = CINIT_OFF + NT * 16;
-  static constexpr int BLK = ((LC_OFF + 1 + 1023) / 1024) * 1024;   // whole double2 per thread for 256- and 512-thread groups
-};
-
-// runtime mirror used by the host-side packer (same formulas, any DP)
-struct TilingRT {
-  int DP, KS, NT, NU, NSTEPS, CINIT_OFF, LC_OFF, BLK;
-  explicit TilingRT(int dp, bool uonly = false) : DP(dp) {
-    KS = DP / 4;
-    NT = uonly ? (DP + 15) / 16 : (2 * DP + 15) / 16;
-    NU = (DP + 15) / 16;
-    NSTEPS = 0;
-    for (int t = 0; t < NT; ++t) NSTEPS += steps(t);
-    CINIT_OFF = NSTEPS * 64;
-    LC_OFF = CINIT_OFF + NT * 16;
-    BLK = ((LC_OFF + 1 + 1023) / 1024) * 1024;
-  }
-  int steps(int t) const { return (16 * t + 15 < DP) ? std::min(4 * (t + 1), KS) : KS; }
-};
 
 typedef double d4 __attribute__((ext_vector_type(4)));
 
@@ -1293,8 +1229,6 @@ convert_from_logdens_kernel(const double *__restrict__ LP, int M, int D, int DP,
 // gfrag[mt][ks][lane]: A-operand fragments, rows = mixtures 16 mt + (lane & 15), k = 4 ks + (lane >> 4); the last k-step
 // carries |mu|^2 (rows >= M: 1e300, never the minimum).
 // ------------------------------------------------------------------------------------------------
-constexpr int kGroupKeyDims = 24;     // dimensions the nearest-mean key is taken over (a multiple of 4)
-
 // keys + one histogram per CHUNK of 1024 consecutive frames (chunkhist[c][m]); a workgroup walks chunks blockIdx.x,
 // blockIdx.x + gridDim.x, ... with the operand fragments staged once.  The counts are integers: whatever order the LDS
 // atomics arrive in, the histogram is the same.
@@ -1369,7 +1303,6 @@ gmmmap_group_key_kernel(const double *__restrict__ gfrag, int M, int D, const do
 // in the accumulator's initial value.  gfrag16[mt]: 64 x 16 bytes of hi, 64 x 16 bytes of lo, 4 x 4 floats of |mu|^2 (lane
 // group g of the result holds rows 4 g .. 4 g + 3; rows >= M: 1e30).  Deterministic like the FP64 kernel; a frame between
 // two means may get the other key, which costs a regression, never a result.
-constexpr int kKey16TileBytes = 2 * 1024 + 64;
 template <int DP>
 __global__ void __launch_bounds__(256)
 gmmmap_group_key16_kernel(const double *__restrict__ gfrag16, int M, int D, const double *__restrict__ X, int64_t ldx, int64_t T,
@@ -1638,14 +1571,6 @@ static int dispatch_mfma(const vcmi_gmmmap *g, const double *dX, int64_t ldx, in
   }
 }
 
-bool gmmmap_has_mfma(int DP) {
-  switch (DP) {
-    case 16: case 20: case 24: case 28: case 32: case 36: case 40: case 44: case 48: case 52: case 56: case 60: case 64:
-    case 68: case 72: case 76: case 80: return true;
-    default: return false;
-  }
-}
-
 template <int MODE>
 static int launch_generic(const vcmi_gmmmap *g, const double *dX, int64_t ldx, int64_t T, double *dY, int64_t ldy,
                           hipStream_t st) {
@@ -1667,8 +1592,6 @@ static bool use_mfma(const vcmi_gmmmap *g) {
   return gmmmap_has_mfma(g->DP);
 }
 
-// shape 3 (gmmmap_screen.hpp): DP = 16..48, any M up to 1024 (the survivors' bitmap)
-static bool screen_has_kernel(int DP) { return DP >= 16 && DP <= 48 && DP % 4 == 0; }
 template <int DP, int FT, bool B16 = false>
 static int launch_screen(const vcmi_gmmmap *g, const double *dX, int64_t ldx, int64_t T, double *dY, int64_t ldy, hipStream_t st,
                          const int *perm, const int *gkey) {
@@ -1754,8 +1677,8 @@ static constexpr double kBroadModelFrac = 0.35;
 // for every wave of its workgroup, a screened mixture 2.5 -- against the 10 of shape 2's last-tile test
 static constexpr double kScreenModelFrac = 0.05;
 // Which loop shape converts with this handle (gmmmap_mfma_kernel's PRUNE): 2 "peaked" when, for the model's own frames, the
-// last whitening tile's share of |z|^2 alone puts most mixtures e^-prune under the best one (model_undecided_frac, estimated
-// once by prepare(): 0.02 on the SURVEY 8d synthetic models) -- the loop that looks at that tile first then skips the other
+// last whitening tile's share of |z|^2 alone puts most mixtures e^-prune under the best one (model.undecided, estimated
+// once by profile_model(), gmmmap_prepare.cpp: 0.02 on the SURVEY 8d synthetic models) -- the loop that looks at that tile first then skips the other
 // whitening tiles; 1 "broad" otherwise (every whitening tile is needed anyway: the straight loop is faster).
 static int convert_shape(const vcmi_gmmmap *g) {
   const bool can_screen = screen_has_kernel(g->DP) && g->M <= 1024 && g->packedQ.p != nullptr;
@@ -1763,15 +1686,13 @@ static int convert_shape(const vcmi_gmmmap *g) {
   if (debug_flag(kDbgConvertShapePeaked)) return 2;
   if (debug_flag(kDbgConvertShapeScreened) && can_screen) return 3;
   if (can_screen && g->model_undecided4_frac <= kScreenModelFrac) return 3;     // (grouped calls only: see gmmmap_convert_device)
-  return g->model_undecided_frac > kBroadModelFrac ? 1 : 2;
+  return g->model.undecided > kBroadModelFrac ? 1 : 2;
 }
 
 // The three grouping kernels (keys + chunk histograms, prefix, stable scatter) on g's scratch: *key = group of every frame,
 // *perm = frames in group order.  The caller brackets its use of them with g->grp_order.enter / leave.
 static size_t group_key_shmem(const vcmi_gmmmap *g, bool fp64) {
-  const int MT = (g->M + 15) / 16;
-  return (fp64 ? (size_t)MT * (std::min(g->DP / 4, kGroupKeyDims / 4) + 1) * 64 * sizeof(double) : (size_t)MT * kKey16TileBytes) +
-         (size_t)g->M * sizeof(int);
+  return (fp64 ? group_key_doubles(g->DP, g->M) : group_key16_doubles(g->M)) * sizeof(double) + (size_t)g->M * sizeof(int);
 }
 static bool group_key_fp64(const vcmi_gmmmap *g) { return debug_flag(kDbgGroupKeyFp64) || !g->gfrag16.p; }
 static bool can_group(const vcmi_gmmmap *g, int64_t T) {
@@ -1885,12 +1806,12 @@ int gmmmap_predict_device(vcmi_gmmmap *g, const double *dX, int64_t ldx, int64_t
   if (T == 0) return VCMI_OK;
   if (use_mfma(g) && !debug_flag(kDbgPredictTwoPass)) {    // argmax inside the MFMA kernel: no (M,T) matrix, one launch
     // long inputs: frames grouped by nearest source mean, then the screened arg-max (exact; gmmmap_screen.hpp)
-    // -- where the model's own frames leave it few survivors (model_argmax_survivors_frac, estimated by prepare(): 3.7 x on the
+    // -- where the model's own frames leave it few survivors (model.argmax_survivors, estimated by profile_model(): 3.7 x on the
     // SURVEY 8d model's frames; on a broad model the bound from four directions never reaches the 40 nats that the full
     // 80-dimensional distance of the best mixture costs, every mixture survives and the early-exit kernel is as fast) and the
     // caller allows it (the trajectory conversion does not: its static + delta vectors are not draws from p(x) -- measured
     // 4.1 against 3.3 ms per 512,000 frames there, tools/predict_screen_ab.py)
-    const bool screen_pays = (g->model_argmax_survivors_frac <= kScreenArgmaxFrac || debug_flag(kDbgPredictScreen)) && allow_screen;
+    const bool screen_pays = (g->model.argmax_survivors <= kScreenArgmaxFrac || debug_flag(kDbgPredictScreen)) && allow_screen;
     if (screen_pays && g->packedQA.p && g->packedU.p && g->M <= 1024 && can_group(g, T) && !debug_flag(kDbgPredictNoScreen) &&
         !debug_flag(kDbgPredictNoEarlyExit)) {
       int *key = nullptr, *perm = nullptr;
@@ -1909,496 +1830,6 @@ int gmmmap_predict_device(vcmi_gmmmap *g, const double *dX, int64_t ldx, int64_t
   hipLaunchKernelGGL(posterior_finish_kernel<1>, dim3(posterior_finish_grid(g->M, T)), dim3(256), 0, st, g->scratch_lp.p,
                      g->M, T, didx);
   VCMI_HIP(hipGetLastError());
-  return VCMI_OK;
-}
-
-// ------------------------------------------------------------------------------------------------
-// model preparation (host) and upload
-// ------------------------------------------------------------------------------------------------
-// How broad is the model?  256 frames are drawn from p(x) itself (stratified over the weights, fixed-seed normal deviates:
-// x = mu_m + L_m z, i.e. U_m (x - mu_m) = z solved by forward substitution) and for each the mixtures within e^-46 of the best
-// one are counted.  Returns the mean fraction of the M mixtures.  A property of the model only; it selects the loop SHAPE of
-// fvconvert (convert_shape), never a result.
-static double model_active_fraction(const std::vector<double> &hU, const std::vector<double> &hcz, const std::vector<double> &hlc,
-                                    const std::vector<double> &hP, const std::vector<double> &hcP,
-                                    const std::vector<double> &hmux, const double *w, int D, int DP, int M,
-                                    double *undecided_frac, double *undecided_rows, double *argmax_survivors) {
-  constexpr int S = 256;
-  const size_t pp = (size_t)DP * DP;
-  std::vector<double> cdf(M);
-  double tot = 0.0;
-  for (int m = 0; m < M; ++m) cdf[m] = (tot += (w[m] > 0.0 ? w[m] : 0.0));
-  if (undecided_frac) *undecided_frac = 0.0;
-  if (undecided_rows) undecided_rows[0] = undecided_rows[1] = undecided_rows[2] = 1.0;   // on the 4 / 2 / 1 strongest screening rows
-  if (!(tot > 0.0) || M < 2) return 0.0;
-  std::vector<int> counts(S, 0), undecided(S, 0), undecided4(3 * S, 0), asurv(S, 0);
-  if (argmax_survivors) *argmax_survivors = 1.0;
-  const int r_last = 16 * ((DP + 15) / 16 - 1);                       // first row of the last whitening tile
-  host_parallel_for(S, 8, [&](int64_t lo, int64_t hi) {
-    std::vector<double> x(D), z(D);
-    for (int s = (int)lo; s < (int)hi; ++s) {
-      const double u = (s + 0.5) / S * tot;
-      int m = 0;
-      while (m + 1 < M && cdf[m] < u) ++m;
-      uint64_t st = 0x9E3779B97F4A7C15ull * (uint64_t)(s + 1);          // splitmix64 stream per frame
-      auto rnd = [&]() {
-        st += 0x9E3779B97F4A7C15ull;
-        uint64_t v = st;
-        v = (v ^ (v >> 30)) * 0xBF58476D1CE4E5B9ull;
-        v = (v ^ (v >> 27)) * 0x94D049BB133111EBull;
-        v ^= v >> 31;
-        return ((double)(v >> 11) + 0.5) * (1.0 / 9007199254740992.0);
-      };
-      for (int d = 0; d < D; d += 2) {                                  // Box-Muller
-        const double r = std::sqrt(-2.0 * std::log(rnd())), a = 6.283185307179586 * rnd();
-        z[d] = r * std::cos(a);
-        if (d + 1 < D) z[d + 1] = r * std::sin(a);
-      }
-      const double *Um = &hU[pp * m];
-      for (int r = 0; r < D; ++r) {                                     // U_m (x - mu_m) = z, U_m lower triangular
-        double acc = z[r];
-        for (int c = 0; c < r; ++c) acc -= Um[(size_t)r * DP + c] * x[c];
-        x[r] = acc / Um[(size_t)r * DP + r];
-      }
-      for (int d = 0; d < D; ++d) x[d] += hmux[(size_t)D * m + d];
-      double best = -INFINITY;
-      std::vector<double> l(M), qlast(M), qlast4(3 * (size_t)M);
-      for (int n = 0; n < M; ++n) {
-        const double *Un = &hU[pp * n];
-        double q = 0.0, ql = 0.0, ql4[3] = {0.0, 0.0, 0.0};
-        for (int r = 0; r < D; ++r) {
-          double zz = -hcz[(size_t)DP * n + r];
-          for (int c = 0; c <= r; ++c) zz += Un[(size_t)r * DP + c] * x[c];
-          q += zz * zz;
-          if (r >= r_last) ql += zz * zz;
-        }
-        if (!hP.empty())
-          for (int i = 0; i < 4; ++i) {                                  // the screen's rows: strongest first
-            double pz = -hcP[(size_t)n * 4 + i];
-            for (int c = 0; c < D; ++c) pz += hP[((size_t)n * 4 + i) * DP + c] * x[c];
-            for (int c = 0; c < 3; ++c)
-              if (i < (4 >> c)) ql4[c] += pz * pz;
-          }
-        l[n] = hlc[n] - 0.5 * q;
-        qlast[n] = ql;
-        for (int c = 0; c < 3; ++c) qlast4[3 * (size_t)n + c] = ql4[c];
-        best = std::max(best, l[n]);
-      }
-      int cnt = 0;
-      for (int n = 0; n < M; ++n) cnt += (l[n] > best - 46.0);
-      counts[s] = cnt;
-      int und = 0;                                                     // ... and on the last 16-row whitening tile's share alone
-      for (int n = 0; n < M; ++n) und += (hlc[n] - 0.5 * qlast[n] > best - 46.0);
-      undecided[s] = und;
-      {                                                                // predict's screen: bound from four rows >= the best log-density
-        int sv = 0;
-        for (int n = 0; n < M; ++n) sv += (hlc[n] - 0.5 * qlast4[3 * (size_t)n] >= best);
-        asurv[s] = sv;
-      }
-      for (int c = 0; c < 3; ++c) {                                    // ... and on the 4 / 2 / 1 strongest screening rows alone (shape 3)
-        int und4 = 0;
-        for (int n = 0; n < M; ++n) und4 += (hlc[n] - 0.5 * qlast4[3 * (size_t)n + c] > best - 46.0);
-        undecided4[3 * s + c] = und4;
-      }
-    }
-  });
-  double sum = 0.0, sumu = 0.0, sumu4[3] = {0.0, 0.0, 0.0};
-  for (int s = 0; s < S; ++s) {
-    sum += counts[s];
-    sumu += undecided[s];
-    for (int c = 0; c < 3; ++c) sumu4[c] += undecided4[3 * s + c];
-  }
-  if (undecided_frac) *undecided_frac = sumu / ((double)S * M);
-  if (undecided_rows)
-    for (int c = 0; c < 3; ++c) undecided_rows[c] = sumu4[c] / ((double)S * M);
-  if (argmax_survivors && !hP.empty()) {
-    double sa = 0.0;
-    for (int s = 0; s < S; ++s) sa += asurv[s];
-    *argmax_survivors = sa / ((double)S * M);
-  }
-  return sum / ((double)S * M);
-}
-
-// px_only: (mu, sigma) describe a plain GMM p(x) of dimension Dj (no target half): only the whitening side is prepared
-// (used by the full-covariance E-step, estep.hip); the regression blocks stay zero and the convert layouts are skipped.
-static int prepare(vcmi_gmmmap *g, const double *w, const double *mu, const double *sigma, int Dj, int M, int swap,
-                   bool px_only = false) {
-  const int D = px_only ? Dj : Dj >> 1;   // src/gmmmap.jl:70
-  const int DP = (D + 3) / 4 * 4;
-  g->D = D;
-  g->M = M;
-  g->DP = DP;
-  const size_t dd = (size_t)D * D, pp = (size_t)DP * DP;
-  const size_t reg = px_only ? 0 : 1;   // the regression side (A, b, Sxy, Syy) does not exist for a p(x)-only handle
-  g->h_A_julia.assign(reg * dd * M, 0.0);
-  g->h_Sxy.assign(reg * dd * M, 0.0);
-  g->h_Syy.assign(reg * dd * M, 0.0);
-  g->h_A.assign(reg * dd * M, 0.0);
-  g->h_mux.assign((size_t)D * M, 0.0);
-  g->h_muy.assign((size_t)D * M, 0.0);
-  std::vector<double> hU(pp * M, 0.0), hA(reg * pp * M, 0.0), hcz((size_t)DP * M, 0.0), hb(reg * DP * M, 0.0), hlc(M);
-  const bool want_screen = !px_only && D >= 4 && gmmmap_has_mfma(DP) && M <= 1024;       // (fvconvert's screen: DP <= 48; predict's: every tile-kernel dimension)
-  std::vector<double> hP(want_screen ? (size_t)M * 4 * DP : 0, 0.0), hcP(want_screen ? (size_t)M * 4 : 0, 0.0);
-  const int xo = (swap && !px_only) ? D : 0, yo = px_only ? 0 : (swap ? 0 : D);   // src/gmmmap.jl:74-78
-  const double LOG2PI = 1.8378770664093454835606594728112;
-  // The mixtures are independent (an inverse, a Cholesky factorisation and a triangular inverse each: 64 x 160^3 flop for
-  // the joint model of delta features): they are shared out over the library's host threads.  The first failing mixture
-  // (lowest index) is reported, as the sequential loop would.
-  std::atomic<int> bad_singular{M}, bad_notpd{M};
-  auto lower_to = [](std::atomic<int> &a, int v) {
-    int cur = a.load();
-    while (v < cur && !a.compare_exchange_weak(cur, v)) {}
-  };
-  host_parallel_for(M, 1, [&](int64_t m_lo, int64_t m_hi) {
-  std::vector<double> Sxx(dd), Syx(dd), inv(dd), L(dd), Ui(dd);
-  for (int m = (int)m_lo; m < (int)m_hi; ++m) {
-    const double *S = sigma + (size_t)Dj * Dj * m;   // column-major (Dj,Dj)
-    double *mux = &g->h_mux[(size_t)D * m], *muy = &g->h_muy[(size_t)D * m];
-    for (int d = 0; d < D; ++d) {
-      mux[d] = mu[xo + d + (size_t)Dj * m];
-      muy[d] = px_only ? 0.0 : mu[yo + d + (size_t)Dj * m];
-    }
-    // row-major copies of the four blocks, src/gmmmap.jl:41-52
-    for (int r = 0; r < D; ++r)
-      for (int c = 0; c < D; ++c) {
-        Sxx[(size_t)r * D + c] = S[(xo + r) + (size_t)Dj * (xo + c)];
-        if (px_only) continue;
-        Syx[(size_t)r * D + c] = S[(yo + r) + (size_t)Dj * (xo + c)];
-        g->h_Sxy[dd * m + (size_t)r * D + c] = S[(xo + r) + (size_t)Dj * (yo + c)];
-        g->h_Syy[dd * m + (size_t)r * D + c] = S[(yo + r) + (size_t)Dj * (yo + c)];
-      }
-    // A_m = Syx inv(Sxx) on the raw block, src/gmmmap.jl:35
-    double *Am = px_only ? nullptr : &g->h_A[dd * m];
-    if (!px_only) {
-      if (!la::inverse(Sxx.data(), D, inv.data())) {
-        lower_to(bad_singular, m);
-        continue;
-      }
-      la::matmul(Syx.data(), inv.data(), D, Am);
-      for (int r = 0; r < D; ++r)
-        for (int c = 0; c < D; ++c) {
-          g->h_A_julia[dd * m + r + (size_t)D * c] = Am[(size_t)r * D + c];
-          hA[pp * m + (size_t)r * DP + c] = Am[(size_t)r * D + c];
-        }
-    }
-    // p(x): Hermitian(Sxx) (upper triangle mirrored, src/gmm.jl:16) -> Cholesky -> U = inv(L)
-    if (!la::cholesky_from_upper(Sxx.data(), D, L.data())) {
-      lower_to(bad_notpd, m);
-      continue;
-    }
-    la::lower_inverse(L.data(), D, Ui.data());
-    double logdiag = 0.0;
-    for (int d = 0; d < D; ++d) logdiag += std::log(L[(size_t)d * D + d]);
-    hlc[m] = (w[m] > 0.0) ? std::log(w[m]) - 0.5 * (D * LOG2PI + 2.0 * logdiag)
-                          : -std::numeric_limits<double>::infinity();   // zero-weight: posterior 0
-    for (int r = 0; r < D; ++r) {
-      double cz = 0.0, ba = 0.0;
-      for (int c = 0; c < D; ++c) {
-        hU[pp * m + (size_t)r * DP + c] = Ui[(size_t)r * D + c];
-        cz += Ui[(size_t)r * D + c] * mux[c];
-        if (!px_only) ba += Am[(size_t)r * D + c] * mux[c];
-      }
-      hcz[(size_t)DP * m + r] = cz;
-      if (!px_only) hb[(size_t)DP * m + r] = muy[r] - ba;
-    }
-    // screening rows of shape 3 (gmmmap_screen.hpp): P_m = diag(sqrt(kappa_i)) v_i' over the FOUR LARGEST eigenpairs of
-    // inv(Sxx_m) = U'U -- the directions of smallest variance.  |P_m (x - mu_m)|^2 is a partial sum of the eigen-expansion of
-    // (x - mu_m)' inv(Sxx_m) (x - mu_m) = |z_m|^2: a lower bound of it, and per row the largest one any direction can give.
-    if (want_screen) {
-      std::vector<double> G(dd), V(dd);
-      for (int r = 0; r < D; ++r)
-        for (int c = 0; c < D; ++c) {
-          double sacc = 0.0;
-          for (int k = std::max(r, c); k < D; ++k) sacc += Ui[(size_t)k * D + r] * Ui[(size_t)k * D + c];
-          G[(size_t)r * D + c] = sacc;
-        }
-      la::sym_eigen_jacobi(G.data(), D, V.data());
-      int top[4] = {-1, -1, -1, -1};
-      for (int i = 0; i < 4; ++i) {
-        double bestv = -1.0;
-        for (int j = 0; j < D; ++j) {
-          bool used = false;
-          for (int u = 0; u < i; ++u) used = used || top[u] == j;
-          if (!used && G[(size_t)j * D + j] > bestv) {
-            bestv = G[(size_t)j * D + j];
-            top[i] = j;
-          }
-        }
-        const double sk = std::sqrt(std::max(bestv, 0.0));
-        double cp = 0.0;
-        for (int k = 0; k < D; ++k) {
-          const double v = sk * V[(size_t)k * D + top[i]];
-          hP[((size_t)m * 4 + i) * DP + k] = v;
-          cp += v * mux[k];
-        }
-        hcP[(size_t)m * 4 + i] = cp;
-      }
-    }
-  }
-  });
-  {
-    const int bs = bad_singular.load(), bp = bad_notpd.load();
-    if (bs < M && bs <= bp) return fail(VCMI_ERR_NOT_PD, "Sigma^xx of mixture %d is singular", bs + 1);
-    if (bp < M) return fail(VCMI_ERR_NOT_PD, "Sigma^xx of mixture %d is not positive definite", bp + 1);
-  }
-  if (!px_only) g->model_active_frac = model_active_fraction(hU, hcz, hlc, hP, hcP, g->h_mux, w, D, DP, M, &g->model_undecided_frac, g->model_undecided_rows, &g->model_argmax_survivors_frac);
-  // row-major blocks for the generic kernels; a p(x)-only handle that takes the MFMA path needs only its packed blocks
-  // (device buffers are grow-only so that a handle re-prepared every EM iteration does not re-allocate)
-  if (!(px_only && gmmmap_has_mfma(DP))) {
-    VCMI_TRY(g->U.reserve(hU.size()));
-    VCMI_TRY(g->cz.reserve(hcz.size()));
-    VCMI_TRY(g->lc.reserve(hlc.size()));
-    VCMI_TRY(upload_now(g->U.p, hU.data(), hU.size() * 8));
-    VCMI_TRY(upload_now(g->cz.p, hcz.data(), hcz.size() * 8));
-    VCMI_TRY(upload_now(g->lc.p, hlc.data(), hlc.size() * 8));
-  }
-  if (!px_only) {
-    VCMI_TRY(g->A.reserve(hA.size()));
-    VCMI_TRY(g->b.reserve(hb.size()));
-    VCMI_TRY(upload_now(g->A.p, hA.data(), hA.size() * 8));
-    VCMI_TRY(upload_now(g->b.p, hb.data(), hb.size() * 8));
-    if (!gmmmap_has_mfma(DP) && D > 16 && D <= 160) {      // convert_from_logdens_kernel reads A transposed
-      std::vector<double> hAt(hA.size());
-      for (int m = 0; m < M; ++m)
-        for (int r = 0; r < DP; ++r)
-          for (int k = 0; k < DP; ++k) hAt[pp * m + (size_t)k * DP + r] = hA[pp * m + (size_t)r * DP + k];
-      VCMI_TRY(g->At.reserve(hAt.size()));
-      VCMI_TRY(upload_now(g->At.p, hAt.data(), hAt.size() * 8));
-    }
-  }
-
-  // packed operand blocks for the MFMA kernel (issue order: phase U k-major over U tiles, then phase A)
-  // variant 0: [U ; A] (convert), 1: U only (log-densities, predict), 2: U only, tile by tile with the LAST tile first
-  // (predict with early exit, MODE 3)
-  for (int uonly = px_only ? 1 : 0; uonly < 3 && gmmmap_has_mfma(DP); ++uonly) {
-    TilingRT tl(DP, uonly != 0);
-    std::vector<double> pk((size_t)tl.BLK * M, 0.0);
-    auto wrow = [&](int m, int p, int k) -> double {   // row p of [U_m ; A_m], column k
-      if (k >= DP) return 0.0;
-      if (p < DP) return hU[pp * m + (size_t)p * DP + k];
-      if (p < 2 * DP && !uonly) return hA[pp * m + (size_t)(p - DP) * DP + k];
-      return 0.0;
-    };
-    for (int m = 0; m < M; ++m) {
-      double *blk = &pk[(size_t)tl.BLK * m];
-      int s = 0;
-      if (uonly == 2) {
-        for (int t = std::min(tl.NU, tl.NT) - 1; t >= 0; --t)
-          for (int ks = 0; ks < tl.steps(t); ++ks) {
-            for (int l = 0; l < 64; ++l) blk[(size_t)s * 64 + l] = wrow(m, 16 * t + (l & 15), 4 * ks + (l >> 4));
-            ++s;
-          }
-      } else {
-        for (int phase = 0; phase < 2; ++phase) {
-          const int t0 = phase == 0 ? 0 : tl.NU, t1 = phase == 0 ? std::min(tl.NU, tl.NT) : tl.NT;
-          for (int ks = 0; ks < tl.KS; ++ks)
-            for (int t = t0; t < t1; ++t) {
-              if (ks >= tl.steps(t)) continue;
-              for (int l = 0; l < 64; ++l) blk[(size_t)s * 64 + l] = wrow(m, 16 * t + (l & 15), 4 * ks + (l >> 4));
-              ++s;
-            }
-        }
-      }
-      for (int p = 0; p < tl.NT * 16; ++p) {
-        double c = 0.0;
-        if (p < DP) c = -hcz[(size_t)DP * m + p];
-        else if (p < 2 * DP && !uonly) c = hb[(size_t)DP * m + (p - DP)];
-        blk[tl.CINIT_OFF + p] = c;
-      }
-      blk[tl.LC_OFF] = hlc[m];
-    }
-    DevBuf<double> &dst = uonly == 2 ? g->packedU2 : (uonly ? g->packedU : g->packed);
-    VCMI_TRY(dst.reserve(pk.size()));
-    VCMI_TRY(upload_now(dst.p, pk.data(), pk.size() * 8));
-  }
-  // stages of the screen of shape 3 (gmmmap_screen.hpp) on the first rpm rows of every mixture's P_m: rpm = the row count
-  // with the smallest estimated cost per 16-frame tile -- KS MFMAs screen 16 / rpm mixtures; a mixture the screen does not
-  // rule out costs its whole whitening (and usually its regression) for the four waves that share it
-  if (want_screen && screen_has_kernel(DP)) {
-    const int KSQ = DP / 4, QFR = screen_frag_doubles(DP), STG = screen_stage_doubles(DP), NQ = screen_quads(DP);
-    int best = 4;
-    double best_cost = 1e300;
-    for (int c = 0; c < 3; ++c) {
-      const int rpm = 4 >> c;
-      const double extra = std::max(0.0, g->model_undecided_rows[c] - 1.0 / M);      // wrong mixtures let through, per frame
-      const double cost = (double)KSQ * M * rpm / 16.0 + 4.0 * extra * M * (2 * KSQ + 2);
-      if (cost < best_cost) {
-        best_cost = cost;
-        best = rpm;
-      }
-    }
-    if (debug_flag(kDbgScreenRows4)) best = 4;        // (test hooks, read when the converter is CREATED)
-    if (debug_flag(kDbgScreenRows2)) best = 2;
-    if (debug_flag(kDbgScreenRows1)) best = 1;
-    g->screen_rpm = best;
-    g->model_undecided4_frac = g->model_undecided_rows[best == 4 ? 0 : best == 2 ? 1 : 2];     // what the chosen screen lets through
-    const int rpm = best, mpt = 16 / rpm, nst = (M + mpt * NQ - 1) / (mpt * NQ);
-    std::vector<double> pq((size_t)nst * STG, 0.0);
-    for (int st = 0; st < nst; ++st)
-      for (int q = 0; q < NQ; ++q) {
-        const int m0 = (NQ * st + q) * mpt;
-        double *fr = &pq[(size_t)st * STG + (size_t)q * KSQ * 64], *cl = &pq[(size_t)st * STG + QFR + (size_t)q * 32];
-        for (int ks = 0; ks < KSQ; ++ks)
-          for (int l = 0; l < 64; ++l) {
-            const int i = l & 15, k = 4 * ks + (l >> 4), m = m0 + screen_row_mixture(i, rpm), row = screen_row_index(i, rpm);
-            fr[(size_t)ks * 64 + l] = (m < M && k < DP) ? hP[((size_t)m * 4 + row) * DP + k] : 0.0;
-          }
-        for (int j = 0; j < 4; ++j) {
-          for (int r = 0; r < 4; ++r) {                        // register r of lane group j holds tile row 4 r + j
-            const int i = 4 * r + j, m = m0 + screen_row_mixture(i, rpm), row = screen_row_index(i, rpm);
-            cl[j * 8 + r] = (m < M) ? -hcP[(size_t)m * 4 + row] : 0.0;
-          }
-          for (int u = 0; u < 4; ++u) {                        // sub-mixture u of lane group j (u < 4 / rpm)
-            const int m = m0 + (4 / rpm) * j + u;
-            cl[j * 8 + 4 + u] = (u < 4 / rpm && m < M) ? hlc[m] : -std::numeric_limits<double>::infinity();
-          }
-        }
-      }
-    VCMI_TRY(g->packedQ.reserve(pq.size()));
-    VCMI_TRY(upload_now(g->packedQ.p, pq.data(), pq.size() * 8));
-    // the same four rows split into bf16 hi + lo for the screen on the BF16 matrix pipe (gmmmap_screen.hpp, B16)
-    if (rpm == 4 && screen16_has(DP)) {
-      const int KS8 = std::min(KSQ, 8), NTL = KSQ - KS8, STG16 = screen16_stage_doubles(DP), nst16 = (M + 4 * NQ - 1) / (4 * NQ);
-      std::vector<double> p16((size_t)nst16 * STG16, 0.0);
-      const double kEps = 1.0 / 4096.0;                            // 2^-12: see the error bound in gmmmap_screen.hpp
-      for (int st = 0; st < nst16; ++st)
-        for (int q = 0; q < NQ; ++q) {
-          const int m0 = (NQ * st + q) * 4;
-          unsigned short *fr = reinterpret_cast<unsigned short *>(&p16[(size_t)st * STG16 + (size_t)q * screen16_tile_doubles()]);
-          double *cl = &p16[(size_t)st * STG16 + (size_t)NQ * screen16_tile_doubles() + (size_t)q * 32];
-          for (int l = 0; l < 64; ++l) {
-            const int r = l & 15, gq = l >> 4, m = m0 + (r >> 2), row = r & 3;     // tile row r <-> mixture r >> 2, screening row r & 3
-            auto pv = [&](int ks) -> double {                      // P[row][feature 4 ks + lane group]
-              const int k = 4 * ks + gq;
-              return (m < M && ks < KSQ && k < DP) ? hP[((size_t)m * 4 + row) * DP + k] : 0.0;
-            };
-            unsigned short ph[10] = {0}, pl[10] = {0};
-            for (int ks = 0; ks < KSQ; ++ks) split_bf16(pv(ks), ph[ks], pl[ks]);
-            for (int j = 0; j < 8; ++j) {
-              fr[(size_t)l * 8 + j] = j < KS8 ? ph[j] : 0;                       // Ph, k-steps 0..7
-              fr[512 + (size_t)l * 8 + j] = j < KS8 ? pl[j] : 0;                 // Pl, k-steps 0..7
-            }
-            const unsigned short t0h = NTL > 0 ? ph[KS8] : 0, t1h = NTL > 1 ? ph[KS8 + 1] : 0;
-            const unsigned short t0l = NTL > 0 ? pl[KS8] : 0, t1l = NTL > 1 ? pl[KS8 + 1] : 0;
-            const unsigned short tail[8] = {t0h, t1h, t0h, t1h, t0l, t1l, 0, 0};  // against {xh8, xh9, xl8, xl9, xh8, xh9, 0, 0}
-            for (int j = 0; j < 8; ++j) fr[1024 + (size_t)l * 8 + j] = tail[j];
-          }
-          for (int j = 0; j < 4; ++j) {
-            const int m = m0 + j;
-            for (int r = 0; r < 4; ++r) {
-              double nrm = 0.0;
-              if (m < M)
-                for (int k = 0; k < D; ++k) nrm += hP[((size_t)m * 4 + r) * DP + k] * hP[((size_t)m * 4 + r) * DP + k];
-              const double c = (m < M) ? hcP[(size_t)m * 4 + r] : 0.0;
-              float *cf = reinterpret_cast<float *>(cl + j * 8);          // {c (4 floats) | 2^-12 |P| (4) | 2^-12 |c| (4)}, margins rounded UP
-              auto up = [](double v) { return std::nextafterf((float)(v * (1.0 + 0x1p-20)), INFINITY); };
-              cf[r] = (float)c;                                           // (its FP32 rounding is inside the 2^-12 |c| margin)
-              cf[4 + r] = up(kEps * std::sqrt(nrm));
-              cf[8 + r] = up(kEps * std::fabs(c));
-            }
-            cl[j * 8 + 6] = (m < M) ? hlc[m] : -std::numeric_limits<double>::infinity();
-          }
-        }
-      VCMI_TRY(g->packedQ16.reserve(p16.size()));
-      VCMI_TRY(upload_now(g->packedQ16.p, p16.data(), p16.size() * 8));
-    }
-  }
-  // ... and of predict's screen (gmmmap_screen_argmax_kernel): always four rows per mixture, every tile-kernel dimension
-  if (want_screen) {
-    const int KSQ = DP / 4, QFR = screen_frag_doubles(DP), STG = screen_stage_doubles(DP), NQ = screen_quads(DP);
-    const int nst = (M + 4 * NQ - 1) / (4 * NQ);
-    std::vector<double> pq((size_t)nst * STG, 0.0);
-    for (int st = 0; st < nst; ++st)
-      for (int q = 0; q < NQ; ++q) {
-        const int m0 = (NQ * st + q) * 4;
-        double *fr = &pq[(size_t)st * STG + (size_t)q * KSQ * 64], *cl = &pq[(size_t)st * STG + QFR + (size_t)q * 32];
-        for (int ks = 0; ks < KSQ; ++ks)
-          for (int l = 0; l < 64; ++l) {
-            const int i = l & 15, k = 4 * ks + (l >> 4), m = m0 + (i & 3), row = i >> 2;
-            fr[(size_t)ks * 64 + l] = (m < M && k < DP) ? hP[((size_t)m * 4 + row) * DP + k] : 0.0;
-          }
-        for (int j = 0; j < 4; ++j) {
-          const int m = m0 + j;
-          for (int r = 0; r < 4; ++r) cl[j * 8 + r] = (m < M) ? -hcP[(size_t)m * 4 + r] : 0.0;
-          for (int u = 0; u < 4; ++u) cl[j * 8 + 4 + u] = (u == 0 && m < M) ? hlc[m] : -std::numeric_limits<double>::infinity();
-        }
-      }
-    VCMI_TRY(g->packedQA.reserve(pq.size()));
-    VCMI_TRY(upload_now(g->packedQA.p, pq.data(), pq.size() * 8));
-  }
-  if (!g->h_mux.empty()) {     // operand of the frame grouping (gmmmap_group_key_kernel): [-2 mu^x | |mu^x|^2] over its first dimensions, fragment order
-    const int KSK = std::min(DP / 4, kGroupKeyDims / 4), KS1 = KSK + 1, MT = (M + 15) / 16, DK = std::min(D, 4 * KSK);
-    std::vector<double> gf((size_t)MT * KS1 * 64, 0.0);
-    for (int mt = 0; mt < MT; ++mt)
-      for (int ks = 0; ks < KS1; ++ks)
-        for (int l = 0; l < 64; ++l) {
-          const int m = 16 * mt + (l & 15), k = 4 * ks + (l >> 4);
-          double v = 0.0;
-          if (ks < KS1 - 1) {
-            if (m < M && k < DK) v = -2.0 * g->h_mux[(size_t)D * m + k];
-          } else if ((l >> 4) == 0) {
-            v = 1e300;
-            if (m < M) {
-              v = 0.0;
-              for (int d = 0; d < DK; ++d) v += g->h_mux[(size_t)D * m + d] * g->h_mux[(size_t)D * m + d];
-            }
-          }
-          gf[((size_t)mt * KS1 + ks) * 64 + l] = v;
-        }
-    VCMI_TRY(g->gfrag.reserve(gf.size()));
-    VCMI_TRY(upload_now(g->gfrag.p, gf.data(), gf.size() * 8));
-    // ... and for the BF16 matrix pipe (gmmmap_group_key16_kernel): -2 mu split into bf16 hi + lo, |mu|^2 as floats
-    {
-      std::vector<double> g16((size_t)MT * (kKey16TileBytes / 8), 0.0);
-      for (int mt = 0; mt < MT; ++mt) {
-        unsigned short *hi = reinterpret_cast<unsigned short *>(&g16[(size_t)mt * (kKey16TileBytes / 8)]), *lo = hi + 512;
-        float *msq = reinterpret_cast<float *>(hi + 1024);
-        for (int l = 0; l < 64; ++l) {
-          const int m = 16 * mt + (l & 15), gq = l >> 4;
-          for (int j = 0; j < 8; ++j) {
-            const int k = 4 * j + gq;
-            const double v = (m < M && j < KSK && k < DK) ? -2.0 * g->h_mux[(size_t)D * m + k] : 0.0;
-            split_bf16(v, hi[(size_t)l * 8 + j], lo[(size_t)l * 8 + j]);
-          }
-        }
-        for (int r = 0; r < 16; ++r) {
-          const int m = 16 * mt + r;
-          double v = 1e30;
-          if (m < M) {
-            v = 0.0;
-            for (int d = 0; d < DK; ++d) v += g->h_mux[(size_t)D * m + d] * g->h_mux[(size_t)D * m + d];
-          }
-          msq[r] = (float)v;                                  // lane group r >> 2 reads floats 4 (r >> 2) .. + 3
-        }
-      }
-      VCMI_TRY(g->gfrag16.reserve(g16.size()));
-      VCMI_TRY(upload_now(g->gfrag16.p, g16.data(), g16.size() * 8));
-    }
-  }
-  return VCMI_OK;
-}
-
-// p(x)-only handle over a plain GMM of dimension D (weights (M), mu (D,M), sigma (D,D,M)); used by estep.hip.
-// *inout == nullptr creates a handle; otherwise the existing handle (same device) is re-prepared in place, reusing its
-// device buffers -- the caller must have drained every stream that still reads them.
-int gmm_px_create(const double *w, const double *mu, const double *sigma, int D, int M, vcmi_gmmmap **inout) {
-  VCMI_TRY(check_device());
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  if (*inout && (*inout)->device != dev) {
-    delete *inout;
-    *inout = nullptr;
-  }
-  vcmi_gmmmap *g = *inout ? *inout : new (std::nothrow) vcmi_gmmmap();
-  if (!g) return fail(VCMI_ERR_OOM, "out of host memory");
-  g->device = dev;
-  int rc = prepare(g, w, mu, sigma, D, M, 0, /*px_only=*/true);
-  if (rc != VCMI_OK) {
-    delete g;
-    *inout = nullptr;
-    return rc;
-  }
-  *inout = g;
   return VCMI_OK;
 }
 
@@ -2588,16 +2019,8 @@ int gmm_px_prepare_device(vcmi_gmmmap **inout, const double *d_w, const double *
                           int *d_flag, hipStream_t st) {
   VCMI_TRY(check_device());
   if (!gmm_px_device_prepare_supported(D)) return fail(VCMI_ERR_ARG, "on-device p(x) preparation: dimension %d too large", D);
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  if (*inout && (*inout)->device != dev) {
-    delete *inout;
-    *inout = nullptr;
-  }
-  vcmi_gmmmap *g = *inout ? *inout : new (std::nothrow) vcmi_gmmmap();
-  if (!g) return fail(VCMI_ERR_OOM, "out of host memory");
-  *inout = g;
-  g->device = dev;
+  VCMI_TRY(gmm_px_handle_here(inout));
+  vcmi_gmmmap *g = *inout;
   const int DP = (D + 3) / 4 * 4;
   g->D = D;
   g->DP = DP;
@@ -2609,14 +2032,10 @@ int gmm_px_prepare_device(vcmi_gmmmap **inout, const double *d_w, const double *
   TilingRT tl(DP, true);
   if (mfma) {
     VCMI_TRY(g->packedU.reserve((size_t)tl.BLK * M));
-    if (g->px_table_dp != DP) {           // issue order: k-major over the U tiles (the host packer's phase 0)
+    if (g->px_table_dp != DP) {           // the issue order of the U-only blocks (what pack_tiles(1) writes on the host)
       std::vector<int> tab;
-      for (int ks = 0; ks < tl.KS; ++ks)
-        for (int t = 0; t < std::min(tl.NU, tl.NT); ++t)
-          if (ks < tl.steps(t)) tab.push_back((t << 16) | ks);
-      if ((int)tab.size() != tl.NSTEPS) return fail(VCMI_ERR_ARG, "internal: tiling table mismatch");
-      VCMI_TRY(g->px_table.reserve(tab.size()));
-      VCMI_TRY(upload_now(g->px_table.p, tab.data(), tab.size() * sizeof(int)));
+      for_each_fragment(tl, 1, [&](int t, int ks) { tab.push_back((t << 16) | ks); });
+      VCMI_TRY(upload_now(g->px_table, tab));
       g->px_table_dp = DP;
     }
   }
@@ -2669,7 +2088,7 @@ int gmmmap_member(vcmi_gmmmap *g, int member, vcmi_gmmmap **out) {
     vcmi_gmmmap *n = new (std::nothrow) vcmi_gmmmap();
     if (!n) return fail(VCMI_ERR_OOM, "out of host memory");
     (void)hipGetDevice(&n->device);
-    const int rc = prepare(n, g->in_w.data(), g->in_mu.data(), g->in_sigma.data(), g->in_Dj, g->M, g->in_swap);
+    const int rc = gmmmap_prepare(n, g->in_w.data(), g->in_mu.data(), g->in_sigma.data(), g->in_Dj, g->M, g->in_swap);
     if (rc != VCMI_OK) {
       delete n;
       return rc;
@@ -2719,7 +2138,7 @@ extern "C" int vcmi_gmmmap_create(const double *weights, const double *mu, const
   vcmi_gmmmap *g = new (std::nothrow) vcmi_gmmmap();
   if (!g) return fail(VCMI_ERR_OOM, "out of host memory");
   (void)hipGetDevice(&g->device);
-  int rc = prepare(g, weights, mu, sigma, Dj, M, swap);
+  int rc = gmmmap_prepare(g, weights, mu, sigma, Dj, M, swap);
   if (rc != VCMI_OK) {
     delete g;
     return rc;
@@ -2782,8 +2201,8 @@ extern "C" int vcmi_gmmmap_convert_plan(vcmi_gmmmap *g, int64_t *mfma_issued, in
     }
   }
   if (shape) *shape = !use_mfma(g) ? -1 : (!(g->prune < 1e300) ? 0 : convert_shape(g));
-  if (model_active_frac) *model_active_frac = g->model_active_frac;
-  if (model_undecided_frac) *model_undecided_frac = g->model_undecided_frac;
+  if (model_active_frac) *model_active_frac = g->model.active;
+  if (model_undecided_frac) *model_undecided_frac = g->model.undecided;
   return VCMI_OK;
 }
 

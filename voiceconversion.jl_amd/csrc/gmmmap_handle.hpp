@@ -1,6 +1,26 @@
-// gmmmap_handle.hpp -- the opaque vcmi_gmmmap handle (shared by gmmmap.hip and traj.hip).
+// gmmmap_handle.hpp -- the opaque vcmi_gmmmap handle (shared by gmmmap.hip, gmmmap_prepare.cpp, estep.hip and traj.hip).
 #pragma once
 #include "vcmi_common.hpp"
+#include "gmmmap_layout.hpp"
+
+namespace vcmi {
+// What 256 frames drawn from the model itself say about it (sampled on the host by profile_model(), gmmmap_prepare.cpp, fixed
+// seed): fractions of the M mixtures, means over the frames.
+struct ModelProfile {
+  // within e^-46 of the best one for the frame.  Reported by vcmi_gmmmap_convert_plan (synthetic SURVEY 8d models: 1/M; the
+  // reference's trained 32-mixture model: 0.37).
+  double active = 0.0;
+  // ... that the LAST 16-row whitening tile's share of |z|^2 alone does not put e^-46 under the best one: what the "peaked"
+  // loop's first test leaves undecided.  Selects the loop shape (convert_shape).
+  double undecided = 0.0;
+  // ... that the 4 / 2 / 1 strongest screening rows (largest eigenpairs of inv(Sxx_m)) leave undecided: what the screen of
+  // shape 3 (gmmmap_screen.hpp) lets through with that many rows per mixture
+  double undecided_rows[3] = {1.0, 1.0, 1.0};
+  // ... whose four-row bound reaches the frame's best log-density: what predict's screen (gmmmap_screen_argmax_kernel) would
+  // have to evaluate in full besides the frame's own mixture
+  double argmax_survivors = 1.0;
+};
+}  // namespace vcmi
 
 struct vcmi_gmmmap {
   int D = 0;    // dim(g): source feature dimension, src/gmmmap.jl:94
@@ -12,22 +32,11 @@ struct vcmi_gmmmap {
   // the posterior there is below e^-prune (1e-20 at 46: under the rounding error of the sum).  +inf: dense loop.
   double prune = 46.0;
   vcmi::DevBuf<unsigned long long> prune_count;   // optional diagnostic counters (vcmi_gmmmap_prune_stats): [0] (tile, mixture) regressions, [1] FP64 MFMAs issued, [2] BF16 MFMAs of the screen
-  // Mean fraction of the mixtures that lie within e^-46 of the best one for a frame drawn from the model itself (256 frames
-  // sampled on the host by prepare(), fixed seed).  Reported by vcmi_gmmmap_convert_plan (synthetic SURVEY 8d models: 1/M;
-  // the reference's trained 32-mixture model: 0.37).
-  double model_active_frac = 0.0;
-  // ... and the mean fraction of the mixtures that the LAST 16-row whitening tile's share of |z|^2 alone does not put
-  // e^-46 under the best one: what the "peaked" loop's first test leaves undecided.  Selects the loop shape (convert_shape).
-  double model_undecided_frac = 0.0;
-  // ... and the fractions that the 4 / 2 / 1 strongest screening rows (largest eigenpairs of inv(Sxx_m)) leave undecided: what the screen of shape 3
-  // (gmmmap_screen.hpp) lets through with that many rows per mixture.  prepare() picks screen_rpm (the cheapest) and keeps its
-  // fraction in model_undecided4_frac: small (<= kScreenModelFrac) -> grouped calls run the screening kernel.
-  double model_undecided_rows[3] = {1.0, 1.0, 1.0};
-  double model_undecided4_frac = 1.0;
+  vcmi::ModelProfile model;
+  // rows per mixture of fvconvert's screen (choose_screen_rows(): the cheapest for this model) and what that many rows leave
+  // undecided (model.undecided_rows): small (<= kScreenModelFrac) -> grouped calls run the screening kernel
   int screen_rpm = 4;
-  // mean fraction of the mixtures whose four-row bound reaches a model-drawn frame's best log-density: what predict's screen
-  // (gmmmap_screen_argmax_kernel) would have to evaluate in full besides the frame's own mixture
-  double model_argmax_survivors_frac = 1.0;
+  double model_undecided4_frac = 1.0;
 
   // host copies kept for accessors and for TrajectoryGMMMap's constructor (row-major (D,D) per mixture)
   std::vector<double> h_A_julia;   // Julia memory image (D,D,M) of ΣʸˣΣˣˣ⁻¹
@@ -69,7 +78,17 @@ struct vcmi_gmmmap {
 };
 
 namespace vcmi {
-bool gmmmap_has_mfma(int DP);
+// Host-side preparation (gmmmap_prepare.cpp): factorises the joint GMM (weights (M), mu (Dj,M), sigma (Dj,Dj,M), Julia
+// memory images), profiles it, and packs and uploads every device image of g on the current device.
+// px_only: (mu, sigma) describe a plain GMM p(x) of dimension Dj (no target half): only the whitening side is prepared
+// (used by the full-covariance E-step, estep.hip); the regression blocks stay zero and the convert layouts are skipped.
+int gmmmap_prepare(vcmi_gmmmap *g, const double *w, const double *mu, const double *sigma, int Dj, int M, int swap,
+                   bool px_only = false);
+// *inout becomes a handle on the current device: the existing one if it lives there, else a new one (the old one deleted)
+int gmm_px_handle_here(vcmi_gmmmap **inout);
+// p(x)-only handle over a plain GMM of dimension D (weights (M), mu (D,M), sigma (D,D,M)); used by estep.hip.
+// *out == nullptr creates a handle; otherwise the existing handle (same device) is re-prepared in place, reusing its
+// device buffers -- the caller must have drained every stream that still reads them.
 int gmm_px_create(const double *w, const double *mu, const double *sigma, int D, int M, vcmi_gmmmap **out);
 // Same handle prepared ON THE DEVICE from device-resident parameters (w (M), mu (D,M), sigma (D,D,M)): one workgroup
 // per mixture does the Cholesky, the triangular inverse and the MFMA operand packing.  Asynchronous on `st`;

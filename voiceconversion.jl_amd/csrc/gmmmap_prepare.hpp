@@ -1,0 +1,37 @@
+// gmmmap_prepare.hpp -- the steps of gmmmap_prepare() (gmmmap_handle.hpp), each a host function of its own: factor the
+// model, profile it, choose the screen's rows, pack the device images.  Only factor_model() touches a handle (its host
+// copies); nothing here touches the device, so the steps also run in the CPU sanitizer build (tests/c/prepare_check.cpp).
+#pragma once
+#include <vector>
+#include "gmmmap_handle.hpp"
+
+namespace vcmi {
+
+// Row-major host images of a factored model, rows and columns padded with zeros to DP.
+struct HostModel {
+  int D = 0, DP = 0, M = 0;
+  bool px_only = false;             // p(x) only: A and b are empty
+  std::vector<double> U, A;         // [M][DP][DP]
+  std::vector<double> cz, b;        // [M][DP]
+  std::vector<double> lc;           // [M]
+  std::vector<double> P, cP;        // screening rows [M][4][DP], strongest first, and their constants [M][4]; empty: no screen
+};
+// Fills hm and g's host copies (h_A_julia, h_A, h_Sxy, h_Syy, h_mux, h_muy) from the joint GMM; VCMI_ERR_NOT_PD names the
+// first mixture whose Sigma^xx cannot be factored.
+int factor_model(vcmi_gmmmap *g, HostModel &hm, const double *w, const double *mu, const double *sigma, int Dj, int M, int swap,
+                 bool px_only);
+
+// ModelProfile: gmmmap_handle.hpp
+ModelProfile profile_model(const HostModel &hm, const std::vector<double> &mux, const double *w);
+// rows per mixture (4, 2 or 1) of fvconvert's screen with the smallest estimated cost per 16-frame tile
+int choose_screen_rows(const ModelProfile &pf, int DP, int M);
+
+// The device images (gmmmap_handle.hpp names them; gmmmap_layout.hpp gives their layouts and lengths).
+std::vector<double> pack_tiles(const HostModel &hm, int variant);    // packed (0), packedU (1), packedU2 (2): for_each_fragment's variants
+std::vector<double> pack_screen(const HostModel &hm, int rpm);       // packedQ; rpm = 4: packedQA
+std::vector<double> pack_screen_bf16(const HostModel &hm);           // packedQ16 (four rows per mixture)
+std::vector<double> pack_group_keys(const HostModel &hm, const std::vector<double> &mux);        // gfrag
+std::vector<double> pack_group_keys_bf16(const HostModel &hm, const std::vector<double> &mux);   // gfrag16
+std::vector<double> transpose_A(const HostModel &hm);                // At
+
+}  // namespace vcmi

@@ -6,7 +6,7 @@
 // share of |z|^2 is a lower bound of |z|^2.  |z_m|^2 = (x - mu_m)' inv(Sxx_m) (x - mu_m) = sum_i kappa_i (v_i' (x - mu_m))^2
 // over the eigenpairs of inv(Sxx_m): ANY partial sum is a lower bound, and the largest kappa (the directions of smallest
 // variance) give the largest one per row.  So the proof is made with the rows sqrt(kappa_i) v_i' of the FOUR largest
-// eigenpairs (prepare(), host: Jacobi), and the MFMA result layout does the rest: lane group g of a 16 x 16 result holds rows
+// eigenpairs (factor_model(), gmmmap_prepare.cpp: Jacobi on the host), and the MFMA result layout does the rest: lane group g of a 16 x 16 result holds rows
 // {g, 4 + g, 8 + g, 12 + g}, so a tile whose row 4 r + j is screening row r of mixture j gives lane group j
 // the four rows of mixture j -- its bound is four multiply-adds in the lane, no cross-lane sum, and ONE tile of KS
 // MFMAs screens FOUR mixtures (2.5 MFMAs per pair instead of 10).  Per workgroup (WAVES waves x FT tiles of 16 frames):
@@ -23,45 +23,10 @@
 #pragma once
 #include <type_traits>
 #include "bf16_split.hpp"
+#include "gmmmap_layout.hpp"      // rows per mixture, stage layouts of the FP64 and the bf16 screen
 #include "lds_dma.hpp"
 
 namespace vcmi {
-
-// ROWS PER MIXTURE (rpm, chosen per model by prepare(): the fewest rows that still rule (almost) every wrong mixture out):
-//   4: lane group j of a screening tile = mixture j's four strongest rows               ->  4 mixtures per tile
-//   2: registers {0,1} of lane group j = mixture 2j's two strongest rows, {2,3} = mixture 2j+1's  ->  8 mixtures per tile
-//   1: register r of lane group j = the strongest row of mixture 4j + r                  -> 16 mixtures per tile (KS MFMAs screen 16)
-// screening tiles per stage (one barrier per stage: 16 / 32 / 64 mixtures at four): two beyond DP = 48, where a stage of four
-// would no longer leave room for two workgroups per CU beside the 32 KB whitening block
-__host__ __device__ constexpr int screen_quads(int DP) { return DP <= 48 ? 4 : 2; }
-
-// stage layout in doubles: [QS x KS x 64 operand fragments | QS x 4 lane groups x 8 {cinit r = 0..3, lc of sub-mixture 0..3}], whole KB
-__host__ __device__ constexpr int screen_frag_doubles(int DP) { return screen_quads(DP) * (DP / 4) * 64; }
-__host__ __device__ constexpr int screen_stage_doubles(int DP) { return (screen_frag_doubles(DP) + screen_quads(DP) * 32 + 127) / 128 * 128; }
-// which mixture (relative to the tile's first) and which of its screening rows (0 = the strongest) tile row i stands for
-__host__ __device__ constexpr int screen_row_mixture(int i, int rpm) { return (4 / rpm) * (i & 3) + (i >> 2) / rpm; }
-__host__ __device__ constexpr int screen_row_index(int i, int rpm) { return (i >> 2) % rpm; }
-
-// ---- the screen on the BF16 matrix pipe (B16 = true; rpm = 4, DP <= 40) --------------------------------------------------
-// The screen only has to produce a CERTIFIED lower bound of sum_i a_i^2, a_i = P_i x - c_i.  v_mfma_f32_16x16x32_bf16 runs
-// at 16x the FP64 MFMA rate, so P and x are split into two bf16 pieces each (hi + lo: 16 of their 53 bits) and
-//   a^ = Ph xh + Ph xl + Pl xh - c      (three K = 32 instructions over the first eight k-steps of the FP64 operand layout -- lane
-//                                        group g, slot j <-> feature 4 j + g, exactly what the lane's xb[.][j] holds -- and one
-//                                        more whose slots carry the three terms of k-steps 8, 9), accumulated in FP32.
-// |a^ - a| <= (dropped Pl xl and the two split residuals: 3 x 2^-16; FP32 accumulation of <= 130 exact products: 2^-15)
-//             x sum_k |P_ik||x_k|  +  2^-24 |c_i|   <=   eps_i := 2^-12 (|P_i| |x| + |c_i|)       (Cauchy-Schwarz; ~2 x the sum above),
-// so  a_i^2 >= max(|a^_i| - eps_i, 0)^2  and  lc - sum_i max(|a^_i| - eps_i, 0)^2 / 2  is still an upper bound of the mixture's
-// log-density: a mixture it rules out is ruled out.  eps is ~0.3 where the test needs |a| of 10 and more: what the screen
-// decides hardly changes, its matrix work drops from 10 FP64 MFMAs (640 cycles) to 4 BF16 ones (64 cycles) per tile.
-// The FP32 result layout gives lane group j rows 4 j .. 4 j + 3: tile row i <-> mixture i >> 2, screening row i & 3.
-// The margins and the sum of squares are formed in FP32 (the FP64 vector pipe is the one the conversion itself needs): the
-// constants are rounded UP on the host (and carry a factor 1 + 2^-20 for the FP32 roundings of eps), the sum is taken down by
-// 1 - 2^-20 before it is used.
-// Stage layout in doubles: per tile [Ph main | Pl main | tail] as 3 x 1 KB of bf16x8 per lane, then per tile and lane group
-// 8 doubles {c_0..3 (4 floats), 2^-12 |P_0..3| (4 floats), 2^-12 |c_0..3| (4 floats), lc (double), pad}.
-__host__ __device__ constexpr int screen16_tile_doubles() { return 3 * 128; }
-__host__ __device__ constexpr int screen16_stage_doubles(int DP) { return screen_quads(DP) * (screen16_tile_doubles() + 32); }
-__host__ __device__ constexpr bool screen16_has(int DP) { return DP >= 16 && DP <= 40 && DP % 4 == 0; }
 
 template <int DP, int FT, int WAVES, bool B16 = false>
 __global__ void __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(DP <= 40 ? (FT == 2 ? 3 : 4) : 2)))

@@ -34,6 +34,12 @@ int staged_upload(void *dDst, const void *hSrc, size_t bytes, hipStream_t consum
 // around the same heap addresses -- that DMA hit an unmapped page about once in three runs: "Memory access fault by GPU" inside
 // vcmi_gmmmap_create, round 6.)
 int upload_now(void *dDst, const void *hSrc, size_t bytes);
+// ... a whole vector into a grow-only device buffer (a handle that is re-prepared does not re-allocate)
+template <class T>
+int upload_now(DevBuf<T> &dst, const std::vector<T> &v) {
+  VCMI_TRY(dst.reserve(v.size()));
+  return upload_now(dst.p, v.data(), v.size() * sizeof(T));
+}
 inline hipError_t upload_now_hip(void *dDst, const void *hSrc, size_t bytes) {      // for call sites that chain hipError_t
   return upload_now(dDst, hSrc, bytes) == VCMI_OK ? hipSuccess : hipErrorUnknown;
 }

@@ -1502,20 +1502,21 @@ extern "C" int vcmi_traj_create(vcmi_gmmmap *g, int64_t T, vcmi_traj **out) {
       bv[(size_t)D2 * m + r] = g->h_muy[(size_t)D2 * m + r] - ba;
     }
   }
-  // Q in MFMA A-operand order for the GV ascent: lane l of fragment (row tile i, k-step ks) holds Q[16i + (l&15)][4ks + (l>>4)]
+  // Q in MFMA A-operand order for the GV ascent: fragment (row tile i, k-step ks) holds rows 16 i .. 16 i + 15, columns 4 ks .. 4 ks + 3
+  // (the lane rule: fill_fragment, gmmmap_layout.hpp)
   t->NT = (D2 + 15) / 16;
   t->KS = (D2 + 3) / 4;
   std::vector<double> Qf((size_t)M * t->NT * t->KS * 64, 0.0), Af(Qf.size(), 0.0);
   for (int m = 0; m < M; ++m)
     for (int i = 0; i < t->NT; ++i)
-      for (int ks = 0; ks < t->KS; ++ks)
-        for (int l = 0; l < 64; ++l) {
-          const int r = 16 * i + (l & 15), k = 4 * ks + (l >> 4);
-          if (r < D2 && k < D2) {
-            Qf[(((size_t)m * t->NT + i) * t->KS + ks) * 64 + l] = Q[nn * m + (size_t)r * D2 + k];
-            Af[(((size_t)m * t->NT + i) * t->KS + ks) * 64 + l] = g->h_A[nn * m + (size_t)r * D2 + k];
-          }
-        }
+      for (int ks = 0; ks < t->KS; ++ks) {
+        auto frag = [&](const double *W, std::vector<double> &F) {     // tile (i, ks) of the row-major (D2,D2) matrix W, zero outside it
+          fill_fragment(&F[(((size_t)m * t->NT + i) * t->KS + ks) * 64], ks,
+                        [&](int row, int k) { return (16 * i + row < D2 && k < D2) ? W[(size_t)(16 * i + row) * D2 + k] : 0.0; });
+        };
+        frag(&Q[nn * m], Qf);
+        frag(&g->h_A[nn * m], Af);
+      }
   t->Dpad = traj_blk_padded_dim(D);
   if (t->Dpad) {
     const int Dp = t->Dpad, Dp2 = 2 * Dp;
