@@ -1704,10 +1704,14 @@ static int estep_full_device(const double *dX, int64_t N, int Dj, int M, const d
 // ------------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(256)
 em_mstep_full_kernel(const double *__restrict__ stats, int Dj, int M, double min_covar, double *__restrict__ w,
-                     double *__restrict__ mu, double *__restrict__ sigma) {
+                     double *__restrict__ mu, double *__restrict__ sigma, const int *__restrict__ flag) {
   __shared__ double red[256];
   __shared__ double mus[256];
   const int tid = threadIdx.x, m = blockIdx.x;
+  // a covariance of the CURRENT parameters was reported not positive definite: the statistics computed under them are NaN
+  // for every mixture.  Keep the parameters, so that the preparation that follows reports the same mixture again (and not
+  // the last one of a model that is NaN throughout) and vcmi_gmm_em_get still shows the model that failed.
+  if (*flag) return;
   const double eps = 2.220446049250313e-16;
   double t = 0.0;
   for (int k = tid; k < M; k += 256) t += stats[k];
@@ -1752,11 +1756,15 @@ struct vcmi_gmm_em {
 
 namespace vcmi {
 static int em_prepare(vcmi_gmm_em *h, hipStream_t st) {
+  // a host preparation that fails (not positive definite) deletes the handle: the state is unprepared until one succeeds,
+  // so that the next E-step prepares (and reports) again instead of running on a handle that is gone
+  h->prepared = false;
   if (gmm_px_device_prepare_supported(h->Dj)) {
     VCMI_TRY(gmm_px_prepare_device(&h->px, h->w(), h->mu(), h->sigma(), h->Dj, h->M, h->flag.p, st));
   } else {
-    // dimensions without a device preparation (Dj > 160, and 98 < Dj whose padded size has an MFMA instantiation --
-    // there is none today): Cholesky on the host
+    // dimensions without a device preparation (198 < Dj <= 256: px_prep_kernel serves Dj <= 99, px_prep_packed_kernel
+    // 100 <= Dj <= 198 -- and 99 < Dj whose padded size has an MFMA instantiation; there is none today): Cholesky on the
+    // host, with a stream synchronisation
     const size_t dd = (size_t)h->Dj * h->Dj;
     std::vector<double> hw(h->M), hmu((size_t)h->M * h->Dj), hs((size_t)h->M * dd);
     VCMI_HIP(hipStreamSynchronize(st));
@@ -1911,7 +1919,7 @@ extern "C" int vcmi_gmm_em_mstep(vcmi_gmm_em *h, const double *dstats, void *str
   if (!h || !dstats) return fail(VCMI_ERR_ARG, "vcmi_gmm_em_mstep: NULL argument");
   hipStream_t st = as_stream(stream);
   hipLaunchKernelGGL(em_mstep_full_kernel, dim3(h->M), dim3(256), 0, st, dstats, h->Dj, h->M, h->min_covar, h->w(), h->mu(),
-                     h->sigma());
+                     h->sigma(), h->flag.p);
   VCMI_HIP(hipGetLastError());
   VCMI_TRY(em_prepare(h, st));
   double ll = 0.0;

@@ -1923,7 +1923,7 @@ px_prep_kernel(const double *__restrict__ w, const double *__restrict__ mu, cons
   }
 }
 
-// The same preparation for dimensions whose two D x (D+1) images do not fit LDS (D > 98, e.g. the 160-dimensional joint
+// The same preparation for dimensions whose two D x (D+1) images do not fit LDS (99 < D <= 198, e.g. the 160-dimensional joint
 // model of delta features): ONE lower triangle in packed storage (D(D+1)/2 doubles: 103 KB at D = 160) holds the
 // covariance, then its Cholesky factor, then -- inverted in place, column by column from the last, with the column
 // being replaced kept in a D-vector -- U = L^-1.  Outputs: the generic layout only (U, cz, lc: what
@@ -2004,7 +2004,7 @@ px_prep_packed_kernel(const double *__restrict__ w, const double *__restrict__ m
   }
 }
 
-static bool px_prep_fits_full(int D) {      // px_prep_kernel: two D x (D+1) images
+static bool px_prep_fits_full(int D) {      // px_prep_kernel: two D x (D+1) images (D <= 99: 158,400 B + 2 KB static of 160 KB)
   return (size_t)2 * D * (D + 1) * sizeof(double) + 4096 <= (size_t)160 * 1024;
 }
 bool gmm_px_device_prepare_supported(int D) {
