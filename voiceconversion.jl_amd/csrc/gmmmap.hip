@@ -1222,20 +1222,26 @@ convert_from_logdens_kernel(const double *__restrict__ LP, int M, int D, int DP,
 // that union large; the same frames grouped by mixture leave one or two.  The grouping does not have to be right -- any
 // permutation gives the same y, frame by frame -- only cheap and mostly right: the NEAREST SOURCE MEAN (Euclidean), one
 // small MFMA product per tile ([-2 mu | |mu|^2] x [x ; 1], 44 MFMAs per 16 frames at D = 40, M = 64 against 2400 for the
-// conversion).  Three kernels: keys + a histogram per chunk of 1024 frames, a prefix over (group, chunk), and a STABLE
-// counting-sort scatter (round 4; the first version ranked with LDS / global atomics, which left the order inside a group --
-// hence the tiles, the rotated mixture order of a boundary workgroup and the last bit of a frame shared by several
-// mixtures -- to the scheduler).
+// conversion).  A STABLE counting sort (round 4; the first version ranked with LDS / global atomics, which left the order
+// inside a group -- hence the tiles, the rotated mixture order of a boundary workgroup and the last bit of a frame shared by
+// several mixtures -- to the scheduler) in TWO launches: keys + a histogram per chunk of 1024 frames and per super-chunk of
+// ~sqrt(nchunks) chunks (gmmmap_group_key16_kernel / gmmmap_group_key_kernel), and the scatter, every workgroup of which sums
+// the few histogram rows in front of its chunk itself (gmmmap_group_place_kernel).  It used to be three: a prefix over
+// (group, chunk) stood between them (gmmmap_group_scan_kernel) only to hand every scatter workgroup that sum -- a launch, its
+// drain and its ramp on a path of four dependent kernels.  The E-step's hard path (estep.hip), whose launches are gated by a
+// device word, still runs that scan and gmmmap_group_scatter_kernel.  The scatter also leaves gbase[0 .. M], the first
+// sorted position of every group: the screen kernels take their groups from it instead of a key per frame.
 // gfrag[mt][ks][lane]: A-operand fragments, rows = mixtures 16 mt + (lane & 15), k = 4 ks + (lane >> 4); the last k-step
 // carries |mu|^2 (rows >= M: 1e300, never the minimum).
 // ------------------------------------------------------------------------------------------------
 // keys + one histogram per CHUNK of 1024 consecutive frames (chunkhist[c][m]); a workgroup walks chunks blockIdx.x,
 // blockIdx.x + gridDim.x, ... with the operand fragments staged once.  The counts are integers: whatever order the LDS
-// atomics arrive in, the histogram is the same.
+// atomics arrive in, the histogram is the same.  superhist[c >> super_shift][m] (zero on entry: launch_grouping) receives
+// the chunk histograms' sums by vector atomic adds to global memory, integers again.
 template <int DP>
 __global__ void __launch_bounds__(256)
 gmmmap_group_key_kernel(const double *__restrict__ gfrag, int M, int D, const double *__restrict__ X, int64_t ldx, int64_t T,
-                        int *__restrict__ key, int *__restrict__ chunkhist) {
+                        int *__restrict__ key, int *__restrict__ chunkhist, int *__restrict__ superhist, int super_shift) {
   // KS: the k-steps the key LOOKS AT -- the first 24 dimensions at most (kGroupKeyDims).  The key only has to be cheap and
   // mostly right, and the distance over 24 of 40 dimensions picks the same groups (CPU simulation of the kernel's rule, 6e4
   // frames: regressions evaluated 0.0168 / 0.0168 on the SURVEY 8d model, 0.6765 / 0.6760 on the reference's trained model,
@@ -1291,7 +1297,11 @@ gmmmap_group_key_kernel(const double *__restrict__ gfrag, int M, int D, const do
       }
     }
     __syncthreads();
-    for (int m = tid; m < M; m += 256) chunkhist[c * M + m] = hist[m];
+    for (int m = tid; m < M; m += 256) {
+      const int h = hist[m];
+      chunkhist[c * M + m] = h;
+      if (h) atomicAdd(&superhist[(c >> super_shift) * M + m], h);   // (integers: the sum does not depend on the order of arrival)
+    }
     __syncthreads();
   }
 }
@@ -1306,7 +1316,7 @@ gmmmap_group_key_kernel(const double *__restrict__ gfrag, int M, int D, const do
 template <int DP>
 __global__ void __launch_bounds__(256)
 gmmmap_group_key16_kernel(const double *__restrict__ gfrag16, int M, int D, const double *__restrict__ X, int64_t ldx, int64_t T,
-                          int *__restrict__ key, int *__restrict__ chunkhist) {
+                          int *__restrict__ key, int *__restrict__ chunkhist, int *__restrict__ superhist, int super_shift) {
   constexpr int KS = (DP / 4 < kGroupKeyDims / 4) ? DP / 4 : kGroupKeyDims / 4;
   static_assert(KS <= 8, "one K = 32 instruction per term");
   extern __shared__ double gsm[];
@@ -1382,7 +1392,11 @@ gmmmap_group_key16_kernel(const double *__restrict__ gfrag16, int M, int D, cons
       }
     }
     __syncthreads();
-    for (int m = tid; m < M; m += 256) chunkhist[c * M + m] = hist[m];
+    for (int m = tid; m < M; m += 256) {
+      const int h = hist[m];
+      chunkhist[c * M + m] = h;
+      if (h) atomicAdd(&superhist[(c >> super_shift) * M + m], h);   // (integers: the sum does not depend on the order of arrival)
+    }
     __syncthreads();
   }
 }
@@ -1419,41 +1433,32 @@ gmmmap_group_scan_kernel(int *__restrict__ chunkhist, int64_t nchunks, int M, in
 
 // perm: frames in group order, and inside a group in FRAME order (a stable counting sort: the permutation, hence every tile
 // of the convert kernel and every sum it forms, is a function of the data alone -- repeat runs are bit-identical).  One
-// workgroup per chunk; position = sum of the smaller groups' totals + the group's frames in earlier chunks (chunkhist after
-// the scan) + those in earlier 64-frame rows of this chunk + those on lower lanes of the row.
-__global__ void __launch_bounds__(256)
-gmmmap_group_scatter_kernel(const int *__restrict__ key, int64_t T, int M, const int *__restrict__ chunkhist,
-                            const int *__restrict__ total, int *__restrict__ perm, const int64_t *__restrict__ gate) {
-  if (gate && *gate == 0) return;
-  extern __shared__ int lsm[];             // [M] group bases, then [16][M] row counts -> row bases
-  int *base = lsm, *rowcnt = lsm + M;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int64_t c = blockIdx.x, f0 = c * kGroupChunk;
-  // group bases: exclusive prefix of the totals (wave 0: a lane sums its stretch, the lanes' sums are scanned by shuffles) + the
-  // group's frames in earlier chunks.  (One thread walking total[] and chunkhist[] through global memory took 10 us per
-  // workgroup at 128 groups: most of this kernel's time.)
-  for (int m = tid; m < M; m += 256) base[m] = total[m];
-  for (int e = tid; e < 16 * M; e += 256) rowcnt[e] = 0;
-  __syncthreads();
-  if (wave == 0) {
-    const int per = (M + 63) / 64, lo = lane * per, hi = (lo + per < M) ? lo + per : M;
-    int s = 0;
-    for (int m = lo; m < hi; ++m) s += base[m];
-    int incl = s;
+// workgroup per chunk; position = sum of the smaller groups' totals + the group's frames in earlier chunks + those in earlier
+// 64-frame rows of this chunk + those on lower lanes of the row.  The two kernels below differ in where the first two terms
+// come from; the rest is scatter_chunk().
+// base[m] (LDS): the groups' totals -> their exclusive prefix (wave 0: a lane sums its stretch, the lanes' sums are scanned by
+// shuffles; one thread walking the totals took 10 us per workgroup at 128 groups).  Barriers around it are the caller's.
+__device__ __forceinline__ void group_bases_from_totals(int *base, int M, int lane) {
+  const int per = (M + 63) / 64, lo = lane * per, hi = (lo + per < M) ? lo + per : M;
+  int s = 0;
+  for (int m = lo; m < hi; ++m) s += base[m];
+  int incl = s;
 #pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const int v = __shfl_up(incl, o);
-      if (lane >= o) incl += v;
-    }
-    int run = incl - s;
-    for (int m = lo; m < hi; ++m) {
-      const int v = base[m];
-      base[m] = run;
-      run += v;
-    }
+  for (int o = 1; o < 64; o <<= 1) {
+    const int v = __shfl_up(incl, o);
+    if (lane >= o) incl += v;
   }
-  __syncthreads();
-  for (int m = tid; m < M; m += 256) base[m] += chunkhist[c * M + m];
+  int run = incl - s;
+  for (int m = lo; m < hi; ++m) {
+    const int v = base[m];
+    base[m] = run;
+    run += v;
+  }
+}
+// base[m] (LDS, visible): first position of group m's frames of this chunk; rowcnt: [16][M] zeros (visible)
+__device__ __forceinline__ void scatter_chunk(const int *__restrict__ key, int64_t T, int M, int64_t f0, const int *base, int *rowcnt,
+                                              int *__restrict__ perm) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   int k[4], rank[4];
   const int nbits = 32 - __builtin_clz((unsigned)(M > 1 ? M - 1 : 1));
 #pragma unroll
@@ -1486,8 +1491,86 @@ gmmmap_group_scatter_kernel(const int *__restrict__ key, int64_t T, int M, const
   for (int i = 0; i < 4; ++i) {
     const int r = wave + 4 * i;
     const int64_t fr = f0 + 64 * r + lane;
-    if (k[i] >= 0) perm[base[k[i]] + rowcnt[r * M + k[i]] + rank[i]] = (int)fr;
+    if (k[i] >= 0) {
+      const int64_t pos = (int64_t)base[k[i]] + rowcnt[r * M + k[i]] + rank[i];
+      if (pos < T) perm[pos] = (int)fr;                            // (always, with consistent histograms: never a store past perm)
+    }
   }
+}
+
+// After gmmmap_group_scan_kernel: chunkhist holds the prefix over the chunks, total[] the groups' sizes (the E-step's hard path).
+__global__ void __launch_bounds__(256)
+gmmmap_group_scatter_kernel(const int *__restrict__ key, int64_t T, int M, const int *__restrict__ chunkhist,
+                            const int *__restrict__ total, int *__restrict__ perm, const int64_t *__restrict__ gate) {
+  if (gate && *gate == 0) return;
+  extern __shared__ int lsm[];             // [M] group bases, then [16][M] row counts -> row bases
+  int *base = lsm, *rowcnt = lsm + M;
+  const int tid = threadIdx.x;
+  const int64_t c = blockIdx.x;
+  for (int m = tid; m < M; m += 256) base[m] = total[m];
+  for (int e = tid; e < 16 * M; e += 256) rowcnt[e] = 0;
+  __syncthreads();
+  if (tid < 64) group_bases_from_totals(base, M, tid);
+  __syncthreads();
+  for (int m = tid; m < M; m += 256) base[m] += chunkhist[c * M + m];
+  __syncthreads();
+  scatter_chunk(key, T, M, c * kGroupChunk, base, rowcnt, perm);
+}
+
+// The same scatter WITHOUT a scan launch in front of it (fvconvert, predict): the key kernel has also summed its chunk
+// histograms into one row per SUPER-CHUNK of 2^super_shift chunks (superhist[s][m], nsuper rows), and workgroup c forms what it
+// needs from those by itself: the groups' totals = the sum of all super-chunk rows, the group's frames in earlier chunks = the
+// super-chunk rows before its own + the chunk rows of its own super-chunk before c.  Both are reads of rows that the key
+// kernel -- an earlier launch -- has finished: no workgroup waits for another one.  2^super_shift ~ sqrt(nchunks) (32 at 10^6
+// frames: at most 31 + 31 coalesced rows of M ints per workgroup).
+// Workgroup 0 also leaves gbase[0 .. M] (the exclusive prefix of the totals, gbase[M] = T): sorted position p belongs to group
+// m exactly when gbase[m] <= p < gbase[m + 1], which is all the screen kernels want to know (gmmmap_screen.hpp).
+// clear[0 .. nclear): the OTHER super-chunk table, zeroed here for the next call (launch_grouping explains why that is safe).
+__global__ void __launch_bounds__(256)
+gmmmap_group_place_kernel(const int *__restrict__ key, int64_t T, int M, const int *__restrict__ chunkhist,
+                          const int *__restrict__ superhist, int nsuper, int super_shift, int *__restrict__ clear, int64_t nclear,
+                          int *__restrict__ gbase, int *__restrict__ perm) {
+  extern __shared__ int lsm[];             // [M] totals -> group bases, [16][M] row counts -> row bases, [M] frames in earlier chunks
+  int *base = lsm, *rowcnt = lsm + M, *before = lsm + 17 * M;
+  const int tid = threadIdx.x;
+  const int64_t c = blockIdx.x;
+  for (int64_t e = c * 256 + tid; e < nclear; e += (int64_t)gridDim.x * 256) clear[e] = 0;
+  for (int m = tid; m < M; m += 256) {
+    base[m] = 0;
+    before[m] = 0;
+  }
+  for (int e = tid; e < 16 * M; e += 256) rowcnt[e] = 0;
+  __syncthreads();
+  {
+    // up to 256 groups: thread <-> (row slot, group), `slots` rows in flight; more: thread <-> group, row after row
+    const int slots = M <= 256 ? 256 / M : 1, slot = M <= 256 ? tid / M : 0;
+    const int own = (int)(c >> super_shift);
+    const int64_t c_lo = (int64_t)own << super_shift;
+    if (slot < slots) {
+      for (int m = M <= 256 ? tid % M : tid; m < M; m += 256) {
+        int tot = 0, bef = 0;
+#pragma unroll 4
+        for (int s = slot; s < nsuper; s += slots) {
+          const int v = superhist[(int64_t)s * M + m];
+          tot += v;
+          bef += s < own ? v : 0;
+        }
+#pragma unroll 4
+        for (int64_t cc = c_lo + slot; cc < c; cc += slots) bef += chunkhist[cc * M + m];
+        atomicAdd(&base[m], tot);                                  // (integers: any order gives the same sums)
+        atomicAdd(&before[m], bef);
+      }
+    }
+  }
+  __syncthreads();
+  if (tid < 64) group_bases_from_totals(base, M, tid);
+  __syncthreads();
+  if (c == 0)
+    for (int m = tid; m <= M; m += 256) gbase[m] = m < M ? base[m] : (int)T;
+  __syncthreads();
+  for (int m = tid; m < M; m += 256) base[m] += before[m];
+  __syncthreads();
+  scatter_chunk(key, T, M, c * kGroupChunk, base, rowcnt, perm);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1594,7 +1677,7 @@ static bool use_mfma(const vcmi_gmmmap *g) {
 
 template <int DP, int FT, bool B16 = false>
 static int launch_screen(const vcmi_gmmmap *g, const double *dX, int64_t ldx, int64_t T, double *dY, int64_t ldy, hipStream_t st,
-                         const int *perm, const int *gkey) {
+                         const int *perm, const int *gbase) {
   constexpr int WAVES = 4;
   using TL = Tiling<DP, false>;
   constexpr int STG = B16 ? screen16_stage_doubles(DP) : screen_stage_doubles(DP);
@@ -1610,18 +1693,18 @@ static int launch_screen(const vcmi_gmmmap *g, const double *dX, int64_t ldx, in
   }
   const int64_t per_wg = (int64_t)16 * FT * WAVES;
   hipLaunchKernelGGL(kern, dim3((unsigned)((T + per_wg - 1) / per_wg)), dim3(WAVES * 64), shmem, st, g->packed.p, B16 ? g->packedQ16.p : g->packedQ.p, g->screen_rpm,
-                     g->M, g->D, dX, ldx, T, dY, ldy, g->prune, g->prune_count.p, perm, gkey);
+                     g->M, g->D, dX, ldx, T, dY, ldy, g->prune, g->prune_count.p, perm, gbase);
   VCMI_HIP(hipGetLastError());
   return VCMI_OK;
 }
 static int dispatch_screen(const vcmi_gmmmap *g, const double *dX, int64_t ldx, int64_t T, double *dY, int64_t ldy, hipStream_t st,
-                           const int *perm, const int *gkey) {
+                           const int *perm, const int *gbase) {
   const bool narrow = T <= kSmallCallFrames && !debug_flag(kDbgConvertWideTiles);     // one frame tile per wave, as dispatch_mfma
   // the screen on the BF16 matrix pipe (certified bound from split operands) where it exists: four rows per mixture, DP <= 40
   if (g->packedQ16.p && g->screen_rpm == 4 && screen16_has(g->DP) && !debug_flag(kDbgScreenFp64)) {
     switch (g->DP) {
 #define VCMI_CASE(DPV) \
-  case DPV: return narrow ? launch_screen<DPV, 1, true>(g, dX, ldx, T, dY, ldy, st, perm, gkey) : launch_screen<DPV, 2, true>(g, dX, ldx, T, dY, ldy, st, perm, gkey);
+  case DPV: return narrow ? launch_screen<DPV, 1, true>(g, dX, ldx, T, dY, ldy, st, perm, gbase) : launch_screen<DPV, 2, true>(g, dX, ldx, T, dY, ldy, st, perm, gbase);
       VCMI_CASE(16) VCMI_CASE(20) VCMI_CASE(24) VCMI_CASE(28) VCMI_CASE(32) VCMI_CASE(36) VCMI_CASE(40)
 #undef VCMI_CASE
       default: break;
@@ -1629,7 +1712,7 @@ static int dispatch_screen(const vcmi_gmmmap *g, const double *dX, int64_t ldx, 
   }
   switch (g->DP) {
 #define VCMI_CASE(DPV) \
-  case DPV: return narrow ? launch_screen<DPV, 1>(g, dX, ldx, T, dY, ldy, st, perm, gkey) : launch_screen<DPV, 2>(g, dX, ldx, T, dY, ldy, st, perm, gkey);
+  case DPV: return narrow ? launch_screen<DPV, 1>(g, dX, ldx, T, dY, ldy, st, perm, gbase) : launch_screen<DPV, 2>(g, dX, ldx, T, dY, ldy, st, perm, gbase);
     VCMI_CASE(16) VCMI_CASE(20) VCMI_CASE(24) VCMI_CASE(28) VCMI_CASE(32) VCMI_CASE(36) VCMI_CASE(40) VCMI_CASE(44) VCMI_CASE(48)
 #undef VCMI_CASE
     default: return fail(VCMI_ERR_ARG, "no screening kernel for padded dimension %d", g->DP);
@@ -1639,7 +1722,7 @@ static int dispatch_screen(const vcmi_gmmmap *g, const double *dX, int64_t ldx, 
 // predict on grouped frames with the four-row screen (gmmmap_screen_argmax_kernel): every padded dimension of the tile kernel
 template <int DP>
 static int launch_screen_argmax(const vcmi_gmmmap *g, const double *dX, int64_t ldx, int64_t T, int64_t *didx, hipStream_t st,
-                                const int *perm, const int *gkey) {
+                                const int *perm, const int *gbase) {
   constexpr int WAVES = 4;
   using TL = Tiling<DP, true>;
   constexpr int BUF = (TL::BLK > screen_stage_doubles(DP)) ? TL::BLK : screen_stage_doubles(DP);
@@ -1654,15 +1737,15 @@ static int launch_screen_argmax(const vcmi_gmmmap *g, const double *dX, int64_t 
   }
   const int64_t per_wg = (int64_t)32 * WAVES;
   hipLaunchKernelGGL(kern, dim3((unsigned)((T + per_wg - 1) / per_wg)), dim3(WAVES * 64), shmem, st, g->packedU.p, g->packedQA.p, g->M, g->D,
-                     dX, ldx, T, didx, perm, gkey);
+                     dX, ldx, T, didx, perm, gbase);
   VCMI_HIP(hipGetLastError());
   return VCMI_OK;
 }
 static int dispatch_screen_argmax(const vcmi_gmmmap *g, const double *dX, int64_t ldx, int64_t T, int64_t *didx, hipStream_t st,
-                                  const int *perm, const int *gkey) {
+                                  const int *perm, const int *gbase) {
   switch (g->DP) {
 #define VCMI_CASE(DPV) \
-  case DPV: return launch_screen_argmax<DPV>(g, dX, ldx, T, didx, st, perm, gkey);
+  case DPV: return launch_screen_argmax<DPV>(g, dX, ldx, T, didx, st, perm, gbase);
     VCMI_CASE(16) VCMI_CASE(20) VCMI_CASE(24) VCMI_CASE(28) VCMI_CASE(32) VCMI_CASE(36) VCMI_CASE(40) VCMI_CASE(44)
     VCMI_CASE(48) VCMI_CASE(52) VCMI_CASE(56) VCMI_CASE(60) VCMI_CASE(64) VCMI_CASE(68) VCMI_CASE(72) VCMI_CASE(76)
     VCMI_CASE(80)
@@ -1689,8 +1772,9 @@ static int convert_shape(const vcmi_gmmmap *g) {
   return g->model.undecided > kBroadModelFrac ? 1 : 2;
 }
 
-// The three grouping kernels (keys + chunk histograms, prefix, stable scatter) on g's scratch: *key = group of every frame,
-// *perm = frames in group order.  The caller brackets its use of them with g->grp_order.enter / leave.
+// The two grouping kernels (keys + chunk and super-chunk histograms, stable scatter) on g's scratch: *perm = frames in group
+// order, *gbase = first sorted position of every group (M + 1 ints), *key = group of every frame.  The caller brackets its use
+// of them with g->grp_order.enter / leave.
 static size_t group_key_shmem(const vcmi_gmmmap *g, bool fp64) {
   return (fp64 ? group_key_doubles(g->DP, g->M) : group_key16_doubles(g->M)) * sizeof(double) + (size_t)g->M * sizeof(int);
 }
@@ -1698,21 +1782,58 @@ static bool group_key_fp64(const vcmi_gmmmap *g) { return debug_flag(kDbgGroupKe
 static bool can_group(const vcmi_gmmmap *g, int64_t T) {
   return T >= kSortMinFrames && T < ((int64_t)1 << 31) && g->M >= 4 && g->gfrag.p && group_key_shmem(g, group_key_fp64(g)) <= 64 * 1024;
 }
-static int launch_grouping(vcmi_gmmmap *g, const double *dX, int64_t ldx, int64_t T, hipStream_t st, int **key_out, int **perm_out) {
+// chunks per super-chunk, as a shift: the power of two from 32 on that reaches sqrt(nchunks) -- a scatter workgroup reads
+// nsuper + 2^shift rows at most, so the two terms are kept alike
+static int group_super_shift(int64_t nchunks) {
+  int sh = 5;
+  while (((int64_t)1 << (2 * sh)) < nchunks) ++sh;
+  return sh;
+}
+static int launch_grouping(vcmi_gmmmap *g, const double *dX, int64_t ldx, int64_t T, hipStream_t st, int **key_out, int **perm_out,
+                           int **gbase_out) {
   const bool fp64 = group_key_fp64(g);
   const size_t gshmem = group_key_shmem(g, fp64);
   const int64_t nchunks = (T + kGroupChunk - 1) / kGroupChunk;
-  VCMI_TRY(g->grp.reserve((size_t)2 * T + (size_t)(nchunks + 1) * g->M));
+  const int sshift = group_super_shift(nchunks);
+  const int64_t nsuper = (nchunks + ((int64_t)1 << sshift) - 1) >> sshift;
+  const size_t sneed = (size_t)nsuper * g->M;
+  VCMI_TRY(g->grp.reserve((size_t)2 * T + (size_t)nchunks * g->M + (size_t)g->M + 1));
+  if (sneed > g->grp_super_stride) {
+    g->grp_super_ok = false;
+    g->grp_super_stride = 0;
+    VCMI_TRY(g->grp_super.alloc(2 * sneed));
+    g->grp_super_stride = sneed;
+  }
   VCMI_TRY(g->grp_order.enter(st));
-  int *key = g->grp.p, *perm = key + T, *chunkhist = perm + T, *total = chunkhist + nchunks * g->M;
-  int cus = 256;
-  (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, g->device);
-  const unsigned kgrid = (unsigned)std::min<int64_t>(nchunks, (int64_t)cus * 4);
+  // The super-chunk table that the key kernel adds into must be all zero when it starts, without a memset in every call: there
+  // are two, call n uses table n & 1 and its scatter kernel zeroes what call n - 1 left in the other one, for call n + 1.  That
+  // is safe because everything that touches the tables is ordered: within a call the key kernel, the scatter kernel and the
+  // next call's key kernel follow each other on the stream (or, on another stream, behind grp_order's event, which the
+  // caller records after its last kernel) -- the table being cleared was last read by the scatter kernel of call n - 1, which
+  // has finished, and is next written by the key kernel of call n + 1, which has not begun.  Only a buffer that is new, or a
+  // call that returned between its launches, leaves them in an unknown state: both are then zeroed here, once.
+  // A call that is being CAPTURED into a graph runs again and again with the table of this one visit: it zeroes both tables
+  // itself, inside the graph, and leaves the state unknown for the next call outside it.
+  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+  if (hipStreamIsCapturing(st, &cap) != hipSuccess) {
+    (void)hipGetLastError();
+    cap = hipStreamCaptureStatusNone;
+  }
+  const bool captured = cap != hipStreamCaptureStatusNone;
+  if (!g->grp_super_ok || captured) {
+    VCMI_HIP(hipMemsetAsync(g->grp_super.p, 0, 2 * g->grp_super_stride * sizeof(int), st));
+    g->grp_super_used[0] = g->grp_super_used[1] = 0;
+  }
+  g->grp_super_ok = false;
+  const unsigned cur = g->grp_calls & 1u, oth = cur ^ 1u;
+  int *key = g->grp.p, *perm = key + T, *chunkhist = perm + T, *gbase = chunkhist + nchunks * g->M;
+  int *superhist = g->grp_super.p + cur * g->grp_super_stride, *superclear = g->grp_super.p + oth * g->grp_super_stride;
+  const unsigned kgrid = (unsigned)std::min<int64_t>(nchunks, (int64_t)g->cus * 4);
   switch (g->DP) {
 #define VCMI_CASE(DPV) \
   case DPV: \
-    if (fp64) hipLaunchKernelGGL(gmmmap_group_key_kernel<DPV>, dim3(kgrid), dim3(256), gshmem, st, g->gfrag.p, g->M, g->D, dX, ldx, T, key, chunkhist); \
-    else hipLaunchKernelGGL(gmmmap_group_key16_kernel<DPV>, dim3(kgrid), dim3(256), gshmem, st, g->gfrag16.p, g->M, g->D, dX, ldx, T, key, chunkhist); \
+    if (fp64) hipLaunchKernelGGL(gmmmap_group_key_kernel<DPV>, dim3(kgrid), dim3(256), gshmem, st, g->gfrag.p, g->M, g->D, dX, ldx, T, key, chunkhist, superhist, sshift); \
+    else hipLaunchKernelGGL(gmmmap_group_key16_kernel<DPV>, dim3(kgrid), dim3(256), gshmem, st, g->gfrag16.p, g->M, g->D, dX, ldx, T, key, chunkhist, superhist, sshift); \
     break;
     VCMI_CASE(16) VCMI_CASE(20) VCMI_CASE(24) VCMI_CASE(28) VCMI_CASE(32) VCMI_CASE(36) VCMI_CASE(40) VCMI_CASE(44)
     VCMI_CASE(48) VCMI_CASE(52) VCMI_CASE(56) VCMI_CASE(60) VCMI_CASE(64) VCMI_CASE(68) VCMI_CASE(72) VCMI_CASE(76)
@@ -1720,12 +1841,19 @@ static int launch_grouping(vcmi_gmmmap *g, const double *dX, int64_t ldx, int64_
 #undef VCMI_CASE
     default: return fail(VCMI_ERR_ARG, "no MFMA instantiation for padded dimension %d", g->DP);
   }
-  hipLaunchKernelGGL(gmmmap_group_scan_kernel, dim3((unsigned)g->M), dim3(256), 0, st, chunkhist, nchunks, g->M, total, (const int64_t *)nullptr);
-  hipLaunchKernelGGL(gmmmap_group_scatter_kernel, dim3((unsigned)nchunks), dim3(256), (size_t)17 * g->M * sizeof(int), st,
-                     key, T, g->M, chunkhist, total, perm, (const int64_t *)nullptr);
   VCMI_HIP(hipGetLastError());
+  hipLaunchKernelGGL(gmmmap_group_place_kernel, dim3((unsigned)nchunks), dim3(256), (size_t)18 * g->M * sizeof(int), st,
+                     key, T, g->M, chunkhist, superhist, (int)nsuper, sshift, superclear, (int64_t)g->grp_super_used[oth], gbase, perm);
+  VCMI_HIP(hipGetLastError());
+  if (!captured) {
+    g->grp_super_used[cur] = sneed;
+    g->grp_super_used[oth] = 0;
+    ++g->grp_calls;
+    g->grp_super_ok = true;
+  }
   *key_out = key;
   *perm_out = perm;
+  *gbase_out = gbase;
   return VCMI_OK;
 }
 
@@ -1736,13 +1864,13 @@ int gmmmap_convert_device(vcmi_gmmmap *g, const double *dX, int64_t ldx, int64_t
   if (g->kernel_choice == 2 && !gmmmap_has_mfma(g->DP))
     return fail(VCMI_ERR_ARG, "MFMA kernel forced but dimension %d has no instantiation", g->D);
   if (use_mfma(g)) {
-    // frames grouped by their nearest source mean first (see gmmmap_group_key_kernel): worth its three small kernels from a
+    // frames grouped by their nearest source mean first (see gmmmap_group_key_kernel): worth its two small kernels from a
     // few thousand frames on; the prune = +inf (dense) setting has nothing to gain from it
     if (can_group(g, T) && g->prune < 1e300 && !debug_flag(kDbgConvertNoGrouping)) {
-      int *key = nullptr, *perm = nullptr;
-      VCMI_TRY(launch_grouping(g, dX, ldx, T, st, &key, &perm));
+      int *key = nullptr, *perm = nullptr, *gbase = nullptr;
+      VCMI_TRY(launch_grouping(g, dX, ldx, T, st, &key, &perm, &gbase));
       const int shape = convert_shape(g);
-      const int rc = shape == 3 ? dispatch_screen(g, dX, ldx, T, dY, ldy, st, perm, key)
+      const int rc = shape == 3 ? dispatch_screen(g, dX, ldx, T, dY, ldy, st, perm, gbase)
                    : shape == 1 ? dispatch_mfma<0, 1>(g, dX, ldx, T, dY, ldy, st, perm, key)
                                 : dispatch_mfma<0, 2>(g, dX, ldx, T, dY, ldy, st, perm, key);
       (void)g->grp_order.leave(st);
@@ -1814,9 +1942,9 @@ int gmmmap_predict_device(vcmi_gmmmap *g, const double *dX, int64_t ldx, int64_t
     const bool screen_pays = (g->model.argmax_survivors <= kScreenArgmaxFrac || debug_flag(kDbgPredictScreen)) && allow_screen;
     if (screen_pays && g->packedQA.p && g->packedU.p && g->M <= 1024 && can_group(g, T) && !debug_flag(kDbgPredictNoScreen) &&
         !debug_flag(kDbgPredictNoEarlyExit)) {
-      int *key = nullptr, *perm = nullptr;
-      VCMI_TRY(launch_grouping(g, dX, ldx, T, st, &key, &perm));
-      const int rc = dispatch_screen_argmax(g, dX, ldx, T, didx, st, perm, key);
+      int *key = nullptr, *perm = nullptr, *gbase = nullptr;
+      VCMI_TRY(launch_grouping(g, dX, ldx, T, st, &key, &perm, &gbase));
+      const int rc = dispatch_screen_argmax(g, dX, ldx, T, didx, st, perm, gbase);
       (void)g->grp_order.leave(st);
       return rc;
     }
@@ -2087,7 +2215,9 @@ int gmmmap_member(vcmi_gmmmap *g, int member, vcmi_gmmmap **out) {
     if (g->in_w.empty()) return fail(VCMI_ERR_ARG, "this converter cannot be replicated on another device");
     vcmi_gmmmap *n = new (std::nothrow) vcmi_gmmmap();
     if (!n) return fail(VCMI_ERR_OOM, "out of host memory");
-    (void)hipGetDevice(&n->device);
+    int ndev = 0;
+    (void)hipGetDevice(&ndev);
+    n->bind_device(ndev);
     const int rc = gmmmap_prepare(n, g->in_w.data(), g->in_mu.data(), g->in_sigma.data(), g->in_Dj, g->M, g->in_swap);
     if (rc != VCMI_OK) {
       delete n;
@@ -2137,7 +2267,9 @@ extern "C" int vcmi_gmmmap_create(const double *weights, const double *mu, const
   VCMI_TRY(check_device());
   vcmi_gmmmap *g = new (std::nothrow) vcmi_gmmmap();
   if (!g) return fail(VCMI_ERR_OOM, "out of host memory");
-  (void)hipGetDevice(&g->device);
+  int dev = 0;
+  (void)hipGetDevice(&dev);
+  g->bind_device(dev);
   int rc = gmmmap_prepare(g, weights, mu, sigma, Dj, M, swap);
   if (rc != VCMI_OK) {
     delete g;

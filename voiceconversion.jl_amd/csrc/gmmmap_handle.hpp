@@ -56,8 +56,24 @@ struct vcmi_gmmmap {
   // and the call's scratch: key (T), perm (T), counts (M), cursors (M)
   vcmi::DevBuf<double> gfrag;
   vcmi::DevBuf<double> gfrag16;   // the same operand split into bf16 hi + lo for gmmmap_group_key16_kernel
+  // grp: key (T), perm (T), the chunk histograms (nchunks, M) and gbase (M + 1): the first sorted position of every group, gbase[M] = T
   vcmi::DevBuf<int> grp;
   vcmi::StreamOrder grp_order;
+  // the grouping's super-chunk histograms: TWO tables of grp_super_stride ints, each all zero between the calls that use it
+  // (launch_grouping, gmmmap.hip: call n adds into table n & 1 and clears the other one).  grp_super_used[i]: ints of table i
+  // that the last call on it left non-zero; grp_super_ok: false until the tables are known to be in that state (new or grown
+  // buffer, a call whose launches did not all go out) -- the next call then zeroes both before it starts.
+  vcmi::DevBuf<int> grp_super;
+  size_t grp_super_stride = 0;
+  size_t grp_super_used[2] = {0, 0};
+  unsigned grp_calls = 0;
+  bool grp_super_ok = false;
+  int cus = 256;   // compute units of `device` (bind_device)
+  void bind_device(int dev) {
+    device = dev;
+    int n = 0;
+    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0) cus = n;
+  }
 
   // issue-order table of the U-only tiling (slot -> tile << 16 | k-step) for the on-device packer (gmm_px_prepare_device)
   vcmi::DevBuf<int> px_table;

@@ -468,7 +468,7 @@ int gmm_px_handle_here(vcmi_gmmmap **inout) {
   }
   if (!*inout) *inout = new (std::nothrow) vcmi_gmmmap();
   if (!*inout) return fail(VCMI_ERR_OOM, "out of host memory");
-  (*inout)->device = dev;
+  (*inout)->bind_device(dev);
   return VCMI_OK;
 }
 

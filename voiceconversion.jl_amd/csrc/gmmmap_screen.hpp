@@ -10,7 +10,7 @@
 // {g, 4 + g, 8 + g, 12 + g}, so a tile whose row 4 r + j is screening row r of mixture j gives lane group j
 // the four rows of mixture j -- its bound is four multiply-adds in the lane, no cross-lane sum, and ONE tile of KS
 // MFMAs screens FOUR mixtures (2.5 MFMAs per pair instead of 10).  Per workgroup (WAVES waves x FT tiles of 16 frames):
-//   1. the mixtures of the workgroup's groups (gkey of its frames: one, or two or three where the workgroup straddles group
+//   1. the mixtures of the workgroup's groups (from gbase: one, or two or three where the workgroup straddles group
 //      boundaries) are evaluated in full -- whitening, regression, softmax -- which makes the running maximum tight for
 //      (almost) all of its frames;
 //   2. every quad of mixtures is screened against (running maximum - prune); a mixture that no frame of the workgroup lets
@@ -28,11 +28,30 @@
 
 namespace vcmi {
 
+// The groups among the sorted positions [p0, p1), from gbase[0 .. M] (first position of every group, gbase[M] = T; written by
+// gmmmap_group_place_kernel): group m is there exactly when its own range [gbase[m], gbase[m + 1]) is not empty and meets
+// the other one, gbase[m] < p1 && gbase[m + 1] > p0 (the second test alone would also take every EMPTY group whose position
+// lies strictly inside (p0, p1)).  One lane per group, 64 groups per turn: the ballot IS the pair of bitmap words, handed
+// to emit(word index, low, high), and its first bit the group of position p0, which is returned (0 for an empty range).
+// Wave-uniform; every wave may call it (the same two cache lines per turn), so nobody waits for the answer.
+template <class Emit>
+__device__ __forceinline__ int groups_in_range(const int *__restrict__ gbase, int M, int p0, int p1, int lane, Emit &&emit) {
+  int first = -1;
+  for (int b = 0; b < M; b += 64) {
+    const int m = b + lane;
+    const int lo = gbase[m < M ? m : M], hi = gbase[m + 1 < M ? m + 1 : M];
+    const unsigned long long bal = __builtin_amdgcn_ballot_w64(m < M && hi > lo && lo < p1 && hi > p0);
+    emit(b >> 5, (unsigned)bal, (unsigned)(bal >> 32));
+    if (first < 0 && bal != 0ull) first = b + __builtin_ctzll(bal);
+  }
+  return __builtin_amdgcn_readfirstlane(first < 0 ? 0 : first);
+}
+
 template <int DP, int FT, int WAVES, bool B16 = false>
 __global__ void __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(DP <= 40 ? (FT == 2 ? 3 : 4) : 2)))
 gmmmap_screen_kernel(const double *__restrict__ packed, const double *__restrict__ packedQ, int rpm, int M, int D,
                      const double *__restrict__ X, int64_t ldx, int64_t T, double *__restrict__ Y, int64_t ldy, double prune,
-                     unsigned long long *__restrict__ nreg, const int *__restrict__ perm, const int *__restrict__ gkey) {
+                     unsigned long long *__restrict__ nreg, const int *__restrict__ perm, const int *__restrict__ gbase) {
   using TL = Tiling<DP, false>;
   constexpr int KS = TL::KS, NT = TL::NT, NU = TL::NU, BLK = TL::BLK;
   constexpr int QS = screen_quads(DP), QFR = screen_frag_doubles(DP), STG = B16 ? screen16_stage_doubles(DP) : screen_stage_doubles(DP);
@@ -52,21 +71,21 @@ gmmmap_screen_kernel(const double *__restrict__ packed, const double *__restrict
   const int64_t frame0 = ((int64_t)blockIdx.x * WAVES + wave) * (16 * FT);
   const unsigned lds0 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char *)(reinterpret_cast<char *>(smem));
 
-  if (tid < 64) etab[tid] = kExp2Tab[tid];
+  // the groups of the workgroup's positions -> `keys` (every word that is read later is written here: nothing to zero), and the
+  // group of its first one: the mixture evaluated first.  The loads of gbase are the kernel's first, so the DMA of that block
+  // goes out after ONE short latency (it used to be the chain perm[f0] -> gkey[...] -> DMA, and a gather of gkey per frame)
+  // (the table of vc_exp_tab is requested in front of them, so that it arrives in the same wait)
+  const double etv = (tid < 64) ? kExp2Tab[tid] : 0.0;
+  const int64_t f0 = (int64_t)blockIdx.x * WAVES * (16 * FT);
+  const int64_t f1 = (f0 + WAVES * (16 * FT) < T) ? f0 + WAVES * (16 * FT) : T;
+  const int mg = groups_in_range(gbase, M, (int)f0, (int)f1, lane, [&](int w, unsigned lo, unsigned hi) {
+    if (tid == 0) {
+      keys[w] = lo;
+      keys[w + 1] = hi;
+    }
+  });
+  if (tid < 64) etab[tid] = etv;
   if (tid < 32) survivors[tid] = 0u;
-  else if (tid < 64) keys[tid - 32] = 0u;
-
-  // group of the workgroup's first frame: the mixture evaluated first
-  int mg = 0;
-  {
-    // (uniform addresses through the constant address space: two dependent SCALAR loads -- the chain perm -> gkey -> DMA of the
-    // block does not queue behind, or hold up, the vector loads of the frames below; perm / gkey were written by earlier kernels)
-    const int64_t f0 = (int64_t)blockIdx.x * WAVES * (16 * FT);
-    const __attribute__((address_space(4))) int *perm_c = (const __attribute__((address_space(4))) int *)perm;
-    const __attribute__((address_space(4))) int *gkey_c = (const __attribute__((address_space(4))) int *)gkey;
-    mg = (f0 < T) ? gkey_c[perm_c[f0]] : 0;
-    mg = (mg >= 0 && mg < M) ? mg : 0;
-  }
   // block mg -> buffer 0, stage 0 -> buffer 1 (each wave issues every WAVES-th KB)
   auto dma_block = [&](int m, int buf) {
     const char *gb = reinterpret_cast<const char *>(packed + (size_t)m * BLK);
@@ -110,17 +129,8 @@ gmmmap_screen_kernel(const double *__restrict__ packed, const double *__restrict
     }
   };
   load_x();
-  __syncthreads();                                               // the bitmaps are zeroed
-  if (lgrp == 0) {
-#pragma unroll
-    for (int f = 0; f < FT; ++f) {
-      const int64_t fr = frame0 + 16 * f + lcol;
-      if (fr < T) {
-        const int k = gkey[frow[f]];
-        if (k >= 0 && k < M) atomicOr(&keys[k >> 5], 1u << (k & 31));
-      }
-    }
-  }
+  // (no barrier here: keys, survivors and etab are complete before the barrier in front of the first block, and nothing reads
+  // or updates them earlier)
   double yacc[FT][KS];
   double runmax[FT], den[FT];          // PAIRED: [0] holds tile 0's value in the even lane groups, tile 1's in the odd ones
 #pragma unroll
@@ -495,7 +505,7 @@ template <int DP, int WAVES>
 __global__ void __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(DP <= 40 ? 3 : 2)))
 gmmmap_screen_argmax_kernel(const double *__restrict__ packedU, const double *__restrict__ packedQ, int M, int D,
                             const double *__restrict__ X, int64_t ldx, int64_t T, int64_t *__restrict__ idx,
-                            const int *__restrict__ perm, const int *__restrict__ gkey) {
+                            const int *__restrict__ perm, const int *__restrict__ gbase) {
   using TL = Tiling<DP, true>;
   constexpr int FT = 2;
   constexpr int KS = TL::KS, NU = TL::NT, BLK = TL::BLK;
@@ -512,17 +522,16 @@ gmmmap_screen_argmax_kernel(const double *__restrict__ packedU, const double *__
   const int lcol = lane & 15, lgrp = lane >> 4;
   const int64_t frame0 = ((int64_t)blockIdx.x * WAVES + wave) * (16 * FT);
   const unsigned lds0 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char *)(reinterpret_cast<char *>(smem));
+  // (the groups of the workgroup's positions and the first one's, as in gmmmap_screen_kernel)
+  const int64_t f0 = (int64_t)blockIdx.x * WAVES * (16 * FT);
+  const int64_t f1 = (f0 + WAVES * (16 * FT) < T) ? f0 + WAVES * (16 * FT) : T;
+  const int mg = groups_in_range(gbase, M, (int)f0, (int)f1, lane, [&](int w, unsigned lo, unsigned hi) {
+    if (tid == 0) {
+      keys[w] = lo;
+      keys[w + 1] = hi;
+    }
+  });
   if (tid < 32) survivors[tid] = 0u;
-  else if (tid < 64) keys[tid - 32] = 0u;
-
-  int mg = 0;
-  {
-    const int64_t f0 = (int64_t)blockIdx.x * WAVES * (16 * FT);
-    const __attribute__((address_space(4))) int *perm_c = (const __attribute__((address_space(4))) int *)perm;
-    const __attribute__((address_space(4))) int *gkey_c = (const __attribute__((address_space(4))) int *)gkey;
-    mg = (f0 < T) ? gkey_c[perm_c[f0]] : 0;
-    mg = (mg >= 0 && mg < M) ? mg : 0;
-  }
   auto dma_block = [&](int m, int buf) {
     const char *gb = reinterpret_cast<const char *>(packedU + (size_t)m * BLK);
     const unsigned lb = lds0 + (unsigned)buf * (BUF * 8u);
@@ -554,17 +563,6 @@ gmmmap_screen_argmax_kernel(const double *__restrict__ packedU, const double *__
     frow[f] = (fr < T) ? (int64_t)perm[fr] : fr;
     if (frame0 + 16 * f < T) tiles_in_range |= 1u << f;
     load_frame_row<KS>(X + (fr < T ? frow[f] : (int64_t)0) * ldx, fr < T, rows_as_lines(X, ldx, D, DP), D, lgrp, xb[f]);
-  }
-  __syncthreads();                                               // the bitmaps are zeroed
-  if (lgrp == 0) {
-#pragma unroll
-    for (int f = 0; f < FT; ++f) {
-      const int64_t fr = frame0 + 16 * f + lcol;
-      if (fr < T) {
-        const int k = gkey[frow[f]];
-        if (k >= 0 && k < M) atomicOr(&keys[k >> 5], 1u << (k & 31));
-      }
-    }
   }
   // selected layout: the even lane groups carry tile 0's running maximum and index, the odd ones tile 1's
   double runmax = -INFINITY;

@@ -1,4 +1,6 @@
 // grouping.hpp -- the stable counting sort of frames by an integer key (defined in gmmmap.hip; also used by estep.hip).
+// These two are the scan + scatter pair that the E-step's hard path launches behind its gate; fvconvert and predict sort
+// with one launch fewer (gmmmap_group_place_kernel, gmmmap.hip: no scan, super-chunk histograms from the key kernel).
 #pragma once
 #include "vcmi_common.hpp"
 
