@@ -316,6 +316,27 @@ int vcmi_push_delta_dev(const double *dsrc, int64_t lds, int D, int64_t T, doubl
  * 2..D+1 BEFORE the download: out[2:end,:] = fvpostf(VarianceScaling(sigma2), vc(t, fm)[2:end,:]); sigma2 (D) host vector,
  * NULL = plain vcmi_vc_traj.  One upload, one download; everything in between stays in HBM. */
 int vcmi_vc_traj_postf(vcmi_traj *t, const double *fm, int64_t T, const double *sigma2, double *out);
+/* bin/vc.jl:75-82 in one call: fm (D+1,T) STATIC features, row 1 power.
+ * X = [fm[1,:]; push_delta(fm[2:end,:])] over the WHOLE matrix (bin/vc.jl:77-78), then vc(t, X) in chunks of length(t)
+ * (src/common.jl:31-63), then fvpostf! (src/gv.jl:10-15) on rows 2..D+1 when sigma2 != NULL.  out (D+1,T).
+ * The deltas are taken BEFORE chunking: frame kL+1 takes its delta from frame kL of the previous chunk, and only frames 1 and
+ * T of the utterance keep the copy of the static value in the delta rows (src/datasets.jl:6-13); they are bit-identical to
+ * vcmi_push_delta's.  Row 1 is passed through bit for bit.  Chunks are [kL+1, min((k+1)L, T)], L = length(t); afterwards
+ * length(t) is the last chunk's length, as vcmi_vc_traj leaves it.
+ * T = 0 is a no-op; sigma2 != NULL with T < 2: VCMI_ERR_DIM; length(t) < 1: VCMI_ERR_ARG.
+ * This entry and the three that follow run on the calling thread's device: the device group of vcmi_set_devices is not used.
+ * Device scratch of the four, per thread and grow-only: the converter input (2D,T) and the result (D,T); the host-pointer
+ * entries add one staging matrix for fm, in which static input is converted IN PLACE (out has the shape of fm: the power row
+ * never moves) -- (4D+1) T doubles for this entry, where vcmi_vc_traj_postf holds (6D+2) T; vcmi_vc_trajgv with
+ * is_static = 0 keeps its (D+1,T) result behind the (2D+1,T) input: (6D+2) T.  A host-pointer entry frees the three buffers
+ * on return when together they exceed 256 MiB (kVcTrajScratchKeepBytes, csrc/traj.hip).  The converter handle's own per-frame
+ * workspace is that of vcmi_traj_convert_batch_dev. */
+int vcmi_vc_traj_static(vcmi_traj *t, const double *fm, int64_t T, const double *sigma2, double *out);
+/* the same on DEVICE-RESIDENT matrices with leading dimensions (ldf >= the row count of dfm, ldo >= D+1; below:
+ * VCMI_ERR_ARG), asynchronous on `stream` up to the status read that vcmi_traj_convert_batch_dev already does; dout must not
+ * overlap dfm.  is_static = 0: dfm is (2D+1,T) (src/common.jl:31-63 as it stands); 1: dfm is (D+1,T) as above. */
+int vcmi_vc_traj_dev(vcmi_traj *t, const double *dfm, int64_t ldf, int64_t T, int is_static, const double *sigma2,
+                     double *dout, int64_t ldo, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
  * TrajectoryGVGMMMap -- src/trajectory_gmmmap.jl:114-189
@@ -332,6 +353,16 @@ int vcmi_trajgv_convert_batch(vcmi_trajgv *h, int64_t n, const double *const *X,
                               double *const *Y);
 int vcmi_trajgv_convert_batch_dev(vcmi_trajgv *h, int64_t n, const double *dX, const int64_t *x_off, const int64_t *T,
                                   int epochs, double alpha, double *dY, const int64_t *y_off, void *stream);
+/* vc(c::TrajectoryConverter, fm) for TrajectoryGVGMMMap (src/common.jl:31-63): each chunk through
+ * fvconvert(tgv, X; epochs, alpha) (src/trajectory_gmmmap.jl:139-168).  is_static = 0: fm is (2D+1,T); 1: fm is (D+1,T) STATIC
+ * features and the deltas are taken over the whole matrix first (bin/vc.jl:75-78), as vcmi_vc_traj_static does.  sigma2 may be
+ * NULL; otherwise fvpostf! (src/gv.jl:10-15) runs on rows 2..D+1 of the whole result.  A chunk of exactly one frame has no
+ * variance: VCMI_ERR_DIM, before anything runs.  Afterwards length(h's trajectory converter) is the last chunk's length
+ * (src/trajectory_gmmmap.jl:70-72,146).  Other rules, device and scratch: see vcmi_vc_traj_static / vcmi_vc_traj_dev. */
+int vcmi_vc_trajgv(vcmi_trajgv *h, const double *fm, int64_t T, int is_static, int epochs, double alpha,
+                   const double *sigma2, double *out);
+int vcmi_vc_trajgv_dev(vcmi_trajgv *h, const double *dfm, int64_t ldf, int64_t T, int is_static, int epochs,
+                       double alpha, const double *sigma2, double *dout, int64_t ldo, void *stream);
 
 /* fvpostf(vs::VarianceScaling, src) -- src/gv.jl:10-21.  src, out (D,T), sigma2 (D); out may alias src. */
 int vcmi_variance_scaling(const double *src, int D, int64_t T, const double *sigma2, double *out);

@@ -122,6 +122,10 @@ SIGNATURES = {
     "vcmi_push_delta": (_int, [_dp, _int, _i64, _dp]),
     "vcmi_push_delta_dev": (_int, [_vp, _i64, _int, _i64, _vp, _i64, _vp]),
     "vcmi_vc_traj_postf": (_int, [_vp, _dp, _i64, _dp, _dp]),
+    "vcmi_vc_traj_static": (_int, [_vp, _dp, _i64, _dp, _dp]),
+    "vcmi_vc_traj_dev": (_int, [_vp, _vp, _i64, _i64, _int, _dp, _vp, _i64, _vp]),
+    "vcmi_vc_trajgv": (_int, [_vp, _dp, _i64, _int, _int, C.c_double, _dp, _dp]),
+    "vcmi_vc_trajgv_dev": (_int, [_vp, _vp, _i64, _i64, _int, _int, C.c_double, _dp, _vp, _i64, _vp]),
     "vcmi_trajgv_create": (_int, [_vp, _dp, _dp, C.POINTER(_vp)]),
     "vcmi_trajgv_destroy": (_int, [_vp]),
     "vcmi_trajgv_convert": (_int, [_vp, _dp, _i64, _int, C.c_double, _dp]),

@@ -13,12 +13,20 @@ class TrajectoryConverter(AbstractConverter):     # src/common.jl:4
     pass
 
 
-def vc(c, fm, postfilter=None):
+def vc(c, fm, postfilter=None, delta=False):
     """vc(c, fm): row 1 of `fm` is the power coefficient and is passed through; the remaining rows are
     converted -- frame by frame for a FrameByFrameConverter (src/common.jl:7-26; here one kernel launch
     over all T frames), in chunks of length(c) frames for a TrajectoryConverter (src/common.jl:31-63).
     postfilter: a VarianceScaling applied to the converted rows 2..end before the result leaves the device
-    (out[2:end,:] = fvpostf(postfilter, vc(c, fm)[2:end,:]), src/gv.jl:10-15): one upload, one download."""
+    (out[2:end,:] = fvpostf(postfilter, vc(c, fm)[2:end,:]), src/gv.jl:10-15): one upload, one download.
+    delta=True (TrajectoryConverter only, as bin/vc.jl:76): `fm` holds the STATIC features (D+1,T) and the input
+    [fm[1,:]; push_delta(fm[2:end,:])] of bin/vc.jl:77-78 is built on the device -- the deltas over the whole
+    utterance, before it is cut into chunks.  A trajectory converter also takes a torch tensor on the device
+    and returns one."""
+    if delta:
+        if isinstance(c, FrameByFrameConverter):
+            raise ValueError("delta=True: only a TrajectoryConverter takes delta features (bin/vc.jl:76)")
+        return c._vc(fm, postfilter, delta=True)
     if postfilter is None:
         return c._vc(fm)
     return c._vc(fm, postfilter)

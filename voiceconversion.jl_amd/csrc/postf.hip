@@ -4,6 +4,8 @@
 //   vcmi_push_delta / _dev           [src; delta]: delta_t = (x_{t+1} - x_{t-1}) / 2 for 2 <= t <= T-1, the static value at t = 1, T
 //   vcmi_variance_scaling / _dev     per row sqrt(sigma2 / var) (x - mean) + mean, Julia's corrected variance, in place allowed
 //   vcmi_vc_frames_postf             vc(g::GMMMap, fm) with fvpostf! applied to the converted rows before the download
+//   vc_traj_pre_kernel / vc_traj_post_kernel   the two ends of vc(c::TrajectoryConverter, fm) from static features or on device
+//                                    matrices (vcmi_vc_traj_static, vcmi_vc_traj_dev, vcmi_vc_trajgv, vcmi_vc_trajgv_dev in traj.hip)
 // (vcmi_vc_traj_postf lives in traj.hip beside vcmi_vc_traj.)  Everything is HBM-bound streaming: a frame is D contiguous
 // doubles, lanes run along the features of consecutive frames (coalesced), every reduction has a fixed order.
 #include "postf.hpp"
@@ -93,16 +95,17 @@ static VsScratch &vs_scratch() {
   return s;
 }
 
-int variance_scaling_device(const double *dsrc, int64_t lds, int D, int64_t T, const double *sigma2_host, double *dout,
-                            int64_t ldo, hipStream_t st) {
+int variance_scaling_stats_device(const double *dsrc, int64_t lds, int D, int64_t T, const double *sigma2_host,
+                                  const double **dstat, hipStream_t st) {
+  static_assert(kVsStatStride >= 256, "one slot per supported feature row");
   if (D < 1 || D > 256 || T < 2)
     return fail(VCMI_ERR_DIM, "variance scaling: D=%d T=%lld unsupported (needs 1 <= D <= 256, T >= 2)", D, (long long)T);
   VsScratch &sc = vs_scratch();
   const int nchunks = (int)((T + kVsChunk - 1) / kVsChunk);
   VCMI_TRY(sc.part.reserve((size_t)nchunks * D));
-  VCMI_TRY(sc.stat.reserve((size_t)3 * 256));
+  VCMI_TRY(sc.stat.reserve((size_t)3 * kVsStatStride));
   VCMI_TRY(sc.order.enter(st));
-  double *mean = sc.stat.p, *var = sc.stat.p + 256, *sig = sc.stat.p + 512;
+  double *mean = sc.stat.p, *var = sc.stat.p + kVsStatStride, *sig = sc.stat.p + 2 * kVsStatStride;
   // (D doubles from pageable memory: the runtime stages them before returning, the caller's vector is free at once)
   VCMI_HIP(hipMemcpyAsync(sig, sigma2_host, sizeof(double) * D, hipMemcpyHostToDevice, st));
   const size_t shm = (size_t)(256 / D) * D * sizeof(double);
@@ -110,9 +113,21 @@ int variance_scaling_device(const double *dsrc, int64_t lds, int D, int64_t T, c
   hipLaunchKernelGGL(vs_final_kernel, dim3(1), dim3(256), 0, st, sc.part.p, nchunks, D, (double)T, mean);
   hipLaunchKernelGGL(vs_partial_kernel<1>, dim3(nchunks), dim3(256), shm, st, dsrc, lds, D, T, mean, sc.part.p);
   hipLaunchKernelGGL(vs_final_kernel, dim3(1), dim3(256), 0, st, sc.part.p, nchunks, D, (double)(T - 1), var);   // Julia's var
-  hipLaunchKernelGGL(vs_scale_kernel, dim3(2048), dim3(256), 0, st, dsrc, lds, D, T, sig, mean, var, dout, ldo);
   VCMI_HIP(hipGetLastError());
-  return sc.order.leave(st);
+  *dstat = sc.stat.p;
+  return VCMI_OK;
+}
+
+int variance_scaling_stats_leave(hipStream_t st) { return vs_scratch().order.leave(st); }
+
+int variance_scaling_device(const double *dsrc, int64_t lds, int D, int64_t T, const double *sigma2_host, double *dout,
+                            int64_t ldo, hipStream_t st) {
+  const double *stat = nullptr;
+  VCMI_TRY(variance_scaling_stats_device(dsrc, lds, D, T, sigma2_host, &stat, st));
+  hipLaunchKernelGGL(vs_scale_kernel, dim3(2048), dim3(256), 0, st, dsrc, lds, D, T, stat + 2 * kVsStatStride, stat,
+                     stat + kVsStatStride, dout, ldo);
+  VCMI_HIP(hipGetLastError());
+  return variance_scaling_stats_leave(st);
 }
 
 __global__ void __launch_bounds__(256)
@@ -130,6 +145,69 @@ int copy_rows_device(const double *din, int64_t ldi, int r0, int nrows, int64_t 
   const int64_t n = (int64_t)nrows * T;
   hipLaunchKernelGGL(copy_rows_kernel, dim3((unsigned)std::min<int64_t>((n + 255) / 256, 8192)), dim3(256), 0, st, din, ldi, r0, nrows, T,
                      dout, ldo, q0);
+  VCMI_HIP(hipGetLastError());
+  return VCMI_OK;
+}
+
+// ---- the two ends of vc(c::TrajectoryConverter, fm) around the chunk conversions, bin/vc.jl:75-82 + src/common.jl:31-63 ------
+// vc_traj_pre_kernel: fm (rows,T), leading dimension ldf, read once -> x (2D,T) dense, the converter's input, and the power row
+// into `out` (skipped when out is NULL: the caller assembles the result in place in fm, the row is already there).
+//   STATIC: rows = D+1; x = [fm[2:end,:]; delta], the delta over the WHOLE matrix with push_delta_kernel's arithmetic (the
+//           first and the last frame of the matrix -- not of a chunk -- keep the copy), bin/vc.jl:77-78, src/datasets.jl:6-13
+//   else:   rows = 2D+1; x = fm[2:end,:]
+template <bool STATIC>
+__global__ void __launch_bounds__(256)
+vc_traj_pre_kernel(const double *__restrict__ fm, int64_t ldf, int D, int64_t T, double *__restrict__ x, double *__restrict__ out,
+                   int64_t ldo) {
+  const int R = STATIC ? D : 2 * D;                                  // feature rows read per frame
+  const int64_t n = (int64_t)R * T;
+  for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < n; e += (int64_t)gridDim.x * 256) {
+    const int64_t t = e / R;
+    const int d = (int)(e - t * R);
+    const double *src = fm + 1;                                      // row 2 of fm: the first feature row
+    const double v = src[t * ldf + d];
+    if (STATIC) {
+      x[t * 2 * D + d] = v;
+      x[t * 2 * D + D + d] = (t >= 1 && t + 1 < T) ? -0.5 * src[(t - 1) * ldf + d] + 0.5 * src[(t + 1) * ldf + d] : v;
+    } else {
+      x[e] = v;
+    }
+    if (d == 0 && out) out[t * ldo] = fm[t * ldf];                   // power row kept, src/common.jl:60
+  }
+}
+
+int vc_traj_pre_device(const double *dfm, int64_t ldf, int D, int64_t T, bool is_static, double *dx, double *dout, int64_t ldo,
+                       hipStream_t st) {
+  if (T == 0) return VCMI_OK;
+  const int64_t n = (int64_t)(is_static ? D : 2 * D) * T;
+  const dim3 grid((unsigned)std::min<int64_t>((n + 255) / 256, 8192));
+  if (is_static) hipLaunchKernelGGL(vc_traj_pre_kernel<true>, grid, dim3(256), 0, st, dfm, ldf, D, T, dx, dout, ldo);
+  else hipLaunchKernelGGL(vc_traj_pre_kernel<false>, grid, dim3(256), 0, st, dfm, ldf, D, T, dx, dout, ldo);
+  VCMI_HIP(hipGetLastError());
+  return VCMI_OK;
+}
+
+// vc_traj_post_kernel: y (D,T) dense -> rows 2..D+1 of out (leading dimension ldo); FILTER: through fvpostf!'s scale
+// (src/gv.jl:13) with stat = [mean | var | sigma2] of variance_scaling_stats_device, the expression of vs_scale_kernel
+template <bool FILTER>
+__global__ void __launch_bounds__(256)
+vc_traj_post_kernel(const double *__restrict__ y, int D, int64_t T, const double *__restrict__ stat, double *__restrict__ out,
+                    int64_t ldo) {
+  const double *mean = stat, *var = stat + kVsStatStride, *sigma2 = stat + 2 * kVsStatStride;
+  const int64_t n = (int64_t)D * T;
+  for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < n; e += (int64_t)gridDim.x * 256) {
+    const int64_t t = e / D;
+    const int d = (int)(e - t * D);
+    out[t * ldo + 1 + d] = FILTER ? sqrt(sigma2[d] / var[d]) * (y[t * D + d] - mean[d]) + mean[d] : y[e];
+  }
+}
+
+int vc_traj_post_device(const double *dy, int D, int64_t T, const double *dstat, double *dout, int64_t ldo, hipStream_t st) {
+  if (T == 0) return VCMI_OK;
+  const int64_t n = (int64_t)D * T;
+  const dim3 grid((unsigned)std::min<int64_t>((n + 255) / 256, 8192));
+  if (dstat) hipLaunchKernelGGL(vc_traj_post_kernel<true>, grid, dim3(256), 0, st, dy, D, T, dstat, dout, ldo);
+  else hipLaunchKernelGGL(vc_traj_post_kernel<false>, grid, dim3(256), 0, st, dy, D, T, dstat, dout, ldo);
   VCMI_HIP(hipGetLastError());
   return VCMI_OK;
 }

@@ -539,12 +539,45 @@ function vc(g::GMMMap, fm::Matrix{Float64}, vs::VarianceScaling)
                 g.h, fm, size(fm, 2), vs.σ², out))
     out
 end
-function vc(t::TrajectoryGMMMap, fm::Matrix{Float64}, vs::VarianceScaling)
-    size(fm, 1) == dim(t) + 1 || throw(DimensionMismatch("Inconsistent dimentions."))
-    length(vs.σ²) == dim(t) >> 1 || throw(DimensionMismatch("σ² must have one entry per converted feature row"))
-    out = Matrix{Float64}(undef, (size(fm, 1) - 1) >> 1 + 1, size(fm, 2))
-    check(ccall((:vcmi_vc_traj_postf, libvcmi), Cint, (Ptr{Cvoid}, Ptr{Float64}, Int64, Ptr{Float64}, Ptr{Float64}),
-                t.h, fm, size(fm, 2), vs.σ², out))
+# vc(t, fm, vs; delta): vs === nothing is the plain conversion.  delta=true: fm holds the STATIC features (D+1,T) and the
+# library builds [fm[1,:]; push_delta(fm[2:end,:])] on the device over the WHOLE matrix before the chunks are cut --
+# bin/vc.jl:75-82 in one call (frame kL+1 takes its delta from frame kL of the previous chunk)
+σ²vector(vs::Nothing, D::Int) = Float64[]                              # pointer passed as C_NULL below
+function σ²vector(vs::VarianceScaling, D::Int)
+    length(vs.σ²) == D || throw(DimensionMismatch("σ² must have one entry per converted feature row"))
+    vs.σ²
+end
+σ²pointer(vs, σ²::Vector{Float64}) = vs === nothing ? Ptr{Float64}(C_NULL) : pointer(σ²)
+
+function vc(t::TrajectoryGMMMap, fm::Matrix{Float64}, vs::Union{VarianceScaling,Nothing}; delta::Bool=false)
+    D = dim(t) >> 1
+    size(fm, 1) == (delta ? D : 2D) + 1 || throw(DimensionMismatch("Inconsistent dimentions."))
+    σ² = σ²vector(vs, D)
+    out = Matrix{Float64}(undef, D + 1, size(fm, 2))
+    GC.@preserve σ² begin
+        if delta
+            check(ccall((:vcmi_vc_traj_static, libvcmi), Cint, (Ptr{Cvoid}, Ptr{Float64}, Int64, Ptr{Float64}, Ptr{Float64}),
+                        t.h, fm, size(fm, 2), σ²pointer(vs, σ²), out))
+        else
+            check(ccall((:vcmi_vc_traj_postf, libvcmi), Cint, (Ptr{Cvoid}, Ptr{Float64}, Int64, Ptr{Float64}, Ptr{Float64}),
+                        t.h, fm, size(fm, 2), σ²pointer(vs, σ²), out))
+        end
+    end
+    out
+end
+# ... and for the GV converter: every chunk through fvconvert(tgv, X; epochs, α), one call on the device; afterwards
+# length(tgv) is the last chunk's length (src/trajectory_gmmmap.jl:70-72,146)
+function vc(tgv::TrajectoryGVGMMMap, fm::Matrix{Float64}, vs::Union{VarianceScaling,Nothing}; delta::Bool=false,
+            epochs::Int=100, α::Float64=1.0e-5)
+    D = dim(tgv) >> 1
+    size(fm, 1) == (delta ? D : 2D) + 1 || throw(DimensionMismatch("Inconsistent dimentions."))
+    σ² = σ²vector(vs, D)
+    out = Matrix{Float64}(undef, D + 1, size(fm, 2))
+    GC.@preserve σ² begin
+        check(ccall((:vcmi_vc_trajgv, libvcmi), Cint,
+                    (Ptr{Cvoid}, Ptr{Float64}, Int64, Cint, Cint, Cdouble, Ptr{Float64}, Ptr{Float64}),
+                    tgv.h, fm, size(fm, 2), delta ? 1 : 0, epochs, α, σ²pointer(vs, σ²), out))
+    end
     out
 end
 
@@ -560,6 +593,34 @@ function push_delta(src::DeviceMatrix, out::DeviceMatrix; stream::Ptr{Cvoid}=C_N
     (out.rows == 2src.rows && out.cols == src.cols) || throw(DimensionMismatch("out must be (2D,T)"))
     check(ccall((:vcmi_push_delta_dev, libvcmi), Cint, (Ptr{Float64}, Int64, Cint, Int64, Ptr{Float64}, Int64, Ptr{Cvoid}),
                 src.ptr, src.ld, src.rows, src.cols, out.ptr, out.ld, stream))
+    out
+end
+# vc of a trajectory converter on a matrix in HBM: fm (D+1,T) static (delta=true) or (2D+1,T) -> out (D+1,T), out must not
+# overlap fm; asynchronous on `stream` up to the read of the solver's status
+function vc(t::TrajectoryGMMMap, fm::DeviceMatrix, out::DeviceMatrix, vs::Union{VarianceScaling,Nothing}=nothing;
+            delta::Bool=false, stream::Ptr{Cvoid}=C_NULL)
+    D = dim(t) >> 1
+    fm.rows == (delta ? D : 2D) + 1 || throw(DimensionMismatch("Inconsistent dimentions."))
+    (out.rows == D + 1 && out.cols == fm.cols) || throw(DimensionMismatch("out must be (D+1,T)"))
+    σ² = σ²vector(vs, D)
+    GC.@preserve σ² begin
+        check(ccall((:vcmi_vc_traj_dev, libvcmi), Cint,
+                    (Ptr{Cvoid}, Ptr{Float64}, Int64, Int64, Cint, Ptr{Float64}, Ptr{Float64}, Int64, Ptr{Cvoid}),
+                    t.h, fm.ptr, fm.ld, fm.cols, delta ? 1 : 0, σ²pointer(vs, σ²), out.ptr, out.ld, stream))
+    end
+    out
+end
+function vc(tgv::TrajectoryGVGMMMap, fm::DeviceMatrix, out::DeviceMatrix, vs::Union{VarianceScaling,Nothing}=nothing;
+            delta::Bool=false, epochs::Int=100, α::Float64=1.0e-5, stream::Ptr{Cvoid}=C_NULL)
+    D = dim(tgv) >> 1
+    fm.rows == (delta ? D : 2D) + 1 || throw(DimensionMismatch("Inconsistent dimentions."))
+    (out.rows == D + 1 && out.cols == fm.cols) || throw(DimensionMismatch("out must be (D+1,T)"))
+    σ² = σ²vector(vs, D)
+    GC.@preserve σ² begin
+        check(ccall((:vcmi_vc_trajgv_dev, libvcmi), Cint,
+                    (Ptr{Cvoid}, Ptr{Float64}, Int64, Int64, Cint, Cint, Cdouble, Ptr{Float64}, Ptr{Float64}, Int64, Ptr{Cvoid}),
+                    tgv.h, fm.ptr, fm.ld, fm.cols, delta ? 1 : 0, epochs, α, σ²pointer(vs, σ²), out.ptr, out.ld, stream))
+    end
     out
 end
 function fvpostf!(vs::VarianceScaling, src::DeviceMatrix; stream::Ptr{Cvoid}=C_NULL)      # src/gv.jl:10-15, in place

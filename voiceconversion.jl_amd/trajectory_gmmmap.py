@@ -51,6 +51,40 @@ def push_delta(src):
     return out
 
 
+def _sigma2(postfilter, D):
+    """The sigma2 argument of the vc entries: NULL without a post-filter."""
+    if postfilter is None:
+        return None
+    if postfilter.sigma2.shape != (D,):
+        raise _lib.DimensionMismatch("sigma2 must have one entry per converted feature row")
+    return _lib.dptr(postfilter.sigma2)
+
+
+def _vc_static_args(c, fm, postfilter):
+    """fm (D+1,T) STATIC features of vc(c, fm; delta=True) -> (fm as a Julia matrix, D, sigma2 argument)"""
+    fm = jl_matrix(fm, "fm")
+    D = c._dim() // 2
+    if fm.shape[0] != D + 1:
+        raise _lib.DimensionMismatch("Inconsistent dimentions.")
+    return fm, D, _sigma2(postfilter, D)
+
+
+def _vc_dev(c, fm, postfilter, delta, call):
+    """vc of a trajectory converter on a device tensor fm ((D+1,T) static or (2D+1,T), unit stride along the rows):
+    call(ptr, ld, T, is_static, sigma2, out_ptr, ld_out, stream) is the converter's `_dev` entry; the result is the (D+1,T)
+    transposed view of a new (T, D+1) device buffer, like push_delta's."""
+    import torch
+
+    ptr, rows, T, ld = dev_matrix(fm, "fm")
+    D = c._dim() // 2
+    if rows != (D if delta else 2 * D) + 1:
+        raise _lib.DimensionMismatch("Inconsistent dimentions.")
+    s2 = _sigma2(postfilter, D)
+    buf = torch.empty((T, D + 1), dtype=torch.float64, device=fm.device)
+    _lib.check(call(ptr, ld, T, int(bool(delta)), s2, buf.data_ptr(), D + 1, current_stream_ptr()))
+    return buf.t()
+
+
 class TrajectoryGMMMap(TrajectoryConverter):
     """TrajectoryGMMMap(g::GMMMap, T) -- src/trajectory_gmmmap.jl:3-37.  `g` is a GMMMap over static+delta
     features (dim(g) = 2D).  The constructor precomputes Dy_m = inv(Sigma^yy_m - A_m Sigma^xy_m) (:24-28)."""
@@ -103,8 +137,21 @@ class TrajectoryGMMMap(TrajectoryConverter):
                                                     dpp(*[_lib.dptr(y) for y in Ys])))
         return Ys
 
-    def _vc(self, fm, postfilter=None):
-        """vc(c::TrajectoryConverter, fm (2D+1,T)) -> (D+1,T) in chunks of length(c) frames; src/common.jl:31-63"""
+    def _vc(self, fm, postfilter=None, delta=False):
+        """vc(c::TrajectoryConverter, fm (2D+1,T)) -> (D+1,T) in chunks of length(c) frames; src/common.jl:31-63.
+        delta=True: fm holds STATIC features (D+1,T); the deltas are taken on the device over the whole matrix before it is
+        cut into chunks (bin/vc.jl:75-78; vcmi_vc_traj_static).  A torch tensor on the device is converted where it is, on
+        the current stream (vcmi_vc_traj_dev), and a device tensor (D+1,T) comes back."""
+        if is_torch(fm) and fm.is_cuda:
+            def entry(*args):
+                return _lib.lib.vcmi_vc_traj_dev(self._h, *args)
+
+            return _vc_dev(self, fm, postfilter, delta, entry)
+        if delta:
+            fm, D, s2 = _vc_static_args(self, fm, postfilter)
+            out = np.empty_like(fm, order="F")
+            _lib.check(_lib.lib.vcmi_vc_traj_static(self._h, _lib.dptr(fm), fm.shape[1], s2, _lib.dptr(out)))
+            return out
         fm = jl_matrix(fm, "fm")
         D2 = self._dim()
         if fm.shape[0] != D2 + 1:
@@ -172,9 +219,30 @@ class TrajectoryGVGMMMap(TrajectoryConverter):
                                                       float(alpha), dpp(*[_lib.dptr(y) for y in Ys])))
         return Ys
 
-    def _vc(self, fm):
-        """vc(c::TrajectoryConverter, fm): chunks of length(c) frames, each converted with the default epochs / alpha;
-        src/common.jl:31-63"""
+    def _vc(self, fm, postfilter=None, delta=False, epochs=100, alpha=1.0e-5):
+        """vc(c::TrajectoryConverter, fm): chunks of length(c) frames, each converted with fvconvert(tgv, X; epochs, alpha);
+        src/common.jl:31-63.  A postfilter, delta=True (STATIC features (D+1,T), deltas over the whole matrix first:
+        bin/vc.jl:75-78), a device tensor or non-default epochs / alpha run as one call on the device (vcmi_vc_trajgv,
+        vcmi_vc_trajgv_dev), after which len(c) is the last chunk's length as the reference leaves it
+        (src/trajectory_gmmmap.jl:70-72,146).  The plain call on a host matrix keeps the loop below."""
+        if is_torch(fm) and fm.is_cuda:
+            def entry(ptr, ld, T, is_static, s2, optr, ldo, stream):
+                return _lib.lib.vcmi_vc_trajgv_dev(self._h, ptr, ld, T, is_static, int(epochs), float(alpha), s2, optr, ldo, stream)
+
+            return _vc_dev(self, fm, postfilter, delta, entry)
+        if delta or postfilter is not None or (epochs, alpha) != (100, 1.0e-5):
+            D = self._dim() // 2
+            if delta:
+                fm, D, s2 = _vc_static_args(self, fm, postfilter)
+            else:
+                fm = jl_matrix(fm, "fm")
+                if fm.shape[0] != 2 * D + 1:
+                    raise _lib.DimensionMismatch("Inconsistent dimentions.")
+                s2 = _sigma2(postfilter, D)
+            out = np.empty((D + 1, fm.shape[1]), order="F")
+            _lib.check(_lib.lib.vcmi_vc_trajgv(self._h, _lib.dptr(fm), fm.shape[1], int(bool(delta)), int(epochs), float(alpha), s2,
+                                               _lib.dptr(out)))
+            return out
         fm = jl_matrix(fm, "fm")
         D2 = self._dim()
         if fm.shape[0] != D2 + 1:
