@@ -238,6 +238,32 @@ int vcmi_gmm_em_estep_dev(vcmi_gmm_em *h, const double *dX, int64_t N, double *d
 int vcmi_gmm_em_mstep(vcmi_gmm_em *h, const double *dstats, void *stream, double *loglik);
 int vcmi_gmm_em_get(vcmi_gmm_em *h, double *w, double *mu, double *sigma);
 
+/* The same loop for a DIAGONAL model (sklearn.mixture.GMM(covariance_type="diag", min_covar); the usual cheap warm start of
+ * the full-covariance fit).  The handle owns the parameters on the device as [w (M) | mu (Dj,M) | var (Dj,M)], 1 <= Dj <= 256;
+ * one iteration is
+ *   vcmi_gmm_em_diag_estep_dev (vcmi_estep_diag_dev's statistics under the handle's parameters, asynchronous on `stream`;
+ *      N == 0 gives zeroed statistics)
+ *   -> the caller sums the statistics buffers of all ranks (one all-reduce of vcmi_estep_stats_len(Dj,M) doubles)
+ *   -> vcmi_gmm_em_diag_mstep (eps = 2^-52:  w = S0 / (sum S0 + 10 eps) + eps,  inv = 1 / (S0 + 10 eps),  mu = S1 inv,
+ *      var = S2 inv - 2 mu S1 inv + mu mu + min_covar; the sum over M in a fixed order, no floating-point atomics: the same
+ *      statistics give the same bits).  It synchronises the stream and returns the log-likelihood the statistics carry.
+ * For M <= 128 and an even Dj <= 160 the E-step's preparation kernels read the handle's block: no parameter crosses the
+ * host, the call waits for nothing, and its statistics are bit-identical to vcmi_estep_diag_dev called with the values
+ * vcmi_gmm_em_diag_get returns (the same paths: vcmi_estep_set_path applies).  Odd Dj, M > 128 and Dj > 160 have no such
+ * route -- their host code pads, regroups or transposes the parameters: the handle copies its block to the host, with ONE
+ * stream synchronisation per E-step, and calls the host-parameter path (same bits again).
+ * VCMI_ERR_NOT_PD: a variance that is not > 0 (a NaN included) -- from create for the initial ones, from mstep for updated
+ * ones (the message names the first (d, m) in memory order).  After a failed mstep the handle keeps the parameters the
+ * statistics were computed under (vcmi_gmm_em_diag_get shows them), every later mstep fails the same way and
+ * vcmi_gmm_em_diag_estep_dev returns VCMI_ERR_NOT_PD without launching. */
+typedef struct vcmi_gmm_em_diag vcmi_gmm_em_diag;
+int vcmi_gmm_em_diag_create(int Dj, int M, const double *w, const double *mu, const double *var, double min_covar,
+                            vcmi_gmm_em_diag **out);
+int vcmi_gmm_em_diag_destroy(vcmi_gmm_em_diag *h);
+int vcmi_gmm_em_diag_estep_dev(vcmi_gmm_em_diag *h, const double *dX, int64_t N, double *dstats, void *stream);
+int vcmi_gmm_em_diag_mstep(vcmi_gmm_em_diag *h, const double *dstats, void *stream, double *loglik);
+int vcmi_gmm_em_diag_get(vcmi_gmm_em_diag *h, double *w, double *mu, double *var);
+
 /* k-means -- sklearn 0.17 cluster.KMeans, what GMM(init_params="wmc") runs over all of X before the first E-step
  * (bin/train_gmm.jl:84-89).  Centers (Dj,M) column-major, 1 <= Dj <= 256, 1 <= M <= 1024; every distance is the direct
  * difference sum_d (x_d - c_d)^2 (sequential in d, FP64, no contraction); exact ties go to the smaller center index.

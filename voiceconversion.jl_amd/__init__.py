@@ -17,7 +17,7 @@ from .estep import (ESTEP_AUTO, ESTEP_HARD, ESTEP_SOFT, estep_diag, estep_diag_a
                     unpack_full_stats)
 from .trajectory_gmmmap import TrajectoryGVGMMMap, TrajectoryGMMMap, constructW, push_delta  # noqa: F401,E402
 from . import dist  # noqa: F401,E402
-from .train import EMState, train_gmm  # noqa: F401,E402
+from .train import DiagEMState, EMState, expand_diag, train_gmm  # noqa: F401,E402
 from .kmeans import KMeansState, kmeans  # noqa: F401,E402
 from .gv import VarianceScaling, diffgmm, fvpostf, fvpostf_  # noqa: F401,E402
 from .datasets import GVDataset, ParallelDataset, align_mcep, mc2e  # noqa: F401,E402

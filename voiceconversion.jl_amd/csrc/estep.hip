@@ -763,9 +763,13 @@ estep_prep_kernel(const double *__restrict__ raw, int M, int dj, double *__restr
 
 // The MFMA path for one joint dimension (parameters staged through pinned buffers, prep kernel, the E-step kernel with one
 // workgroup per CU, fixed-order reduction of the workgroups' partial statistics).
+// `dparams` (optional): the parameters as a DEVICE block [w (M) | mu (dj,M) | var (dj,M)] that the caller keeps alive and orders
+// on `st` (vcmi_gmm_em_diag: the M-step kernel wrote it).  The prep kernels then read that block: no staging slot, no copies, no
+// event, nothing the host waits for -- w / mu / var are not looked at.  Everything from the prep kernels on is the same code on the
+// same operands: the same parameter values give the same bits through either entry.
 template <int DJ>
 static int estep_mfma_launch(EstepScratch &sc, const double *dX, int64_t N, int dj, int M, const double *w, const double *mu,
-                             const double *var, double *dstats, int64_t plen, hipStream_t st) {
+                             const double *var, double *dstats, int64_t plen, hipStream_t st, const double *dparams = nullptr) {
   using C = EstepCfg<DJ>;
   int dev = 0, cus = 256;
   (void)hipGetDevice(&dev);
@@ -773,7 +777,7 @@ static int estep_mfma_launch(EstepScratch &sc, const double *dX, int64_t N, int 
   const int64_t nblocks = (N + C::FB - 1) / C::FB;
   const int grid = (int)std::min<int64_t>(nblocks, cus);
   const size_t nraw = (size_t)M * (1 + 2 * dj);
-  VCMI_TRY(sc.raw.reserve(EstepStaging::kSlots * nraw));                  // one device copy per staging buffer
+  if (!dparams) VCMI_TRY(sc.raw.reserve(EstepStaging::kSlots * nraw));    // one device copy per staging buffer
   VCMI_TRY(sc.Wpack.reserve((size_t)8 * C::KS * 64));
   VCMI_TRY(sc.cinit.reserve((size_t)C::MMAX));
   VCMI_TRY(sc.refiv.reserve((size_t)M * dj));
@@ -783,20 +787,24 @@ static int estep_mfma_launch(EstepScratch &sc, const double *dX, int64_t N, int 
   while (16 * mtp < M) mtp *= 2;
   const int wpt = 8 / mtp;
   VCMI_TRY(sc.part.reserve((size_t)grid * wpt * plen));
-  VCMI_TRY(sc.stage.reserve(nraw));
-  const int b = sc.stage.next;
-  sc.stage.next = (sc.stage.next + 1) % EstepStaging::kSlots;
-  VCMI_HIP(hipEventSynchronize(sc.stage.copied[b]));   // the copy that last used this slot (eight calls ago) is done
-  double *h = sc.stage.host[b], *draw = sc.raw.p + (size_t)b * nraw;
-  memcpy(h, w, sizeof(double) * M);
-  memcpy(h + M, mu, sizeof(double) * M * dj);
-  memcpy(h + M + (size_t)M * dj, var, sizeof(double) * M * dj);
-  // (a copy kernel reading the pinned slot, not hipMemcpyAsync: the copy engine's hand-over to the compute queue costs
-  // ~20 us of idle GPU per call, a kernel on the same queue a few.  Round 4 let the prep kernel read the pinned slot itself
-  // and write the device copy -- one launch less -- and lost 7 us per call: its threads read every parameter three or four
-  // times, across the link.)
-  hipLaunchKernelGGL(estep_param_copy_kernel, dim3((unsigned)((nraw + 255) / 256)), dim3(256), 0, st, h, draw, nraw);
-  VCMI_HIP(hipEventRecord(sc.stage.copied[b], st));
+  const double *draw = dparams;
+  if (!dparams) {
+    VCMI_TRY(sc.stage.reserve(nraw));
+    const int b = sc.stage.next;
+    sc.stage.next = (sc.stage.next + 1) % EstepStaging::kSlots;
+    VCMI_HIP(hipEventSynchronize(sc.stage.copied[b]));   // the copy that last used this slot (eight calls ago) is done
+    double *h = sc.stage.host[b], *dslot = sc.raw.p + (size_t)b * nraw;
+    memcpy(h, w, sizeof(double) * M);
+    memcpy(h + M, mu, sizeof(double) * M * dj);
+    memcpy(h + M + (size_t)M * dj, var, sizeof(double) * M * dj);
+    // (a copy kernel reading the pinned slot, not hipMemcpyAsync: the copy engine's hand-over to the compute queue costs
+    // ~20 us of idle GPU per call, a kernel on the same queue a few.  Round 4 let the prep kernel read the pinned slot itself
+    // and write the device copy -- one launch less -- and lost 7 us per call: its threads read every parameter three or four
+    // times, across the link.)
+    hipLaunchKernelGGL(estep_param_copy_kernel, dim3((unsigned)((nraw + 255) / 256)), dim3(256), 0, st, h, dslot, nraw);
+    VCMI_HIP(hipEventRecord(sc.stage.copied[b], st));
+    draw = dslot;
+  }
   hipLaunchKernelGGL(estep_prep_kernel<DJ>, dim3((8 * C::KS * 64 + 255) / 256), dim3(256), 0, st, draw, M, dj, sc.Wpack.p,
                      sc.cinit.p, sc.refiv.p, sc.refc.p);
   VCMI_HIP(hipGetLastError());
@@ -1024,6 +1032,23 @@ static int estep_mfma_groups_launch(EstepScratch &sc, const double *dX, int64_t 
 static int estep_device_run(const double *dX, int64_t N, int Dj, int M, const double *w, const double *mu, const double *var,
                             double *dstats, hipStream_t st);
 
+// the shapes estep_mfma_launch serves: at most 128 mixtures, an even joint dimension up to 160
+static bool estep_mfma_shape(int Dj, int M) {
+  return M <= EstepCfg<80>::MMAX && Dj % 2 == 0 && Dj <= 160 && !debug_flag(kDbgEstepGeneric);
+}
+// ... and the instantiation that runs one of them, from host parameters or from a device block (estep_mfma_launch)
+static int estep_mfma_dispatch(EstepScratch &sc, const double *dX, int64_t N, int Dj, int M, const double *w, const double *mu,
+                               const double *var, double *dstats, int64_t plen, hipStream_t st, const double *dparams) {
+  // the smallest instantiation that holds Dj (an even Dj keeps the rows of X 16-byte aligned for the LDS-DMA)
+  if (Dj <= 32) return estep_mfma_launch<32>(sc, dX, N, Dj, M, w, mu, var, dstats, plen, st, dparams);
+  if (Dj <= 48) return estep_mfma_launch<48>(sc, dX, N, Dj, M, w, mu, var, dstats, plen, st, dparams);
+  if (Dj <= 64) return estep_mfma_launch<64>(sc, dX, N, Dj, M, w, mu, var, dstats, plen, st, dparams);
+  if (Dj <= 80) return estep_mfma_launch<80>(sc, dX, N, Dj, M, w, mu, var, dstats, plen, st, dparams);
+  // (the two-kernel form beyond 80; 112 for the dimensions between -- Dj = 82 ... 112 ran in the 160-wide one: 1.5 x the work)
+  if (Dj <= 112) return estep_mfma_launch<112>(sc, dX, N, Dj, M, w, mu, var, dstats, plen, st, dparams);
+  return estep_mfma_launch<160>(sc, dX, N, Dj, M, w, mu, var, dstats, plen, st, dparams);
+}
+
 static int estep_device(const double *dX, int64_t N, int Dj, int M, const double *w, const double *mu, const double *var,
                         double *dstats, hipStream_t st) {
   EstepScratch &sc = scratch();
@@ -1083,16 +1108,7 @@ static int estep_device_run(const double *dX, int64_t N, int Dj, int M, const do
     if (Dj <= 112) return estep_mfma_groups_launch<112>(sc, dX, N, Dj, M, w, mu, var, dstats, plen, st);
     return estep_mfma_groups_launch<160>(sc, dX, N, Dj, M, w, mu, var, dstats, plen, st);
   }
-  if (M <= EstepCfg<80>::MMAX && Dj % 2 == 0 && Dj <= 160 && !debug_flag(kDbgEstepGeneric)) {
-    // the smallest instantiation that holds Dj (an even Dj keeps the rows of X 16-byte aligned for the LDS-DMA)
-    if (Dj <= 32) return estep_mfma_launch<32>(sc, dX, N, Dj, M, w, mu, var, dstats, plen, st);
-    if (Dj <= 48) return estep_mfma_launch<48>(sc, dX, N, Dj, M, w, mu, var, dstats, plen, st);
-    if (Dj <= 64) return estep_mfma_launch<64>(sc, dX, N, Dj, M, w, mu, var, dstats, plen, st);
-    if (Dj <= 80) return estep_mfma_launch<80>(sc, dX, N, Dj, M, w, mu, var, dstats, plen, st);
-    // (the two-kernel form beyond 80; 112 for the dimensions between -- Dj = 82 ... 112 ran in the 160-wide one: 1.5 x the work)
-    if (Dj <= 112) return estep_mfma_launch<112>(sc, dX, N, Dj, M, w, mu, var, dstats, plen, st);
-    return estep_mfma_launch<160>(sc, dX, N, Dj, M, w, mu, var, dstats, plen, st);
-  }
+  if (estep_mfma_shape(Dj, M)) return estep_mfma_dispatch(sc, dX, N, Dj, M, w, mu, var, dstats, plen, st, nullptr);
 
   std::vector<double> hiv((size_t)M * Dj), hc(M);
   for (int m = 0; m < M; ++m) {
@@ -1738,6 +1754,45 @@ em_mstep_full_kernel(const double *__restrict__ stats, int Dj, int M, double min
   }
 }
 
+// The diagonal twin (estep.py:mstep_diag, operation for operation; the old sklearn GMM's covariance_type="diag" update):
+//   stats = [S0 (M) | S1 (Dj,M) | S2 (Dj,M) | loglik]  ->  raw = [w (M) | mu (Dj,M) | var (Dj,M)], the block the diagonal E-step's
+//   prep kernels read (estep_prep_kernel, estep_hard_prep_kernel).
+// One workgroup per mixture, thread d owns dimension d (Dj <= 256); the total over M in the fixed order of em_mstep_full_kernel
+// (256 strided partial sums, a tree): no floating-point atomics, the same statistics give the same bits.  The five roundings of
+// the variance are the five of the numpy expression -- no contraction into FMAs.  A variance that is not > 0 (a NaN included)
+// is reported through ctl: ctl[1] receives the smallest 1 + d + Dj m (an integer minimum: the same answer whatever the order
+// of the workgroups).  ctl[0] is the latch of an EARLIER failed M-step: the kernel then leaves `raw` alone.  ctl[2..3] carry the
+// log-likelihood of the statistics, so that the host reads it and the report in one copy.
+__global__ void __launch_bounds__(256)
+em_mstep_diag_kernel(const double *__restrict__ stats, int Dj, int M, double min_covar, double *__restrict__ raw, int *__restrict__ ctl) {
+#pragma clang fp contract(off)
+  __shared__ double red[256];
+  const int tid = threadIdx.x, m = blockIdx.x;
+  if (m == 0 && tid == 0) *reinterpret_cast<double *>(ctl + 2) = stats[(size_t)M * (1 + 2 * (size_t)Dj)];
+  if (ctl[0]) return;
+  const double eps = 2.220446049250313e-16;
+  double t = 0.0;
+  for (int k = tid; k < M; k += 256) t += stats[k];
+  red[tid] = t;
+  __syncthreads();
+  for (int o = 128; o >= 1; o >>= 1) {
+    if (tid < o) red[tid] += red[tid + o];
+    __syncthreads();
+  }
+  const double tot = red[0], s0 = stats[m];
+  const double inv = 1.0 / (s0 + 10 * eps);
+  if (tid == 0) raw[m] = s0 / (tot + 10 * eps) + eps;
+  if (tid < Dj) {
+    const size_t e = (size_t)m * Dj + tid;
+    const double s1 = stats[M + e], s2 = stats[M + (size_t)M * Dj + e];
+    const double mean = s1 * inv;
+    const double v = s2 * inv - ((2.0 * mean) * s1) * inv + mean * mean + min_covar;
+    raw[M + e] = mean;
+    raw[M + (size_t)M * Dj + e] = v;
+    if (!(v > 0.0)) atomicMin(ctl + 1, (int)(1 + e));
+  }
+}
+
 }  // namespace vcmi
 
 struct vcmi_gmm_em {
@@ -1777,6 +1832,25 @@ static int em_prepare(vcmi_gmm_em *h, hipStream_t st) {
   return VCMI_OK;
 }
 }  // namespace vcmi
+
+// The diagonal EM state.  `raw` holds TWO parameter blocks [w | mu (Dj,M) | var (Dj,M)]: the E-step reads block `cur`, the M-step
+// kernel writes the other one, and vcmi_gmm_em_diag_mstep -- which synchronises anyway -- makes that one current only when no
+// variance was reported.  So a failed M-step leaves the parameters its statistics were computed under, whichever workgroup
+// found the variance and whichever had already written.
+struct vcmi_gmm_em_diag {
+  int Dj = 0, M = 0, device = 0, cur = 0;
+  double min_covar = 0.0;
+  bool failed = false;           // an M-step reported a variance: the state takes no further E-step
+  int bad = 0;                   // ... 1 + d + Dj m of that variance
+  vcmi::DevBuf<double> raw;      // 2 x M (1 + 2 Dj)
+  vcmi::DevBuf<int> ctl;         // [latch | smallest bad index (INT_MAX: none) | loglik (a double)]
+  std::vector<double> host;      // the current block on the host, for the shapes without a device-parameter route
+  size_t nraw() const { return (size_t)M * (1 + 2 * (size_t)Dj); }
+  double *params() { return raw.p + (size_t)cur * nraw(); }
+  int not_pd() const {
+    return vcmi::fail(VCMI_ERR_NOT_PD, "M-step: variance (%d,%d) is not positive", (bad - 1) % Dj + 1, (bad - 1) / Dj + 1);
+  }
+};
 
 using namespace vcmi;
 
@@ -1936,6 +2010,118 @@ extern "C" int vcmi_gmm_em_get(vcmi_gmm_em *h, double *w, double *mu, double *si
   VCMI_HIP(hipMemcpy(w, h->w(), sizeof(double) * h->M, hipMemcpyDeviceToHost));
   VCMI_HIP(hipMemcpy(mu, h->mu(), sizeof(double) * h->M * h->Dj, hipMemcpyDeviceToHost));
   VCMI_HIP(hipMemcpy(sigma, h->sigma(), sizeof(double) * h->M * dd, hipMemcpyDeviceToHost));
+  return VCMI_OK;
+}
+
+// ---- device-resident diagonal EM state -----------------------------------------------------------
+extern "C" int vcmi_gmm_em_diag_create(int Dj, int M, const double *w, const double *mu, const double *var, double min_covar,
+                                       vcmi_gmm_em_diag **out) {
+  if (!w || !mu || !var || !out) return fail(VCMI_ERR_ARG, "vcmi_gmm_em_diag_create: NULL argument");
+  *out = nullptr;
+  if (Dj < 1 || M < 1) return fail(VCMI_ERR_DIM, "vcmi_gmm_em_diag_create: Dj=%d M=%d invalid", Dj, M);
+  if (Dj > 256)   // em_mstep_diag_kernel: one thread of a 256-thread workgroup per dimension
+    return fail(VCMI_ERR_DIM, "vcmi_gmm_em_diag_create: joint dimension %d exceeds the device EM limit (256)", Dj);
+  if ((int64_t)M * Dj >= INT32_MAX) return fail(VCMI_ERR_DIM, "vcmi_gmm_em_diag_create: Dj=%d M=%d too large", Dj, M);
+  if (!(min_covar >= 0.0)) return fail(VCMI_ERR_ARG, "vcmi_gmm_em_diag_create: min_covar must be >= 0");
+  for (int m = 0; m < M; ++m)
+    for (int d = 0; d < Dj; ++d)
+      if (!(var[d + (size_t)Dj * m] > 0.0))
+        return fail(VCMI_ERR_NOT_PD, "vcmi_gmm_em_diag_create: variance (%d,%d) is not positive", d + 1, m + 1);
+  VCMI_TRY(check_device());
+  vcmi_gmm_em_diag *h = new (std::nothrow) vcmi_gmm_em_diag();
+  if (!h) return fail(VCMI_ERR_OOM, "out of host memory");
+  h->Dj = Dj;
+  h->M = M;
+  h->min_covar = min_covar;
+  (void)hipGetDevice(&h->device);
+  int rc = h->raw.alloc(2 * h->nraw());
+  if (rc == VCMI_OK) rc = h->ctl.alloc(4);
+  if (rc != VCMI_OK) {
+    delete h;
+    return rc;
+  }
+  const int ctl0[4] = {0, INT32_MAX, 0, 0};
+  hipError_t e = upload_now_hip(h->raw.p, w, sizeof(double) * M);
+  if (e == hipSuccess) e = upload_now_hip(h->raw.p + M, mu, sizeof(double) * M * Dj);
+  if (e == hipSuccess) e = upload_now_hip(h->raw.p + M + (size_t)M * Dj, var, sizeof(double) * M * Dj);
+  if (e == hipSuccess) e = upload_now_hip(h->ctl.p, ctl0, sizeof(ctl0));
+  if (e != hipSuccess) {
+    delete h;
+    return fail(VCMI_ERR_HIP, "vcmi_gmm_em_diag_create: %s", hipGetErrorString(e));
+  }
+  *out = h;
+  return VCMI_OK;
+}
+
+extern "C" int vcmi_gmm_em_diag_destroy(vcmi_gmm_em_diag *h) {
+  delete h;
+  return VCMI_OK;
+}
+
+extern "C" int vcmi_gmm_em_diag_estep_dev(vcmi_gmm_em_diag *h, const double *dX, int64_t N, double *dstats, void *stream) {
+  if (!h || !dstats) return fail(VCMI_ERR_ARG, "vcmi_gmm_em_diag_estep_dev: NULL argument");
+  if (N < 0 || (N > 0 && !dX)) return fail(VCMI_ERR_ARG, "vcmi_gmm_em_diag_estep_dev: bad frame block");
+  if (h->failed) return h->not_pd();
+  hipStream_t st = as_stream(stream);
+  const int Dj = h->Dj, M = h->M;
+  const int64_t plen = vcmi_estep_stats_len(Dj, M);
+  if (N == 0) {
+    VCMI_HIP(hipMemsetAsync(dstats, 0, plen * sizeof(double), st));
+    return VCMI_OK;
+  }
+  if (estep_mfma_shape(Dj, M)) {
+    // the parameters never leave the device: the prep kernels read the block the M-step kernel wrote (its variances are
+    // positive: vcmi_gmm_em_diag_create and every M-step since have checked them)
+    EstepScratch &sc = scratch();
+    VCMI_TRY(sc.order.enter(st));
+    sc.last_hard = false;
+    const int rc = estep_mfma_dispatch(sc, dX, N, Dj, M, nullptr, nullptr, nullptr, dstats, plen, st, h->params());
+    (void)sc.order.leave(st);
+    return rc;
+  }
+  // odd Dj, M > 128, Dj > 160: the host code of these shapes pads, regroups or transposes the parameters -- copy the block
+  // down (one stream synchronisation per E-step) and take the host-parameter path
+  h->host.resize(h->nraw());
+  VCMI_HIP(hipMemcpyAsync(h->host.data(), h->params(), h->nraw() * sizeof(double), hipMemcpyDeviceToHost, st));
+  VCMI_HIP(hipStreamSynchronize(st));
+  const double *hw = h->host.data(), *hmu = hw + M, *hvar = hmu + (size_t)M * Dj;
+  return estep_device(dX, N, Dj, M, hw, hmu, hvar, dstats, st);
+}
+
+extern "C" int vcmi_gmm_em_diag_mstep(vcmi_gmm_em_diag *h, const double *dstats, void *stream, double *loglik) {
+  if (!h || !dstats) return fail(VCMI_ERR_ARG, "vcmi_gmm_em_diag_mstep: NULL argument");
+  hipStream_t st = as_stream(stream);
+  double *next = h->raw.p + (size_t)(1 - h->cur) * h->nraw();
+  hipLaunchKernelGGL(em_mstep_diag_kernel, dim3(h->M), dim3(256), 0, st, dstats, h->Dj, h->M, h->min_covar, next, h->ctl.p);
+  VCMI_HIP(hipGetLastError());
+  struct {
+    int latch, bad;
+    double ll;
+  } r = {0, 0, 0.0};
+  static_assert(sizeof(r) == 16, "the control block is two ints and a double");
+  VCMI_HIP(hipMemcpyAsync(&r, h->ctl.p, sizeof(r), hipMemcpyDeviceToHost, st));
+  VCMI_HIP(hipStreamSynchronize(st));
+  if (loglik) *loglik = r.ll;
+  if (r.bad != INT32_MAX) {
+    if (!h->failed) {      // latch it on the device too: a later M-step kernel returns before it writes
+      const int one = 1;
+      VCMI_HIP(hipMemcpy(h->ctl.p, &one, sizeof(int), hipMemcpyHostToDevice));
+    }
+    h->failed = true;
+    h->bad = r.bad;
+    return h->not_pd();
+  }
+  h->cur = 1 - h->cur;
+  return VCMI_OK;
+}
+
+extern "C" int vcmi_gmm_em_diag_get(vcmi_gmm_em_diag *h, double *w, double *mu, double *var) {
+  if (!h || !w || !mu || !var) return fail(VCMI_ERR_ARG, "vcmi_gmm_em_diag_get: NULL argument");
+  VCMI_HIP(hipDeviceSynchronize());
+  const size_t md = (size_t)h->M * h->Dj;
+  VCMI_HIP(hipMemcpy(w, h->params(), sizeof(double) * h->M, hipMemcpyDeviceToHost));
+  VCMI_HIP(hipMemcpy(mu, h->params() + h->M, sizeof(double) * md, hipMemcpyDeviceToHost));
+  VCMI_HIP(hipMemcpy(var, h->params() + h->M + md, sizeof(double) * md, hipMemcpyDeviceToHost));
   return VCMI_OK;
 }
 

@@ -24,7 +24,7 @@ export DeviceMatrix, FrameByFrameConverter, TrajectoryConverter, GMMMapParam, GM
        align, align_mcep, push_delta, GVDataset, sp2mc, mc2sp, mc2b,
        DTW, fit!, update!, set_template!, backward,
        predict_proba, predict_proba!, predict, predict!, diffgmm,
-       estep_diag, estep_full, estep_set_path, estep_get_path, ESTEP_AUTO, ESTEP_HARD, ESTEP_SOFT, GMMEM, estep!, mstep!, params, KMeansState, kmeans_stats_len, kmeans_assign!, kmeans_update!, kmeans_far!,
+       estep_diag, estep_full, estep_set_path, estep_get_path, ESTEP_AUTO, ESTEP_HARD, ESTEP_SOFT, GMMEM, GMMEMDiag, estep!, mstep!, params, KMeansState, kmeans_stats_len, kmeans_assign!, kmeans_update!, kmeans_far!,
        kmeans_relocate!, kmeans_seed_commit!, kmeans_seed_pick, kmeans_seed_trials!, kmeans_mind2!, kmeans_restore_best!, kmeans_centers,
        kmeans!, set_devices, device_count, set_prune!, convert_plan, pin!, unpin!, ispinned
 
@@ -734,6 +734,42 @@ function params(em::GMMEM)
     w = Vector{Float64}(undef, em.M); μ = Matrix{Float64}(undef, em.Dj, em.M); Σ = Array{Float64,3}(undef, em.Dj, em.Dj, em.M)
     check(ccall((:vcmi_gmm_em_get, libvcmi), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}), em.h, w, μ, Σ))
     w, μ, Σ
+end
+
+# The diagonal twin (covariance_type="diag"): σ² is (Dj,M); `dstats` holds vcmi_estep_stats_len(Dj,M) doubles.
+mutable struct GMMEMDiag
+    h::Ptr{Cvoid}
+    Dj::Int
+    M::Int
+    function GMMEMDiag(w::Vector{Float64}, μ::Matrix{Float64}, σ²::Matrix{Float64}; min_covar::Float64=1.0e-7)
+        Dj, M = size(μ)
+        size(σ²) == (Dj, M) || throw(DimensionMismatch("σ² must be (Dj,M)"))
+        length(w) == M || throw(DimensionMismatch("w must have M entries"))
+        h = Ref{Ptr{Cvoid}}(C_NULL)
+        check(ccall((:vcmi_gmm_em_diag_create, libvcmi), Cint,
+                    (Cint, Cint, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Cdouble, Ref{Ptr{Cvoid}}),
+                    Dj, M, w, μ, σ², min_covar, h))
+        em = new(h[], Dj, M)
+        finalizer(e -> ccall((:vcmi_gmm_em_diag_destroy, libvcmi), Cint, (Ptr{Cvoid},), e.h), em)
+        em
+    end
+end
+
+estep!(em::GMMEMDiag, dX::Ptr{Float64}, N::Integer, dstats::Ptr{Float64}; stream::Ptr{Cvoid}=C_NULL) =
+    check(ccall((:vcmi_gmm_em_diag_estep_dev, libvcmi), Cint, (Ptr{Cvoid}, Ptr{Float64}, Int64, Ptr{Float64}, Ptr{Cvoid}),
+                em.h, dX, N, dstats, stream))
+
+function mstep!(em::GMMEMDiag, dstats::Ptr{Float64}; stream::Ptr{Cvoid}=C_NULL)
+    ll = Ref{Float64}(0.0)
+    check(ccall((:vcmi_gmm_em_diag_mstep, libvcmi), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Cvoid}, Ref{Float64}),
+                em.h, dstats, stream, ll))
+    ll[]
+end
+
+function params(em::GMMEMDiag)
+    w = Vector{Float64}(undef, em.M); μ = Matrix{Float64}(undef, em.Dj, em.M); σ² = Matrix{Float64}(undef, em.Dj, em.M)
+    check(ccall((:vcmi_gmm_em_diag_get, libvcmi), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}), em.h, w, μ, σ²))
+    w, μ, σ²
 end
 
 # ------------------------------------------------------------------------------------- device k-means

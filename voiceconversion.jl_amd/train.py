@@ -13,6 +13,11 @@ takes np.cov of all of X for every mixture.  Two initialisations are offered:
     on the CPU.
   * init="kmeans": sklearn's semantics on the device -- kmeans(X, M) over every frame of every rank (kmeans.py) and
     cov(X) + min_covar I (ddof=1) over every frame, from the M=1 full E-step statistics (N, sum x, sum x x').
+
+covariance_type="diag" runs the same loop on a diagonal model (DiagEMState, vcmi_gmm_em_diag_*): the statistics are the
+M(1+2Dj)+1 doubles of the diagonal E-step, the initial variances the diagonal of the data covariance + min_covar (what the
+old sklearn GMM takes for "diag") -- for init="kmeans" from the M=1 DIAGONAL E-step statistics (N, sum x, sum x^2), not
+the Dj^2 pass.  expand_diag turns its variances into the (Dj,Dj,M) tensor that refine= of the full fit takes.
 """
 import ctypes as C
 
@@ -20,7 +25,7 @@ import numpy as np
 
 from . import _lib
 from ._arrays import current_stream_ptr, dev_matrix, jl_matrix, jl_vector
-from .estep import estep_full_dev, full_stats_len, unpack_full_stats
+from .estep import estep_diag_dev, estep_full_dev, full_stats_len, stats_len, unpack_full_stats, unpack_stats
 from .kmeans import kmeans
 
 
@@ -70,6 +75,65 @@ class EMState:
         return w, mu, sigma
 
 
+class DiagEMState:
+    """Device-resident (w, mu, var) of a diagonal-covariance GMM (vcmi_gmm_em_diag_*): mu, var are (Dj,M)."""
+
+    def __init__(self, w, mu, var, min_covar=1e-7):
+        w = jl_vector(w)
+        mu = jl_matrix(mu, "mu")
+        var = np.asfortranarray(np.asarray(var, dtype=np.float64))
+        Dj, M = mu.shape
+        if var.shape != (Dj, M) or w.shape != (M,):
+            raise _lib.DimensionMismatch(f"w {w.shape}, mu {mu.shape}, var {var.shape} are inconsistent")
+        self.Dj, self.M = Dj, M
+        h = C.c_void_p()
+        _lib.check(_lib.lib.vcmi_gmm_em_diag_create(Dj, M, _lib.dptr(w), _lib.dptr(mu), _lib.dptr(var), float(min_covar), C.byref(h)))
+        self._h = h
+
+    def __del__(self, _destroy=_lib.lib.vcmi_gmm_em_diag_destroy):     # bound at definition: module globals may be gone at exit
+        h, self._h = getattr(self, "_h", None), None
+        if h:
+            _destroy(h)
+
+    def estep(self, X, out=None):
+        """Local statistics of the (Dj,N) device block X -> packed device tensor [S0 | S1 | S2 | loglik] (stats_len)."""
+        import torch
+
+        ptr, D, N, ld = dev_matrix(X, "X")
+        if D != self.Dj or (N > 1 and ld != self.Dj):
+            raise _lib.DimensionMismatch("X must be a dense (Dj,N) matrix matching the model dimension")
+        if out is None:
+            out = torch.empty(stats_len(self.Dj, self.M), dtype=torch.float64, device=X.device)
+        _lib.check(_lib.lib.vcmi_gmm_em_diag_estep_dev(self._h, ptr, N, out.data_ptr(), current_stream_ptr()))
+        return out
+
+    def mstep(self, stats):
+        """Parameters <- statistics (already summed over ranks); returns the log-likelihood they carry."""
+        ll = np.zeros(1)
+        _lib.check(_lib.lib.vcmi_gmm_em_diag_mstep(self._h, stats.data_ptr(), current_stream_ptr(), _lib.dptr(ll)))
+        return float(ll[0])
+
+    def get(self):
+        w = np.empty(self.M)
+        mu = np.empty((self.Dj, self.M), order="F")
+        var = np.empty((self.Dj, self.M), order="F")
+        _lib.check(_lib.lib.vcmi_gmm_em_diag_get(self._h, _lib.dptr(w), _lib.dptr(mu), _lib.dptr(var)))
+        return w, mu, var
+
+
+def expand_diag(covars):
+    """Variances (Dj,M) -> the (Dj,Dj,M) covariance tensor with them on the diagonals:
+    train_gmm(X, refine=(w, mu, expand_diag(var))) warm-starts the full-covariance fit from a diagonal one."""
+    v = np.asarray(covars, dtype=np.float64)
+    if v.ndim != 2:
+        raise _lib.DimensionMismatch(f"expand_diag: covars must be (Dj,M), got {v.shape}")
+    Dj, M = v.shape
+    out = np.zeros((Dj, Dj, M), order="F")
+    i = np.arange(Dj)
+    out[i, i, :] = v
+    return out
+
+
 def kmeans_init(Xs, M, rng, n_iter=10):
     """k-means++ seeding and a few Lloyd iterations on a host subsample Xs (n,Dj): means for init_params='wmc'."""
     n = Xs.shape[0]
@@ -104,8 +168,22 @@ def data_covariance(X, group=None):
     return 0.5 * (cv + cv.T)
 
 
+def data_variance(X, group=None):
+    """var(X) per dimension (ddof=1, the diagonal of np.cov) over every frame of every rank, from the M=1 diagonal E-step
+    statistics (N, sum x, sum x^2)."""
+    import torch.distributed as dist
+
+    Dj = X.shape[0]
+    st = estep_diag_dev(X, np.ones(1), np.zeros((Dj, 1)), np.ones((Dj, 1)))
+    if dist.is_available() and dist.is_initialized():
+        dist.all_reduce(st, group=group)
+    S0, S1, S2, _ = unpack_stats(st.cpu().numpy(), Dj, 1)
+    n, s1 = S0[0], S1[:, 0]
+    return (S2[:, 0] - s1 * s1 / n) / (n - 1.0)
+
+
 def train_gmm(X, n_components=16, n_iter=200, n_init=2, min_covar=1e-7, tol=1e-3, refine=None, seed=0, group=None,
-              init_sample=50000, init="subsample"):
+              init_sample=50000, init="subsample", covariance_type="full"):
     """train_gmm.jl's `gmm[:fit]`: X is this rank's (Dj,N) device-resident shard of the joint features.
 
     n_init random initialisations (k-means means, uniform weights, the data covariance + min_covar*I for every
@@ -115,14 +193,23 @@ def train_gmm(X, n_components=16, n_iter=200, n_init=2, min_covar=1e-7, tol=1e-3
     kmeans over every frame of every rank and the covariance of every frame (see the module docstring); the default
     "subsample" keeps the host-side subsample initialisation.
     Returns {"weights", "means" (Dj,M), "covars" (Dj,Dj,M), "n_components", "loglik" (per-frame history), "converged"}.
+    covariance_type="diag" fits a diagonal model by the same rules (module docstring): refine=(w, mu, var (Dj,M)), the
+    variances start from the diagonal of the data covariance + min_covar, "covars" is (Dj,M) and the result carries
+    "covariance_type": "diag".
     """
+    if covariance_type not in ("full", "diag"):
+        raise ValueError(f"train_gmm: covariance_type must be 'full' or 'diag', got {covariance_type!r}")
+    diag = covariance_type == "diag"
+    Dj, N = X.shape
+    M = int(n_components)
+    if diag and refine is not None and np.shape(refine[2]) != (Dj, M):
+        raise _lib.DimensionMismatch(f"train_gmm: covariance_type='diag' refines from variances ({Dj},{M}), got {np.shape(refine[2])}")
+
     import torch
     import torch.distributed as dist
 
     distributed = dist.is_available() and dist.is_initialized()
     rank = dist.get_rank(group) if distributed else 0
-    Dj, N = X.shape
-    M = int(n_components)
     ntot = torch.tensor([float(N)], dtype=torch.float64, device=X.device)
     if distributed:
         dist.all_reduce(ntot, group=group)
@@ -130,7 +217,13 @@ def train_gmm(X, n_components=16, n_iter=200, n_init=2, min_covar=1e-7, tol=1e-3
     if init not in ("subsample", "kmeans"):
         raise ValueError(f"train_gmm: init must be 'subsample' or 'kmeans', got {init!r}")
     rng = np.random.default_rng(seed)
-    cv_all = data_covariance(X, group) + min_covar * np.eye(Dj) if init == "kmeans" and refine is None else None
+    if init != "kmeans" or refine is not None:
+        cv_all = None
+    elif diag:
+        cv_all = data_variance(X, group) + min_covar
+    else:
+        cv_all = data_covariance(X, group) + min_covar * np.eye(Dj)
+    nsig = Dj if diag else Dj * Dj         # covariance entries per mixture
     best = None
     for _ in range(1 if refine is not None else max(1, int(n_init))):
         if refine is not None:
@@ -138,27 +231,30 @@ def train_gmm(X, n_components=16, n_iter=200, n_init=2, min_covar=1e-7, tol=1e-3
         elif init == "kmeans":
             # every rank runs the same collective k-means and gets the same centers: nothing to broadcast
             mu0 = kmeans(X, M, seed=int(rng.integers(2**31 - 1)), group=group)["centers"]
-            sig0 = np.repeat(cv_all[:, :, None], M, axis=2)
+            sig0 = np.repeat(cv_all[:, None], M, axis=1) if diag else np.repeat(cv_all[:, :, None], M, axis=2)
             w0 = np.full(M, 1.0 / M)
         else:
             # rank 0 draws the initial model from its shard and every rank receives the same one
-            pk = torch.empty(M * (1 + Dj + Dj * Dj), dtype=torch.float64, device=X.device)
+            pk = torch.empty(M * (1 + Dj + nsig), dtype=torch.float64, device=X.device)
             if rank == 0:
                 idx = rng.choice(N, size=min(N, int(init_sample)), replace=False)
                 Xs = X[:, torch.from_numpy(np.sort(idx)).to(X.device)].t().contiguous().cpu().numpy()
                 mu0 = kmeans_init(Xs, M, rng).T
-                cv = np.cov(Xs.T) + min_covar * np.eye(Dj)
-                sig0 = np.repeat(cv[:, :, None], M, axis=2)
+                if diag:
+                    sig0 = np.repeat((np.var(Xs, axis=0, ddof=1) + min_covar)[:, None], M, axis=1)
+                else:
+                    cv = np.cov(Xs.T) + min_covar * np.eye(Dj)
+                    sig0 = np.repeat(cv[:, :, None], M, axis=2)
                 w0 = np.full(M, 1.0 / M)
-                pk.copy_(torch.from_numpy(np.concatenate([w0, mu0.T.ravel(), np.transpose(sig0, (2, 1, 0)).ravel()])))
+                pk.copy_(torch.from_numpy(np.concatenate([w0, mu0.T.ravel(), sig0.T.ravel()])))
             if distributed:
                 dist.broadcast(pk, src=0, group=group)
             h = pk.cpu().numpy()
             w0 = h[:M].copy()
             mu0 = h[M:M + M * Dj].reshape(M, Dj).T
-            sig0 = np.transpose(h[M + M * Dj:].reshape(M, Dj, Dj), (2, 1, 0))
-        em = EMState(w0, mu0, sig0, min_covar)
-        stats = torch.empty(full_stats_len(Dj, M), dtype=torch.float64, device=X.device)
+            sig0 = h[M + M * Dj:].reshape(M, Dj).T if diag else np.transpose(h[M + M * Dj:].reshape(M, Dj, Dj), (2, 1, 0))
+        em = DiagEMState(w0, mu0, sig0, min_covar) if diag else EMState(w0, mu0, sig0, min_covar)
+        stats = torch.empty(stats_len(Dj, M) if diag else full_stats_len(Dj, M), dtype=torch.float64, device=X.device)
         hist, converged = [], False
         for _ in range(int(n_iter)):
             em.estep(X, out=stats)
@@ -171,7 +267,10 @@ def train_gmm(X, n_components=16, n_iter=200, n_init=2, min_covar=1e-7, tol=1e-3
         if best is None or hist[-1] > best[0]:
             best = (hist[-1], em.get(), hist, converged)
     (w, mu, sigma), hist, converged = best[1], best[2], best[3]
-    return {"weights": w, "means": mu, "covars": sigma, "n_components": M, "loglik": hist, "converged": converged}
+    out = {"weights": w, "means": mu, "covars": sigma, "n_components": M, "loglik": hist, "converged": converged}
+    if diag:
+        out["covariance_type"] = "diag"
+    return out
 
 
-__all__ = ["EMState", "train_gmm", "kmeans_init", "data_covariance", "unpack_full_stats"]
+__all__ = ["EMState", "DiagEMState", "train_gmm", "expand_diag", "kmeans_init", "data_covariance", "data_variance", "unpack_full_stats"]
