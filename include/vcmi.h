@@ -403,7 +403,9 @@ int vcmi_diffgmm(const double *mu, const double *sigma, int Dj, int M, double *m
  * align_mcep and the joint training matrix -- src/align.jl:38-55, src/datasets.jl:52-98
  * ------------------------------------------------------------------------------------------- */
 /* mc2e(mc, alpha, len) of MelGeneralizedCepstrums (third party; call site src/align.jl:48) for every column of
- * mc (D,T): energy of c2ir(freqt(mc, len-1, -alpha), len).  e (T). */
+ * mc (D,T): energy of c2ir(freqt(mc, len-1, -alpha), len).  e (T).  2 <= fftlen <= 9600 (a frame's two length-len
+ * vectors stay in the LDS; four frames per workgroup up to 2400, two up to 4800, one beyond); VCMI_ERR_ARG above that, here
+ * and in vcmi_align_mcep / vcmi_parallel_dataset_dev with silence removal. */
 int vcmi_mc2e(const double *mc, int D, int64_t T, double alpha, int fftlen, double *e);
 /* align_mcep(src, tgt, alpha, fftlen; threshold=-14.0, remove_silence=true): align, then keep the columns whose
  * log(mc2e(src)) exceeds the threshold.  src (D,S), tgt (D,T); src_out, newtgt_out (D, up to S); *ncols kept. */

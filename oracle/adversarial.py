@@ -334,3 +334,20 @@ def estep_sentinel_call(Dj, M, seed, tight=False, nbg=65_536, per_class=8, ratio
     X[~mask] = Xb
     return dict(w=w, mu=mu, var=var, X=np.ascontiguousarray(X), cls=c, gap=gg, sent=np.array(sent), owner=np.array(owners),
                 gaps=np.array(gaps), Mu=Mu, nb=nb)
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# Frames on the silence threshold of align_mcep (src/align.jl:47-52: keep a frame when log mc2e(src) > threshold)
+# ---------------------------------------------------------------------------------------------------------------
+def frames_at_energy_threshold(mc, alpha, fftlen, threshold, gaps):
+    """Moves every frame of mc (T,D) so that its log-energy lies `gaps[i]` above (positive) or below (negative) `threshold`.
+
+    A constant term is invariant under frequency warping, so adding a to c0 multiplies the impulse response by e^a and adds
+    exactly 2a to log mc2e: one step  c0 += (threshold + gap - log e) / 2  lands on the requested gap up to the rounding of
+    c0 and of the oracle's own evaluation.  The energies come from the C oracle only (the kernel under test is not asked).
+    Returns (mc' (T,D), achieved gaps (T,)) with the achieved gaps re-evaluated by the oracle on mc'."""
+    from . import c_oracle as co
+    mc = np.array(mc, dtype=np.float64, order="C")
+    gaps = np.resize(np.asarray(gaps, dtype=np.float64), len(mc))
+    mc[:, 0] += (threshold + gaps - np.log(co.mc2e(mc, alpha, fftlen))) / 2.0
+    return mc, np.log(co.mc2e(mc, alpha, fftlen)) - threshold

@@ -83,6 +83,78 @@ def test_gv_dataset_host_helper(vc, ignore0th, add_delta):
         vc.GVDataset([fms[0].T, fms[2][:, :5].T])
 
 
+@pytest.mark.parametrize("add_delta", [False, True])
+def test_gv_dataset_short_and_empty_utterances(vc, add_delta):
+    """lengths [2, 1, 0, 3, 1]: the one- and zero-frame utterances are skipped (their variance is NaN in the reference), the
+    others keep their order, every utterance counts as a phrase; nmax cuts the list BEFORE the skip rule applies"""
+    from oracle import np_oracle as npo
+    rng = np.random.default_rng(13)
+    fms = [rng.standard_normal((T, 6)) * (1 + i) for i, T in enumerate((2, 1, 0, 3, 1))]
+    ds = vc.GVDataset([f.T for f in fms], add_delta=add_delta)
+    ref = npo.gv_dataset(fms, add_delta=add_delta)
+    assert ds.totalphrases == 5 and ds.X.shape == ref.T.shape == (5 * (1 + add_delta), 2)
+    assert np.max(np.abs(ds.X - ref.T) / np.abs(ref.T)) < 1e-12
+    for k, i in enumerate((0, 3)):                                    # order: utterance 1, then utterance 4
+        assert np.allclose(ds.X[:5, k], np.var(fms[i][:, 1:], axis=0, ddof=1), rtol=1e-12, atol=0)
+    # nmax = 3 takes [2, 1, 0] and keeps one; skipping first and cutting afterwards would give [2, 3, .] -> two columns
+    cut = vc.GVDataset([f.T for f in fms], add_delta=add_delta, nmax=3)
+    assert cut.totalphrases == 3 and cut.X.shape[1] == 1 and np.array_equal(cut.X[:, 0], ds.X[:, 0])
+    assert vc.GVDataset([f.T for f in fms], add_delta=add_delta, nmax=4).X.shape[1] == 2
+
+
+def test_gv_dataset_constant_row_and_large_offset(vc):
+    """A row that is constant over the utterance has variance exactly 0.0 wherever the running sum of the row is exact (2.5 and
+    -3e8 over 7 frames; for a value like 0.1 the computed mean is not the value, in numpy's and Julia's var as well as here, and
+    the variance is ~1e-34 in all three).
+
+    Rows 1e8 + N(0,1), T = 500, against a two-pass variance in numpy.longdouble.  The bound: a double near 1e8 is rounded at
+    1e8 * eps = 2.2e-8, i.e. 2.2e-8 of the unit standard deviation.  A two-pass variance sees the offset only through the
+    computed mean m: sum (x - m)^2 = sum (x - mu)^2 + T (mu - m)^2, so an error of m enters squared (naive summation:
+    |mu - m| <= T u 1e8 = 5.5e-6, squared 3e-11), and x - m is exact (both within a factor 2); what is left is the
+    rounding of 500 squares and adds, ~T eps = 1e-13.  1e-7 relative leaves room for a few roundings at 1e8 entering at first
+    order, and nothing more: the one-pass formula sum x^2 - T m^2 cancels 1e16 against 1e16 +- 500 and loses every digit."""
+    rng = np.random.default_rng(14)
+    fm = rng.standard_normal((7, 4))
+    fm[:, 2] = 2.5
+    fm[:, 3] = -3.0e8
+    X = vc.GVDataset([fm.T], ignore0th=False).X
+    assert X[2, 0] == 0.0 and X[3, 0] == 0.0 and np.all(X[:2, 0] > 0)
+    Xd = vc.GVDataset([fm.T], ignore0th=False, add_delta=True).X     # delta row of a constant: 2.5 at both ends, 0 between
+    assert Xd[2, 0] == 0.0 and abs(Xd[6, 0] - 125 / 84) < 1e-14     # (2 (2.5 - 5/7)^2 + 5 (5/7)^2) / 6
+    big = 1e8 + rng.standard_normal((500, 5))
+    got = vc.GVDataset([big.T], ignore0th=False).X[:, 0]
+    xl = big.astype(np.longdouble)
+    ref = ((xl - xl.mean(axis=0)) ** 2).sum(axis=0) / 499
+    assert np.max(np.abs(got - ref) / ref) < 1e-7
+
+
+def test_gv_dataset_non_finite_values(vc):
+    """src/datasets.jl:163-179: an utterance whose variance has a NaN is SKIPPED (:164), and what was kept must be finite
+    (@assert, :179).  A NaN or an Inf among the frames makes the variance NaN (Inf - Inf in the deviations), so the reference
+    skips that utterance, in a one-frame utterance as in a long one; the assertion is reached by a variance that overflows."""
+    from oracle import np_oracle as npo
+    rng = np.random.default_rng(15)
+    good = [rng.standard_normal((T, 4)) for T in (9, 1, 12)]
+    want = npo.gv_dataset(good).T
+    for bad in (np.nan, np.inf, -np.inf):
+        fms = [g.copy() for g in good]
+        fms[1][0, 2] = bad                                           # in the one-frame utterance, which is skipped anyway
+        assert np.array_equal(vc.GVDataset([f.T for f in fms]).X, want)
+        fms[2][5, 2] = bad                                           # in a long one: its variance is NaN -> skipped as well
+        ds = vc.GVDataset([f.T for f in fms])
+        ref = npo.gv_dataset(fms).T
+        assert ds.totalphrases == 3 and ds.X.shape == ref.shape == (3, 1) and np.array_equal(ds.X, want[:, :1])
+    fms = [g.copy() for g in good]
+    fms[2][5, 2], fms[2][6, 2] = 1e200, -1e200                      # finite frames, variance +Inf: kept, then the @assert
+    with np.errstate(over="ignore"):
+        assert np.isinf(npo.gv_dataset(fms)[1, 1])
+    with pytest.raises(AssertionError):
+        vc.GVDataset([f.T for f in fms])
+    fms[1][0, 2] = 1e200                                             # one frame: nothing to overflow, skipped
+    fms[2] = good[2]
+    assert np.array_equal(vc.GVDataset([f.T for f in fms]).X, want)
+
+
 def test_push_delta_and_constructW_host_helpers(vc):
     from oracle import c_oracle as co
     rng = np.random.default_rng(1)

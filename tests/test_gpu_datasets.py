@@ -5,6 +5,8 @@ feature values are copies / exact halves, so the matrices are compared bit for b
 import numpy as np
 import pytest
 
+import dataset_cases as dc
+
 pytestmark = pytest.mark.gpu
 
 
@@ -17,10 +19,8 @@ def vc():
 
 def _mcep_pair(rng, S, T, D):
     """mel-cepstrum-like parallel utterances: decaying coefficients, c0 spread so that part of the frames is silence"""
-    src = rng.standard_normal((S, D)) * np.exp(-0.3 * np.arange(D)) * 0.3
-    src[:, 0] = rng.uniform(-9.0, 1.0, S)
-    idx = np.clip(np.sort(rng.integers(0, S, T)), 0, S - 1)
-    return src, src[idx] + 0.01 * rng.standard_normal((T, D))
+    src = dc.mcep(rng, S, D)
+    return src, dc.warped_copy(rng, src, T)
 
 
 def test_mc2e(vc):

@@ -246,6 +246,7 @@ DBG_SCREEN_FP64 = 33554432
 DBG_GROUP_KEY_FP64 = 67108864
 DBG_ESTEP_NO_HARD = 134217728
 DBG_ESTEP_NO_SMALL = 1024
+DBG_MC2E_TWO_WAVES, DBG_MC2E_ONE_WAVE = 268435456, 536870912
 
 
 def estep_last_soft():

@@ -25,7 +25,8 @@ int dtw_align_on_device(int64_t n, const double *const *src, const int64_t *S, c
                         int D, const double **d_feats, const double **d_newtgt, std::vector<int64_t> &src_off,
                         std::vector<int64_t> &nt_off);
 
-static constexpr int kMc2eWaves = 4;   // frames per workgroup pass
+static constexpr int kMc2eMaxLds = 150 * 1024;                    // dynamic LDS a workgroup of mc2e_kernel may ask for
+static constexpr int kMc2eMaxLen = kMc2eMaxLds / (2 * 8);         // one wave per workgroup: g and h of 9600 doubles
 
 __device__ __forceinline__ double wave_sum(double v) {
 #pragma unroll
@@ -34,14 +35,16 @@ __device__ __forceinline__ double wave_sum(double v) {
 }
 
 // mc: frames of D doubles at mc + frame_off[f]... here a dense (D,nfr) block; Ft: [D][len] (F transposed: row i = freqt of
-// unit vector i); e: (nfr)
-__global__ void __launch_bounds__(64 * kMc2eWaves)
+// unit vector i); e: (nfr).  WAVES frames per workgroup pass, each wave on its own frame with its own g / h slice: the
+// arithmetic of a frame does not depend on WAVES.
+template <int WAVES>
+__global__ void __launch_bounds__(64 * WAVES)
 mc2e_kernel(const double *__restrict__ mc, int D, int64_t nfr, const double *__restrict__ Ft, int len, double *__restrict__ e) {
   extern __shared__ double msm[];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   double *g = msm + (size_t)wave * 2 * len;   // k * g[k]
   double *h = g + len;
-  for (int64_t f = (int64_t)blockIdx.x * kMc2eWaves + wave; f < nfr; f += (int64_t)gridDim.x * kMc2eWaves) {
+  for (int64_t f = (int64_t)blockIdx.x * WAVES + wave; f < nfr; f += (int64_t)gridDim.x * WAVES) {
     const double *c = mc + (size_t)D * f;
     // freqt: g = F c
     double g0 = 0.0;
@@ -113,18 +116,28 @@ static int ensure_freqt(DatasetScratch &sc, int D, int len, double alpha) {
   return VCMI_OK;
 }
 
+template <int WAVES>
+static int mc2e_launch(const DatasetScratch &sc, const double *dmc, int D, int64_t nfr, int len, double *de, hipStream_t st) {
+  const size_t shmem = (size_t)WAVES * 2 * len * sizeof(double);
+  VCMI_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(mc2e_kernel<WAVES>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                               (int)shmem));
+  const int64_t blocks = std::min<int64_t>((nfr + WAVES - 1) / WAVES, 256 * 8);
+  hipLaunchKernelGGL(mc2e_kernel<WAVES>, dim3((unsigned)blocks), dim3(64 * WAVES), shmem, st, dmc, D, nfr, sc.Ft.p, len, de);
+  VCMI_HIP(hipGetLastError());
+  return VCMI_OK;
+}
+
+// frames per workgroup from what fits into the LDS: 4 waves up to len 2400, 2 up to 4800, 1 up to 9600
 static int mc2e_device(DatasetScratch &sc, const double *dmc, int D, int64_t nfr, double alpha, int len, double *de,
                        hipStream_t st) {
   if (nfr == 0) return VCMI_OK;
+  if (len > kMc2eMaxLen) return fail(VCMI_ERR_ARG, "mc2e: fft length %d too large (at most %d)", len, kMc2eMaxLen);
   VCMI_TRY(ensure_freqt(sc, D, len, alpha));
-  const size_t shmem = (size_t)kMc2eWaves * 2 * len * sizeof(double);
-  if (shmem > 150 * 1024) return fail(VCMI_ERR_ARG, "mc2e: fft length %d too large", len);
-  VCMI_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(mc2e_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                               (int)shmem));
-  const int64_t blocks = std::min<int64_t>((nfr + kMc2eWaves - 1) / kMc2eWaves, 256 * 8);
-  hipLaunchKernelGGL(mc2e_kernel, dim3((unsigned)blocks), dim3(64 * kMc2eWaves), shmem, st, dmc, D, nfr, sc.Ft.p, len, de);
-  VCMI_HIP(hipGetLastError());
-  return VCMI_OK;
+  int waves = debug_flag(kDbgMc2eOneWave) ? 1 : debug_flag(kDbgMc2eTwoWaves) ? 2 : 4;
+  while ((size_t)waves * 2 * len * sizeof(double) > (size_t)kMc2eMaxLds) waves >>= 1;
+  if (waves == 4) return mc2e_launch<4>(sc, dmc, D, nfr, len, de, st);
+  if (waves == 2) return mc2e_launch<2>(sc, dmc, D, nfr, len, de, st);
+  return mc2e_launch<1>(sc, dmc, D, nfr, len, de, st);
 }
 
 // per pair: kept source columns in increasing order -> idx[idx_off + k], count -> cnt[p]
@@ -220,9 +233,12 @@ extern "C" int vcmi_parallel_dataset_dev(int64_t n, const double *const *src, co
   if (n < 0 || !nframes) return fail(VCMI_ERR_ARG, "vcmi_parallel_dataset_dev: bad argument");
   *nframes = 0;
   if (n == 0) return VCMI_OK;
-  if (!src || !S || !tgt || !T || !dXY) return fail(VCMI_ERR_ARG, "vcmi_parallel_dataset_dev: NULL argument");
+  // the dimension first: with Dj = 0 a caller's output buffer is empty, and an empty device allocation may be a null pointer
   if (D < 1 + (ignore0th ? 1 : 0)) return fail(VCMI_ERR_DIM, "vcmi_parallel_dataset_dev: feature dimension %d too small", D);
+  if (!src || !S || !tgt || !T || !dXY) return fail(VCMI_ERR_ARG, "vcmi_parallel_dataset_dev: NULL argument");
   if (remove_silence && fftlen < 2) return fail(VCMI_ERR_ARG, "vcmi_parallel_dataset_dev: fft length %d invalid", fftlen);
+  if (remove_silence && fftlen > kMc2eMaxLen)   // before the alignment runs, not after it
+    return fail(VCMI_ERR_ARG, "vcmi_parallel_dataset_dev: fft length %d too large (at most %d)", fftlen, kMc2eMaxLen);
   int64_t total = 0;
   for (int64_t p = 0; p < n; ++p) {
     if (S[p] < 1 || T[p] < 1 || S[p] > INT32_MAX) return fail(VCMI_ERR_DIM, "vcmi_parallel_dataset_dev: empty utterance");
