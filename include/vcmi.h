@@ -104,7 +104,11 @@ int vcmi_gmmmap_convert_dev(vcmi_gmmmap *g, const double *dX, int64_t ldx, int64
 int vcmi_vc_frames(vcmi_gmmmap *g, const double *fm, int64_t T, double *out);
 /* ... with the VarianceScaling post-filter (src/gv.jl:10-15) as a fused post step: out[2:end,:] = fvpostf(VarianceScaling(sigma2),
  * vc(g, fm)[2:end,:]); sigma2 (D) host vector, NULL = plain vcmi_vc_frames.  The converted matrix never leaves HBM between the
- * conversion and the filter: one upload, one download. */
+ * conversion and the filter: one upload, one download.  Runs on the calling thread's device (the filter's
+ * statistics are over the whole matrix).  Device scratch: fm and the result, 2 (D+1) T doubles in the per-thread staging matrix
+ * the vcmi_vc_traj_static family uses, grow-only and freed on return above 256 MiB (see there).  The threshold counts that
+ * family's converter input and result on this thread too: when the sum is above it, the call ends with a device-wide wait
+ * (hipDeviceSynchronize) and frees all three, also after a small matrix. */
 int vcmi_vc_frames_postf(vcmi_gmmmap *g, const double *fm, int64_t T, const double *sigma2, double *out);
 /* predict_proba(g.px, X) -> P (M,T), src/gmm.jl:24-41 */
 int vcmi_gmmmap_posterior(vcmi_gmmmap *g, const double *X, int64_t ldx, int64_t T, double *P);
@@ -340,7 +344,10 @@ int vcmi_push_delta(const double *src, int D, int64_t T, double *out);
 int vcmi_push_delta_dev(const double *dsrc, int64_t lds, int D, int64_t T, double *dout, int64_t ldo, void *stream);
 /* vc(c::TrajectoryConverter, fm) with the VarianceScaling post-filter (src/gv.jl:10-15) applied to the converted rows
  * 2..D+1 BEFORE the download: out[2:end,:] = fvpostf(VarianceScaling(sigma2), vc(t, fm)[2:end,:]); sigma2 (D) host vector,
- * NULL = plain vcmi_vc_traj.  One upload, one download; everything in between stays in HBM. */
+ * NULL = plain vcmi_vc_traj.  One upload, one download; everything in between stays in HBM.  With sigma2 this is
+ * vcmi_vc_traj_static's routine on the (2D+1,T) matrix: its rules (T = 0, T < 2, length(t), device) and its scratch, (6D+2) T
+ * doubles here -- converter input, result, and the staging matrix with the (D+1,T) result behind fm -- freed on return above
+ * 256 MiB. */
 int vcmi_vc_traj_postf(vcmi_traj *t, const double *fm, int64_t T, const double *sigma2, double *out);
 /* bin/vc.jl:75-82 in one call: fm (D+1,T) STATIC features, row 1 power.
  * X = [fm[1,:]; push_delta(fm[2:end,:])] over the WHOLE matrix (bin/vc.jl:77-78), then vc(t, X) in chunks of length(t)
@@ -353,10 +360,10 @@ int vcmi_vc_traj_postf(vcmi_traj *t, const double *fm, int64_t T, const double *
  * This entry and the three that follow run on the calling thread's device: the device group of vcmi_set_devices is not used.
  * Device scratch of the four, per thread and grow-only: the converter input (2D,T) and the result (D,T); the host-pointer
  * entries add one staging matrix for fm, in which static input is converted IN PLACE (out has the shape of fm: the power row
- * never moves) -- (4D+1) T doubles for this entry, where vcmi_vc_traj_postf holds (6D+2) T; vcmi_vc_trajgv with
- * is_static = 0 keeps its (D+1,T) result behind the (2D+1,T) input: (6D+2) T.  A host-pointer entry frees the three buffers
- * on return when together they exceed 256 MiB (kVcTrajScratchKeepBytes, csrc/traj.hip).  The converter handle's own per-frame
- * workspace is that of vcmi_traj_convert_batch_dev. */
+ * never moves) -- (4D+1) T doubles for this entry; vcmi_vc_traj_postf and vcmi_vc_trajgv with is_static = 0 keep their
+ * (D+1,T) result behind the (2D+1,T) input: (6D+2) T.  A host-pointer entry frees the three buffers on return when together
+ * they exceed 256 MiB (kVcScratchKeepBytes, csrc/postf.hpp).  The converter handle's own per-frame workspace is that of
+ * vcmi_traj_convert_batch_dev. */
 int vcmi_vc_traj_static(vcmi_traj *t, const double *fm, int64_t T, const double *sigma2, double *out);
 /* the same on DEVICE-RESIDENT matrices with leading dimensions (ldf >= the row count of dfm, ldo >= D+1; below:
  * VCMI_ERR_ARG), asynchronous on `stream` up to the status read that vcmi_traj_convert_batch_dev already does; dout must not
@@ -390,7 +397,8 @@ int vcmi_vc_trajgv(vcmi_trajgv *h, const double *fm, int64_t T, int is_static, i
 int vcmi_vc_trajgv_dev(vcmi_trajgv *h, const double *dfm, int64_t ldf, int64_t T, int is_static, int epochs,
                        double alpha, const double *sigma2, double *dout, int64_t ldo, void *stream);
 
-/* fvpostf(vs::VarianceScaling, src) -- src/gv.jl:10-21.  src, out (D,T), sigma2 (D); out may alias src. */
+/* fvpostf(vs::VarianceScaling, src) -- src/gv.jl:10-21.  src, out (D,T), sigma2 (D); out may alias src.  D T doubles in the
+ * same per-thread staging matrix, under the same rule (device-wide wait and release included). */
 int vcmi_variance_scaling(const double *src, int D, int64_t T, const double *sigma2, double *out);
 /* fvpostf! on a DEVICE-RESIDENT matrix (leading dimensions lds, ldo >= D; dout may be dsrc: in place), asynchronous on
  * `stream`; sigma2 (D) is a host vector.  Deterministic: every sum has a fixed order. */

@@ -106,3 +106,133 @@ def test_trajectory_vc_with_the_post_filter(vc, T, L):
     ref = ref_tj.vc(np.ascontiguousarray(fm.T), L)            # (T, Ds + 1)
     assert relerr(plain, ref.T) < 1e-6
     assert relerr(out[1:], co.variance_scaling(np.ascontiguousarray(ref[:, 1:]), s2).T) < 1e-6
+
+
+# ---- one routine behind the doors: vcmi_vc_traj_postf, vcmi_vc_traj_dev, vcmi_vc_frames_postf and the filter they share ----
+_DS, _M = 12, 4
+_CASES = [(260, 100), (101, 100), (2, 100)]          # (101, 100): a one-frame last chunk; (2, 100): the smallest matrix with a variance
+
+
+@pytest.fixture(scope="module")
+def traj_model():
+    from oracle import np_oracle as npo
+    return npo.synth_model(311, 4 * _DS, _M, lam_lo=1e-3)
+
+
+def _traj_input(vc, model, T):
+    """(2 Ds + 1, T) host matrix [power; static; delta] and sigma2 (Ds) of test_trajectory_vc_with_the_post_filter"""
+    from oracle import np_oracle as npo
+    w, mu, sig = model
+    st = np.cumsum(npo.sample_frames(32, w, mu, sig, T, 0, _DS), axis=0) / np.sqrt(np.arange(1, T + 1))[:, None]
+    fm = np.asfortranarray(np.vstack([np.linspace(0, 1, T)[None], vc.push_delta(np.asfortranarray(st.T))]))
+    return fm, np.random.default_rng(2).uniform(0.5, 2.0, _DS)
+
+
+def _new_traj(vc, model, L):
+    return vc.TrajectoryGMMMap(vc.GMMMap(*julia_model(*model)), L)
+
+
+def _vc_traj_dev(tj, fm, s2):
+    """vcmi_vc_traj_dev(is_static = 0) on a device copy of the host matrix fm -> (T, Ds + 1) device tensor"""
+    import torch
+    from voiceconversion_jl_amd import _lib
+    rows, T = fm.shape
+    d = torch.from_numpy(np.ascontiguousarray(fm.T)).cuda()
+    out = torch.full((T, _DS + 1), -7.0, dtype=torch.float64, device="cuda")
+    _lib.check(_lib.lib.vcmi_vc_traj_dev(tj._h, d.data_ptr(), rows, T, 0, None if s2 is None else _lib.dptr(s2), out.data_ptr(),
+                                         _DS + 1, torch.cuda.current_stream().cuda_stream))
+    return out
+
+
+def _scale_rows_in_place(buf, D, s2):
+    """vcmi_variance_scaling_dev in place on rows 2..D+1 of the (T, D + 1) device tensor buf (leading dimension D + 1)"""
+    import torch
+    from voiceconversion_jl_amd import _lib
+    p = buf.data_ptr() + 8
+    _lib.check(_lib.lib.vcmi_variance_scaling_dev(p, D + 1, D, buf.shape[0], _lib.dptr(s2), p, D + 1,
+                                                  torch.cuda.current_stream().cuda_stream))
+
+
+@pytest.mark.parametrize("T,L", _CASES)
+def test_postf_and_dev_entries_give_the_same_bits(vc, traj_model, T, L):
+    """vcmi_vc_traj_postf on a host matrix and vcmi_vc_traj_dev(is_static = 0, sigma2) on a device copy of it are one routine:
+    equal bit for bit, and each leaves length(t) at the last chunk's length."""
+    from voiceconversion_jl_amd import _lib
+    fm, s2 = _traj_input(vc, traj_model, T)
+    tj = _new_traj(vc, traj_model, L)
+    host = np.full((_DS + 1, T), -7.0, order="F")
+    _lib.check(_lib.lib.vcmi_vc_traj_postf(tj._h, _lib.dptr(fm), T, _lib.dptr(s2), _lib.dptr(host)))
+    assert len(tj) == (T - 1) % L + 1
+    tj2 = _new_traj(vc, traj_model, L)
+    dev = _vc_traj_dev(tj2, fm, s2).cpu().numpy().T
+    assert len(tj2) == (T - 1) % L + 1
+    assert np.array_equal(host[0], fm[0]) and np.array_equal(host, dev)
+
+
+@pytest.mark.parametrize("T,L", _CASES)
+def test_the_filter_of_vc_is_variance_scaling_in_place(vc, traj_model, T, L):
+    """Rows 2..D+1 of vcmi_vc_traj_dev(sigma2) == vcmi_variance_scaling_dev, in place, on rows 2..D+1 of
+    vcmi_vc_traj_dev(NULL) from a fresh converter, bit for bit: one scale kernel, into an offset output and in place."""
+    fm, s2 = _traj_input(vc, traj_model, T)
+    filtered = _vc_traj_dev(_new_traj(vc, traj_model, L), fm, s2).cpu().numpy()
+    plain = _vc_traj_dev(_new_traj(vc, traj_model, L), fm, None)
+    power = plain[:, 0].clone()
+    _scale_rows_in_place(plain, _DS, s2)
+    assert np.array_equal(plain[:, 0].cpu().numpy(), power.cpu().numpy()) and np.array_equal(power.cpu().numpy(), fm[0])
+    assert np.array_equal(filtered, plain.cpu().numpy())
+
+
+@pytest.mark.parametrize("T", [2, 5000])
+def test_frames_vc_with_the_post_filter_bit_for_bit(vc, fixture_model, T):
+    """vc(g, fm, postfilter): the power row is the input's, rows 2..D+1 are vcmi_variance_scaling_dev in place over
+    vcmi_gmmmap_convert_dev of the same matrix on the device with leading dimension D+1, bit for bit."""
+    import torch
+    from oracle import np_oracle as npo
+    from voiceconversion_jl_amd import _lib
+    w, mu, sig = fixture_model
+    D = 40
+    X = npo.sample_frames(31, w, mu, sig, T, 0, D)
+    fm = np.asfortranarray(np.vstack([np.arange(T, dtype=np.float64)[None], X.T]))
+    s2 = np.random.default_rng(1).uniform(0.5, 2.0, D)
+    g = vc.GMMMap(*julia_model(w, mu, sig))
+    out = vc.vc(g, fm, postfilter=vc.VarianceScaling(s2))
+    assert out.shape == (D + 1, T) and np.array_equal(out[0], fm[0])
+    d = torch.from_numpy(np.ascontiguousarray(fm.T)).cuda()                       # (T, D+1)
+    ref = torch.full((T, D + 1), -7.0, dtype=torch.float64, device="cuda")
+    _lib.check(_lib.lib.vcmi_gmmmap_convert_dev(g._h, d.data_ptr() + 8, D + 1, T, ref.data_ptr() + 8, D + 1,
+                                                torch.cuda.current_stream().cuda_stream))
+    _scale_rows_in_place(ref, D, s2)
+    assert np.array_equal(out[1:], ref[:, 1:].cpu().numpy().T)
+
+
+def test_post_filter_errors_leave_the_handle_usable(vc, traj_model):
+    """The errors of vc with a post-filter, each followed by a valid call on the same handle that gives the bits of a call on
+    a fresh one.  The model of test_not_positive_definite_normal_matrix (tests/test_gpu_trajectory.py) has no input it converts:
+    after its error through vcmi_vc_traj_postf `out` holds its fill pattern, length(t) is unchanged, the handle reports the
+    same error again, and a good converter on the same thread (the same device scratch) still gives its bits."""
+    from voiceconversion_jl_amd import _lib
+    T, L = 260, 100
+    fm, s2 = _traj_input(vc, traj_model, T)
+    vs = vc.VarianceScaling(s2)
+    want = vc.vc(_new_traj(vc, traj_model, L), fm, postfilter=vs)
+    tj = _new_traj(vc, traj_model, L)
+    with pytest.raises(vc.DimensionMismatch):
+        vc.vc(tj, fm[:, :1], postfilter=vs)                    # the variance of one frame is undefined
+    assert len(tj) == L and np.array_equal(vc.vc(tj, fm, postfilter=vs), want)
+    tj = _new_traj(vc, traj_model, L)
+    with pytest.raises(vc.DimensionMismatch):
+        vc.vc(tj, fm, postfilter=vc.VarianceScaling(s2[:-1]))
+    assert len(tj) == L and np.array_equal(vc.vc(tj, fm, postfilter=vs), want)
+
+    D, M, Tb = 12, 2, 9
+    rng = np.random.default_rng(3)
+    I = np.eye(2 * D)
+    bad = vc.TrajectoryGMMMap(vc.GMMMap(*julia_model(np.array([0.5, 0.5]), rng.standard_normal((M, 4 * D)),
+                                                     np.stack([np.block([[I, 2.0 * I], [2.0 * I, I]])] * M))), 5)
+    fb = np.asfortranarray(rng.standard_normal((2 * D + 1, Tb)))
+    out = np.full((D + 1, Tb), -7.0, order="F")
+    for _ in range(2):
+        with pytest.raises(vc.PosDefException):
+            _lib.check(_lib.lib.vcmi_vc_traj_postf(bad._h, _lib.dptr(fb), Tb, _lib.dptr(s2), _lib.dptr(out)))
+        assert np.all(out == -7.0) and len(bad) == 5          # (a success would leave 4, the last chunk)
+    assert np.array_equal(vc.vc(_new_traj(vc, traj_model, L), fm, postfilter=vs), want)

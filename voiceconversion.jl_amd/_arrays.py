@@ -7,6 +7,8 @@ device with the same logical shape (D, T) and unit stride along D (e.g. `buf.vie
 """
 import numpy as np
 
+from . import _lib
+
 
 def jl_matrix(a, name="array"):
     a = np.asarray(a)
@@ -44,3 +46,12 @@ def current_stream_ptr():
     import torch
 
     return torch.cuda.current_stream().cuda_stream
+
+
+def sigma2_arg(postfilter, D):
+    """The sigma2 argument of the vc entries: NULL without a post-filter."""
+    if postfilter is None:
+        return None
+    if postfilter.sigma2.shape != (D,):
+        raise _lib.DimensionMismatch("sigma2 must have one entry per converted feature row")
+    return _lib.dptr(postfilter.sigma2)

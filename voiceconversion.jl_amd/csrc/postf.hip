@@ -4,9 +4,11 @@
 //   vcmi_push_delta / _dev           [src; delta]: delta_t = (x_{t+1} - x_{t-1}) / 2 for 2 <= t <= T-1, the static value at t = 1, T
 //   vcmi_variance_scaling / _dev     per row sqrt(sigma2 / var) (x - mean) + mean, Julia's corrected variance, in place allowed
 //   vcmi_vc_frames_postf             vc(g::GMMMap, fm) with fvpostf! applied to the converted rows before the download
-//   vc_traj_pre_kernel / vc_traj_post_kernel   the two ends of vc(c::TrajectoryConverter, fm) from static features or on device
-//                                    matrices (vcmi_vc_traj_static, vcmi_vc_traj_dev, vcmi_vc_trajgv, vcmi_vc_trajgv_dev in traj.hip)
-// (vcmi_vc_traj_postf lives in traj.hip beside vcmi_vc_traj.)  Everything is HBM-bound streaming: a frame is D contiguous
+//   vc_traj_pre_device / vc_traj_post_device   the two ends of vc(c::TrajectoryConverter, fm) around the chunk conversions
+//                                    (vc_traj_device in traj.hip: vcmi_vc_traj_postf, vcmi_vc_traj_static, vcmi_vc_trajgv, *_dev)
+// One kernel, vs_scale_kernel, holds fvpostf!'s scale: variance_scaling_device runs it in place or into another matrix,
+// vc_traj_post_device into rows 2..D+1 of vc's result.  The host-pointer entries stage whole matrices in the per-thread
+// VcScratch (postf.hpp), freed on return above kVcScratchKeepBytes.  Everything is HBM-bound streaming: a frame is D contiguous
 // doubles, lanes run along the features of consecutive frames (coalesced), every reduction has a fixed order.
 #include "postf.hpp"
 #include "gmmmap_handle.hpp"
@@ -74,15 +76,19 @@ vs_final_kernel(const double *__restrict__ part, int nchunks, int D, double deno
   stat[d] = a / denom;
 }
 
-// (src and out may be the same matrix: every element is read and written by the same thread)
+// src (D,T) -> out (D,T), each with its leading dimension; FILTER: through fvpostf!'s scale (src/gv.jl:13) with
+// stat = [mean | var | sigma2] of variance_scaling_stats_device, else a copy.  (src and out may be the same matrix: every
+// element is read and written by the same thread, hence no __restrict__ on the two.)
+template <bool FILTER>
 __global__ void __launch_bounds__(256)
-vs_scale_kernel(const double *src, int64_t lds, int D, int64_t T, const double *__restrict__ sigma2, const double *__restrict__ mean,
-                const double *__restrict__ var, double *out, int64_t ldo) {
+vs_scale_kernel(const double *src, int64_t lds, int D, int64_t T, const double *__restrict__ stat, double *out, int64_t ldo) {
+  const double *mean = stat, *var = stat + kVsStatStride, *sigma2 = stat + 2 * kVsStatStride;
   const int64_t n = (int64_t)D * T;
   for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < n; e += (int64_t)gridDim.x * 256) {
     const int64_t t = e / D;
     const int d = (int)(e - t * D);
-    out[t * ldo + d] = sqrt(sigma2[d] / var[d]) * (src[t * lds + d] - mean[d]) + mean[d];
+    const double x = src[t * lds + d];
+    out[t * ldo + d] = FILTER ? sqrt(sigma2[d] / var[d]) * (x - mean[d]) + mean[d] : x;
   }
 }
 
@@ -124,29 +130,9 @@ int variance_scaling_device(const double *dsrc, int64_t lds, int D, int64_t T, c
                             int64_t ldo, hipStream_t st) {
   const double *stat = nullptr;
   VCMI_TRY(variance_scaling_stats_device(dsrc, lds, D, T, sigma2_host, &stat, st));
-  hipLaunchKernelGGL(vs_scale_kernel, dim3(2048), dim3(256), 0, st, dsrc, lds, D, T, stat + 2 * kVsStatStride, stat,
-                     stat + kVsStatStride, dout, ldo);
+  hipLaunchKernelGGL(vs_scale_kernel<true>, dim3(2048), dim3(256), 0, st, dsrc, lds, D, T, stat, dout, ldo);
   VCMI_HIP(hipGetLastError());
   return variance_scaling_stats_leave(st);
-}
-
-__global__ void __launch_bounds__(256)
-copy_rows_kernel(const double *__restrict__ in, int64_t ldi, int r0, int nrows, int64_t T, double *__restrict__ out, int64_t ldo, int q0) {
-  const int64_t n = (int64_t)nrows * T;
-  for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < n; e += (int64_t)gridDim.x * 256) {
-    const int64_t t = e / nrows;
-    const int r = (int)(e - t * nrows);
-    out[t * ldo + q0 + r] = in[t * ldi + r0 + r];
-  }
-}
-
-int copy_rows_device(const double *din, int64_t ldi, int r0, int nrows, int64_t T, double *dout, int64_t ldo, int q0, hipStream_t st) {
-  if (T == 0 || nrows == 0) return VCMI_OK;
-  const int64_t n = (int64_t)nrows * T;
-  hipLaunchKernelGGL(copy_rows_kernel, dim3((unsigned)std::min<int64_t>((n + 255) / 256, 8192)), dim3(256), 0, st, din, ldi, r0, nrows, T,
-                     dout, ldo, q0);
-  VCMI_HIP(hipGetLastError());
-  return VCMI_OK;
 }
 
 // ---- the two ends of vc(c::TrajectoryConverter, fm) around the chunk conversions, bin/vc.jl:75-82 + src/common.jl:31-63 ------
@@ -187,37 +173,19 @@ int vc_traj_pre_device(const double *dfm, int64_t ldf, int D, int64_t T, bool is
   return VCMI_OK;
 }
 
-// vc_traj_post_kernel: y (D,T) dense -> rows 2..D+1 of out (leading dimension ldo); FILTER: through fvpostf!'s scale
-// (src/gv.jl:13) with stat = [mean | var | sigma2] of variance_scaling_stats_device, the expression of vs_scale_kernel
-template <bool FILTER>
-__global__ void __launch_bounds__(256)
-vc_traj_post_kernel(const double *__restrict__ y, int D, int64_t T, const double *__restrict__ stat, double *__restrict__ out,
-                    int64_t ldo) {
-  const double *mean = stat, *var = stat + kVsStatStride, *sigma2 = stat + 2 * kVsStatStride;
-  const int64_t n = (int64_t)D * T;
-  for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < n; e += (int64_t)gridDim.x * 256) {
-    const int64_t t = e / D;
-    const int d = (int)(e - t * D);
-    out[t * ldo + 1 + d] = FILTER ? sqrt(sigma2[d] / var[d]) * (y[t * D + d] - mean[d]) + mean[d] : y[e];
-  }
-}
-
+// y (D,T) dense -> rows 2..D+1 of out (leading dimension ldo), through fvpostf!'s scale when dstat is given
 int vc_traj_post_device(const double *dy, int D, int64_t T, const double *dstat, double *dout, int64_t ldo, hipStream_t st) {
   if (T == 0) return VCMI_OK;
   const int64_t n = (int64_t)D * T;
   const dim3 grid((unsigned)std::min<int64_t>((n + 255) / 256, 8192));
-  if (dstat) hipLaunchKernelGGL(vc_traj_post_kernel<true>, grid, dim3(256), 0, st, dy, D, T, dstat, dout, ldo);
-  else hipLaunchKernelGGL(vc_traj_post_kernel<false>, grid, dim3(256), 0, st, dy, D, T, dstat, dout, ldo);
+  if (dstat) hipLaunchKernelGGL(vs_scale_kernel<true>, grid, dim3(256), 0, st, dy, (int64_t)D, D, T, dstat, dout + 1, ldo);
+  else hipLaunchKernelGGL(vs_scale_kernel<false>, grid, dim3(256), 0, st, dy, (int64_t)D, D, T, dstat, dout + 1, ldo);
   VCMI_HIP(hipGetLastError());
   return VCMI_OK;
 }
 
-// whole-matrix device buffers of the host-pointer entries below (grow-only, per thread)
-struct PostfHostScratch {
-  DevBuf<double> in, out;
-};
-static PostfHostScratch &host_scratch() {
-  static thread_local PostfHostScratch s;
+VcScratch &vc_scratch() {
+  static thread_local VcScratch s;
   return s;
 }
 
@@ -262,11 +230,12 @@ extern "C" int vcmi_variance_scaling(const double *src, int D, int64_t T, const 
   if (D < 1 || D > 256 || T < 2)
     return fail(VCMI_ERR_DIM, "vcmi_variance_scaling: D=%d T=%lld unsupported (needs 1 <= D <= 256, T >= 2)", D, (long long)T);
   VCMI_TRY(check_device());
-  PostfHostScratch &hs = host_scratch();
-  VCMI_TRY(hs.in.reserve((size_t)D * T));
-  VCMI_TRY(staged_upload(hs.in.p, src, sizeof(double) * D * T, nullptr));
-  VCMI_TRY(variance_scaling_device(hs.in.p, D, D, T, sigma2, hs.in.p, D, nullptr));
-  return staged_download(out, hs.in.p, sizeof(double) * D * T, nullptr);
+  VcScratch &sc = vc_scratch();
+  VcScratch::Release release{sc};
+  VCMI_TRY(sc.stage.reserve((size_t)D * T));
+  VCMI_TRY(staged_upload(sc.stage.p, src, sizeof(double) * D * T, nullptr));
+  VCMI_TRY(variance_scaling_device(sc.stage.p, D, D, T, sigma2, sc.stage.p, D, nullptr));
+  return staged_download(out, sc.stage.p, sizeof(double) * D * T, nullptr);
 }
 
 // vc(g::GMMMap, fm) followed by fvpostf!(VarianceScaling(sigma2), converted[2:end, :]) -- src/common.jl:7-26, src/gv.jl:10-15:
@@ -282,12 +251,14 @@ extern "C" int vcmi_vc_frames_postf(vcmi_gmmmap *g, const double *fm, int64_t T,
   VCMI_TRY(check_device());
   const int64_t ld = g->D + 1;
   const size_t bytes = sizeof(double) * (size_t)ld * T;
-  PostfHostScratch &hs = host_scratch();
-  VCMI_TRY(hs.in.reserve((size_t)ld * T));
-  VCMI_TRY(hs.out.reserve((size_t)ld * T));
-  VCMI_TRY(staged_upload(hs.in.p, fm, bytes, nullptr));
-  VCMI_TRY(copy_rows_device(hs.in.p, ld, 0, 1, T, hs.out.p, ld, 0, nullptr));                       // power row kept, src/common.jl:23
-  VCMI_TRY(gmmmap_convert_device(g, hs.in.p + 1, ld, T, hs.out.p + 1, ld, nullptr));
-  VCMI_TRY(variance_scaling_device(hs.out.p + 1, ld, g->D, T, sigma2, hs.out.p + 1, ld, nullptr));
-  return staged_download(out, hs.out.p, bytes, nullptr);
+  VcScratch &sc = vc_scratch();
+  VcScratch::Release release{sc};
+  VCMI_TRY(sc.stage.reserve((size_t)2 * ld * T));                    // fm, and the result behind it
+  double *din = sc.stage.p, *dout = sc.stage.p + (size_t)ld * T;
+  VCMI_TRY(staged_upload(din, fm, bytes, nullptr));
+  // the copy keeps row 1 (src/common.jl:23); the kernel then overwrites rows 2..D+1, as in vcmi_vc_frames
+  VCMI_HIP(hipMemcpyAsync(dout, din, bytes, hipMemcpyDeviceToDevice, nullptr));
+  VCMI_TRY(gmmmap_convert_device(g, din + 1, ld, T, dout + 1, ld, nullptr));
+  VCMI_TRY(variance_scaling_device(dout + 1, ld, g->D, T, sigma2, dout + 1, ld, nullptr));
+  return staged_download(out, dout, bytes, nullptr);
 }

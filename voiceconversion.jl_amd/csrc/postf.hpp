@@ -1,6 +1,7 @@
 // postf.hpp -- the pre / post steps of vc on DEVICE-RESIDENT matrices: push_delta (src/datasets.jl:6-13)
-// and the VarianceScaling post-filter (src/gv.jl:10-15), shared by postf.hip (C entries) and traj.hip (vcmi_vc_traj_postf and
-// the vcmi_vc_traj_static / vcmi_vc_trajgv / *_dev family).
+// and the VarianceScaling post-filter (src/gv.jl:10-15), shared by postf.hip (C entries) and traj.hip (vc_traj_device, the
+// routine behind vcmi_vc_traj_postf / vcmi_vc_traj_static / vcmi_vc_trajgv and their *_dev forms), and the whole-matrix device
+// scratch of the host-pointer entries of both files.
 #pragma once
 #include "vcmi_common.hpp"
 
@@ -13,14 +14,12 @@ int variance_scaling_device(const double *dsrc, int64_t lds, int D, int64_t T, c
                             int64_t ldo, hipStream_t st);
 // The statistics half of variance_scaling_device: *dstat receives the per-thread device vector
 //   [mean (D) | var (D) | sigma2 (D)], each part kVsStatStride doubles from the previous one,
-// for a caller whose own kernel applies the scale (vc_traj_post_kernel).  It enters the stream order of that vector; the caller
+// for a caller that applies the scale itself (vc_traj_post_device).  It enters the stream order of that vector; the caller
 // enqueues its kernel on st and then calls variance_scaling_stats_leave(st).
 static constexpr int kVsStatStride = 256;
 int variance_scaling_stats_device(const double *dsrc, int64_t lds, int D, int64_t T, const double *sigma2_host,
                                   const double **dstat, hipStream_t st);
 int variance_scaling_stats_leave(hipStream_t st);
-// rows r0 .. r0 + nrows - 1 of a (ldi, T) matrix -> rows q0 .. of a (ldo, T) matrix (power row / feature rows of vc's matrices)
-int copy_rows_device(const double *din, int64_t ldi, int r0, int nrows, int64_t T, double *dout, int64_t ldo, int q0, hipStream_t st);
 
 // The two ends of vc(c::TrajectoryConverter, fm) around the chunk conversions, one streaming pass each.
 // pre:  dfm (D+1,T) static features (is_static) or (2D+1,T) -> dx (2D,T) dense, the converter's input.  Static input:
@@ -30,4 +29,27 @@ int vc_traj_pre_device(const double *dfm, int64_t ldf, int D, int64_t T, bool is
                        hipStream_t st);
 // post: dy (D,T) dense -> rows 2..D+1 of dout; with dstat (variance_scaling_stats_device) the rows are scaled on the way.
 int vc_traj_post_device(const double *dy, int D, int64_t T, const double *dstat, double *dout, int64_t ldo, hipStream_t st);
+
+// Whole-matrix device scratch of the vc and post-filter entries, one per thread, grow-only between calls: the converter input
+// x (2D,T) and result y (D,T) of vc_traj_device under their stream order (the *_dev entries run on the caller's stream), and
+// the staging matrix of the host-pointer entries (null stream, every call ends in a blocking download).  A host-pointer entry
+// holds a Release for the call: on every way out it waits for the device and frees the three once together they exceed
+// kVcScratchKeepBytes, so one long utterance does not keep its footprint for the life of the thread.
+static constexpr size_t kVcScratchKeepBytes = (size_t)256 << 20;
+struct VcScratch {
+  DevBuf<double> x, y, stage;
+  StreamOrder order;
+  size_t bytes() const { return (x.n + y.n + stage.n) * sizeof(double); }
+  struct Release {
+    VcScratch &s;
+    ~Release() {
+      if (s.bytes() <= kVcScratchKeepBytes) return;
+      (void)hipDeviceSynchronize();
+      s.x.release();
+      s.y.release();
+      s.stage.release();
+    }
+  };
+};
+VcScratch &vc_scratch();   // the calling thread's
 }  // namespace vcmi

@@ -1577,12 +1577,11 @@ extern "C" int vcmi_traj_convert_batch(vcmi_traj *t, int64_t n, const double *co
   return traj_host_batch(t, n, X, T, Y);
 }
 
-extern "C" int vcmi_traj_convert_batch_dev(vcmi_traj *t, int64_t n, const double *dX, const int64_t *x_off, const int64_t *T,
-                                           double *dY, const int64_t *y_off, void *stream) {
-  if (!t) return fail(VCMI_ERR_ARG, "vcmi_traj_convert_batch_dev: NULL handle");
-  if (n < 0) return fail(VCMI_ERR_ARG, "vcmi_traj_convert_batch_dev: negative batch size");
+// the body of the two device-resident batch entries: utterance u has X at dX + x_off[u] and Y at dY + y_off[u]
+static int traj_batch_device(vcmi_traj *t, const TrajGV *gv /* may be NULL */, int64_t n, const double *dX, const int64_t *x_off,
+                             const int64_t *T, double *dY, const int64_t *y_off, hipStream_t st, const char *who) {
   if (n == 0) return VCMI_OK;
-  if (!dX || !x_off || !T || !dY || !y_off) return fail(VCMI_ERR_ARG, "vcmi_traj_convert_batch_dev: NULL argument");
+  if (!dX || !x_off || !T || !dY || !y_off) return fail(VCMI_ERR_ARG, "%s: NULL argument", who);
   std::vector<TrajUtt> utts(n);
   int64_t f0 = 0;
   bool contiguous = true;
@@ -1593,90 +1592,33 @@ extern "C" int vcmi_traj_convert_batch_dev(vcmi_traj *t, int64_t n, const double
     f0 += T[u];
   }
   if (f0 == 0) return VCMI_OK;   // only empty utterances: nothing was launched, there is no status to read
-  VCMI_TRY(traj_run(t, utts, f0, contiguous, dX + x_off[0], as_stream(stream)));
-  return traj_check_status(t, as_stream(stream));
+  VCMI_TRY(traj_run(t, utts, f0, contiguous, dX + x_off[0], st, gv));
+  return traj_check_status(t, st);
 }
 
-extern "C" int vcmi_vc_traj(vcmi_traj *t, const double *fm, int64_t T, double *out) {
-  if (!t) return fail(VCMI_ERR_ARG, "vcmi_vc_traj: NULL handle");
-  if (T < 0 || (T > 0 && (!fm || !out))) return fail(VCMI_ERR_ARG, "vcmi_vc_traj: bad argument");
-  if (T == 0) return VCMI_OK;
-  if (t->length < 1) return fail(VCMI_ERR_ARG, "vcmi_vc_traj: length(t) must be positive");
-  const int D = t->D, D2 = t->D2;
-  const int64_t L = t->length, nch = (T + L - 1) / L;   // chunks [kL+1, min((k+1)L, T)], src/common.jl:42-57
-  std::vector<double> x((size_t)T * D2), y((size_t)T * D);
-  for (int64_t f = 0; f < T; ++f) memcpy(&x[(size_t)f * D2], fm + (size_t)f * (D2 + 1) + 1, sizeof(double) * D2);
-  std::vector<const double *> xs(nch);
-  std::vector<double *> ys(nch);
-  std::vector<int64_t> Ts(nch);
-  for (int64_t k = 0; k < nch; ++k) {
-    xs[k] = &x[(size_t)k * L * D2];
-    ys[k] = &y[(size_t)k * L * D];
-    Ts[k] = std::min<int64_t>(L, T - k * L);
-  }
-  VCMI_TRY(traj_host_batch(t, nch, xs.data(), Ts.data(), ys.data()));
-  for (int64_t f = 0; f < T; ++f) {
-    out[(size_t)f * (D + 1)] = fm[(size_t)f * (D2 + 1)];   // power row kept, src/common.jl:60
-    memcpy(out + (size_t)f * (D + 1) + 1, &y[(size_t)f * D], sizeof(double) * D);
-  }
-  t->length = Ts[nch - 1];   // the last fvconvert of the loop left W at the last chunk's length (see vcmi_traj_convert)
+extern "C" int vcmi_traj_convert_batch_dev(vcmi_traj *t, int64_t n, const double *dX, const int64_t *x_off, const int64_t *T,
+                                           double *dY, const int64_t *y_off, void *stream) {
+  if (!t) return fail(VCMI_ERR_ARG, "vcmi_traj_convert_batch_dev: NULL handle");
+  if (n < 0) return fail(VCMI_ERR_ARG, "vcmi_traj_convert_batch_dev: negative batch size");
+  return traj_batch_device(t, nullptr, n, dX, x_off, T, dY, y_off, as_stream(stream), "vcmi_traj_convert_batch_dev");
+}
+
+// the checks of a call on a TrajectoryGVGMMMap (T may be NULL) and the per-call parameters of its GV ascent
+static int trajgv_args(const vcmi_trajgv *h, int64_t n, const int64_t *T, int epochs, TrajGV *gv) {
+  if (!h) return fail(VCMI_ERR_ARG, "TrajectoryGVGMMMap: NULL handle");
+  if (epochs < 0) return fail(VCMI_ERR_ARG, "TrajectoryGVGMMMap: negative epoch count");
+  for (int64_t u = 0; T && u < n; ++u)
+    if (T[u] == 1) return fail(VCMI_ERR_DIM, "TrajectoryGVGMMMap: the variance of a one-frame trajectory is undefined");
+  gv->muv = h->muv.p;
+  gv->pv = h->pv.p;
+  gv->epochs = epochs;
   return VCMI_OK;
 }
 
-// vc(c::TrajectoryConverter, fm) followed by fvpostf!(VarianceScaling(sigma2), converted[2:end, :]) -- src/common.jl:31-63,
-// src/gv.jl:10-15 -- with the matrix resident in HBM from the upload of fm to the download of the filtered result: the power
-// row and the (2D,T) feature rows are split on the device, the chunks are converted by the device-resident batch path, the
-// post-filter runs on the (D,T) result and the output matrix is assembled on the device.
-extern "C" int vcmi_vc_traj_postf(vcmi_traj *t, const double *fm, int64_t T, const double *sigma2, double *out) {
-  if (!sigma2) return vcmi_vc_traj(t, fm, T, out);
-  if (!t) return fail(VCMI_ERR_ARG, "vcmi_vc_traj_postf: NULL handle");
-  if (T < 0 || (T > 0 && (!fm || !out))) return fail(VCMI_ERR_ARG, "vcmi_vc_traj_postf: bad argument");
-  if (T == 0) return VCMI_OK;
-  if (T < 2) return fail(VCMI_ERR_DIM, "vcmi_vc_traj_postf: the variance of a one-frame matrix is undefined");
-  if (t->length < 1) return fail(VCMI_ERR_ARG, "vcmi_vc_traj_postf: length(t) must be positive");
-  VCMI_TRY(check_device());
-  const int D = t->D, D2 = t->D2;
-  const int64_t L = t->length, nch = (T + L - 1) / L;   // chunks [kL+1, min((k+1)L, T)], src/common.jl:42-57
-  static thread_local DevBuf<double> dfm, dx, dy, dout;
-  VCMI_TRY(dfm.reserve((size_t)(D2 + 1) * T));
-  VCMI_TRY(dx.reserve((size_t)D2 * T));
-  VCMI_TRY(dy.reserve((size_t)D * T));
-  VCMI_TRY(dout.reserve((size_t)(D + 1) * T));
-  VCMI_TRY(staged_upload(dfm.p, fm, sizeof(double) * (size_t)(D2 + 1) * T, nullptr));
-  VCMI_TRY(copy_rows_device(dfm.p, D2 + 1, 1, D2, T, dx.p, D2, 0, nullptr));
-  VCMI_TRY(copy_rows_device(dfm.p, D2 + 1, 0, 1, T, dout.p, D + 1, 0, nullptr));         // power row kept, src/common.jl:60
-  std::vector<int64_t> xo(nch), yo(nch), Ts(nch);
-  for (int64_t k = 0; k < nch; ++k) {
-    xo[k] = k * L * D2;
-    yo[k] = k * L * D;
-    Ts[k] = std::min<int64_t>(L, T - k * L);
-  }
-  VCMI_TRY(vcmi_traj_convert_batch_dev(t, nch, dx.p, xo.data(), Ts.data(), dy.p, yo.data(), nullptr));
-  VCMI_TRY(variance_scaling_device(dy.p, D, D, T, sigma2, dy.p, D, nullptr));
-  VCMI_TRY(copy_rows_device(dy.p, D, 0, D, T, dout.p, D + 1, 1, nullptr));
-  VCMI_TRY(staged_download(out, dout.p, sizeof(double) * (size_t)(D + 1) * T, nullptr));
-  t->length = Ts[nch - 1];   // as vcmi_vc_traj: the last fvconvert of the loop left W at the last chunk's length
-  return VCMI_OK;
-}
-
-// ---- vc of a trajectory converter from STATIC features, on device matrices, with the GV ascent: vcmi_vc_traj_static,
-// vcmi_vc_trajgv, vcmi_vc_traj_dev, vcmi_vc_trajgv_dev (bin/vc.jl:75-82, src/common.jl:31-63, src/gv.jl:10-15) ----------------
-static int trajgv_args(const vcmi_trajgv *h, int64_t n, const int64_t *T, int epochs, vcmi::TrajGV *gv);
-
+// ---- vc of a trajectory converter (bin/vc.jl:75-82, src/common.jl:31-63, src/gv.jl:10-15): vcmi_vc_traj on the host-batch
+// path; with the post-filter, from STATIC features, on device matrices or with the GV ascent (vcmi_vc_traj_postf,
+// vcmi_vc_traj_static, vcmi_vc_trajgv, vcmi_vc_traj_dev, vcmi_vc_trajgv_dev) through vc_traj_device -------------------------
 namespace vcmi {
-
-// converter input x (2D,T) and result y (D,T) of the four entries, and the staging matrix of the two host-pointer ones;
-// per thread, grow-only between calls -- a host-pointer entry frees them on return once they exceed kVcTrajScratchKeepBytes
-static constexpr size_t kVcTrajScratchKeepBytes = (size_t)256 << 20;
-struct VcTrajScratch {
-  DevBuf<double> x, y, stage;
-  StreamOrder order;
-  size_t bytes() const { return (x.n + y.n + stage.n) * sizeof(double); }
-};
-static VcTrajScratch &vc_traj_scratch() {
-  static thread_local VcTrajScratch s;
-  return s;
-}
 
 // the checks of a call with T > 0 frames, and its chunk lengths [kL+1, min((k+1)L, T)], src/common.jl:42-57
 static int vc_traj_args(const vcmi_traj *t, const vcmi_trajgv *gvh, int epochs, int64_t T, const double *sigma2,
@@ -1691,7 +1633,7 @@ static int vc_traj_args(const vcmi_traj *t, const vcmi_trajgv *gvh, int epochs, 
   return VCMI_OK;
 }
 
-// The one routine behind the four entries.  dfm (D+1,T) static or (2D+1,T); dout (D+1,T); gvh != NULL: every chunk through
+// The one routine behind the five entries.  dfm (D+1,T) static or (2D+1,T); dout (D+1,T); gvh != NULL: every chunk through
 // fvconvert(tgv, X; epochs, alpha).  dout == dfm (static input only) assembles the result in place: the power row never
 // moves, rows 2..D+1 are overwritten after the pre kernel has read them.  Every argument is checked before the first launch.
 static int vc_traj_device(vcmi_traj *t, vcmi_trajgv *gvh, int epochs, double alpha, const double *dfm, int64_t ldf, int64_t T,
@@ -1707,7 +1649,7 @@ static int vc_traj_device(vcmi_traj *t, vcmi_trajgv *gvh, int epochs, double alp
   const int64_t L = t->length, nch = (int64_t)Ts.size();
   std::vector<TrajUtt> utts((size_t)nch);
   VCMI_TRY(check_device());
-  VcTrajScratch &sc = vc_traj_scratch();
+  VcScratch &sc = vc_scratch();
   VCMI_TRY(sc.x.reserve((size_t)D2 * T));
   VCMI_TRY(sc.y.reserve((size_t)D * T));
   VCMI_TRY(sc.order.enter(st));
@@ -1738,18 +1680,8 @@ static int vc_traj_host(vcmi_traj *t, vcmi_trajgv *gvh, int epochs, double alpha
     VCMI_TRY(vc_traj_args(t, gvh, epochs, T, sigma2, Ts, &gv, who));
   }
   VCMI_TRY(check_device());
-  VcTrajScratch &sc = vc_traj_scratch();
-  struct Release {   // on every way out
-    VcTrajScratch &s;
-    ~Release() {
-      if (s.bytes() > kVcTrajScratchKeepBytes) {
-        (void)hipDeviceSynchronize();
-        s.x.release();
-        s.y.release();
-        s.stage.release();
-      }
-    }
-  } release{sc};
+  VcScratch &sc = vc_scratch();
+  VcScratch::Release release{sc};   // on every way out
   const int D = t->D, rows = (is_static ? D : t->D2) + 1;
   const size_t nin = (size_t)rows * T, nout = (size_t)(D + 1) * T;
   VCMI_TRY(sc.stage.reserve(is_static ? nin : nin + nout));
@@ -1760,6 +1692,40 @@ static int vc_traj_host(vcmi_traj *t, vcmi_trajgv *gvh, int epochs, double alpha
 }
 
 }  // namespace vcmi
+
+extern "C" int vcmi_vc_traj(vcmi_traj *t, const double *fm, int64_t T, double *out) {
+  if (!t) return fail(VCMI_ERR_ARG, "vcmi_vc_traj: NULL handle");
+  if (T < 0 || (T > 0 && (!fm || !out))) return fail(VCMI_ERR_ARG, "vcmi_vc_traj: bad argument");
+  if (T == 0) return VCMI_OK;
+  std::vector<int64_t> Ts;
+  VCMI_TRY(vc_traj_args(t, nullptr, 0, T, nullptr, Ts, nullptr, "vcmi_vc_traj"));
+  const int D = t->D, D2 = t->D2;
+  const int64_t L = t->length, nch = (int64_t)Ts.size();
+  std::vector<double> x((size_t)T * D2), y((size_t)T * D);
+  for (int64_t f = 0; f < T; ++f) memcpy(&x[(size_t)f * D2], fm + (size_t)f * (D2 + 1) + 1, sizeof(double) * D2);
+  std::vector<const double *> xs(nch);
+  std::vector<double *> ys(nch);
+  for (int64_t k = 0; k < nch; ++k) {
+    xs[k] = &x[(size_t)k * L * D2];
+    ys[k] = &y[(size_t)k * L * D];
+  }
+  VCMI_TRY(traj_host_batch(t, nch, xs.data(), Ts.data(), ys.data()));
+  for (int64_t f = 0; f < T; ++f) {
+    out[(size_t)f * (D + 1)] = fm[(size_t)f * (D2 + 1)];   // power row kept, src/common.jl:60
+    memcpy(out + (size_t)f * (D + 1) + 1, &y[(size_t)f * D], sizeof(double) * D);
+  }
+  t->length = Ts[nch - 1];   // the last fvconvert of the loop left W at the last chunk's length (see vcmi_traj_convert)
+  return VCMI_OK;
+}
+
+// vc(c::TrajectoryConverter, fm) followed by fvpostf!(VarianceScaling(sigma2), converted[2:end, :]) -- src/common.jl:31-63,
+// src/gv.jl:10-15 -- with the matrix resident in HBM from the upload of fm to the download of the filtered result.  Without a
+// filter the call is vcmi_vc_traj's (device group, bounded pinned ring).
+extern "C" int vcmi_vc_traj_postf(vcmi_traj *t, const double *fm, int64_t T, const double *sigma2, double *out) {
+  if (!sigma2) return vcmi_vc_traj(t, fm, T, out);
+  if (!t) return fail(VCMI_ERR_ARG, "vcmi_vc_traj_postf: NULL handle");
+  return vc_traj_host(t, nullptr, 0, 0.0, fm, T, false, sigma2, out, "vcmi_vc_traj_postf");
+}
 
 extern "C" int vcmi_vc_traj_static(vcmi_traj *t, const double *fm, int64_t T, const double *sigma2, double *out) {
   if (!t) return fail(VCMI_ERR_ARG, "vcmi_vc_traj_static: NULL handle");
@@ -1827,17 +1793,6 @@ extern "C" int vcmi_trajgv_destroy(vcmi_trajgv *h) {
   return VCMI_OK;
 }
 
-static int trajgv_args(const vcmi_trajgv *h, int64_t n, const int64_t *T, int epochs, TrajGV *gv) {
-  if (!h) return fail(VCMI_ERR_ARG, "TrajectoryGVGMMMap: NULL handle");
-  if (epochs < 0) return fail(VCMI_ERR_ARG, "TrajectoryGVGMMMap: negative epoch count");
-  for (int64_t u = 0; T && u < n; ++u)
-    if (T[u] == 1) return fail(VCMI_ERR_DIM, "TrajectoryGVGMMMap: the variance of a one-frame trajectory is undefined");
-  gv->muv = h->muv.p;
-  gv->pv = h->pv.p;
-  gv->epochs = epochs;
-  return VCMI_OK;
-}
-
 extern "C" int vcmi_trajgv_convert_batch(vcmi_trajgv *h, int64_t n, const double *const *X, const int64_t *T, int epochs,
                                          double alpha, double *const *Y) {
   TrajGV gv{};
@@ -1859,22 +1814,8 @@ extern "C" int vcmi_trajgv_convert_batch_dev(vcmi_trajgv *h, int64_t n, const do
   TrajGV gv{};
   gv.alpha = alpha;
   VCMI_TRY(trajgv_args(h, n, T, epochs, &gv));
-  vcmi_traj *t = h->t;
   if (n < 0) return fail(VCMI_ERR_ARG, "vcmi_trajgv_convert_batch_dev: negative batch size");
-  if (n == 0) return VCMI_OK;
-  if (!dX || !x_off || !T || !dY || !y_off) return fail(VCMI_ERR_ARG, "vcmi_trajgv_convert_batch_dev: NULL argument");
-  std::vector<TrajUtt> utts(n);
-  int64_t f0 = 0;
-  bool contiguous = true;
-  for (int64_t u = 0; u < n; ++u) {
-    if (T[u] < 0 || T[u] > INT32_MAX) return fail(VCMI_ERR_DIM, "trajectory: bad utterance length");
-    if (x_off[u] != x_off[0] + f0 * t->D2) contiguous = false;
-    utts[u] = TrajUtt{dX + x_off[u], dY + y_off[u], f0, (int32_t)T[u], (int32_t)u};
-    f0 += T[u];
-  }
-  if (f0 == 0) return VCMI_OK;
-  VCMI_TRY(traj_run(t, utts, f0, contiguous, dX + x_off[0], as_stream(stream), &gv));
-  return traj_check_status(t, as_stream(stream));
+  return traj_batch_device(h->t, &gv, n, dX, x_off, T, dY, y_off, as_stream(stream), "vcmi_trajgv_convert_batch_dev");
 }
 
 // diffgmm(params) -- src/diffgmm.jl:9-25, on the joint parameters mu (2D,M), sigma (2D,2D,M) (host arithmetic: a

@@ -4,7 +4,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._arrays import current_stream_ptr, dev_matrix, is_torch, jl_matrix, jl_vector
+from ._arrays import current_stream_ptr, dev_matrix, is_torch, jl_matrix, jl_vector, sigma2_arg
 from .common import FrameByFrameConverter
 from .gmm import GMM
 
@@ -113,11 +113,7 @@ class GMMMap(FrameByFrameConverter):
         fm = jl_matrix(fm, "fm")
         if fm.shape[0] != self._D + 1:
             raise _lib.DimensionMismatch("Inconsistent dimentions.")
+        s2 = sigma2_arg(postfilter, self._D)
         out = np.empty_like(fm, order="F")
-        if postfilter is None:
-            _lib.check(_lib.lib.vcmi_vc_frames(self._h, _lib.dptr(fm), fm.shape[1], _lib.dptr(out)))
-        else:
-            if postfilter.sigma2.shape != (self._D,):
-                raise _lib.DimensionMismatch("sigma2 must have one entry per converted feature row")
-            _lib.check(_lib.lib.vcmi_vc_frames_postf(self._h, _lib.dptr(fm), fm.shape[1], _lib.dptr(postfilter.sigma2), _lib.dptr(out)))
+        _lib.check(_lib.lib.vcmi_vc_frames_postf(self._h, _lib.dptr(fm), fm.shape[1], s2, _lib.dptr(out)))   # NULL: vcmi_vc_frames
         return out

@@ -4,7 +4,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._arrays import current_stream_ptr, dev_matrix, is_torch, jl_matrix
+from ._arrays import current_stream_ptr, dev_matrix, is_torch, jl_matrix, sigma2_arg
 from .common import TrajectoryConverter
 
 
@@ -51,22 +51,14 @@ def push_delta(src):
     return out
 
 
-def _sigma2(postfilter, D):
-    """The sigma2 argument of the vc entries: NULL without a post-filter."""
-    if postfilter is None:
-        return None
-    if postfilter.sigma2.shape != (D,):
-        raise _lib.DimensionMismatch("sigma2 must have one entry per converted feature row")
-    return _lib.dptr(postfilter.sigma2)
-
-
-def _vc_static_args(c, fm, postfilter):
-    """fm (D+1,T) STATIC features of vc(c, fm; delta=True) -> (fm as a Julia matrix, D, sigma2 argument)"""
+def _vc_host_args(c, fm, postfilter, delta):
+    """fm of vc(c, fm; delta) on the host, (D+1,T) STATIC features if delta else (2D+1,T) -> (fm as a Julia matrix, D, sigma2
+    argument)"""
     fm = jl_matrix(fm, "fm")
     D = c._dim() // 2
-    if fm.shape[0] != D + 1:
+    if fm.shape[0] != (D if delta else 2 * D) + 1:
         raise _lib.DimensionMismatch("Inconsistent dimentions.")
-    return fm, D, _sigma2(postfilter, D)
+    return fm, D, sigma2_arg(postfilter, D)
 
 
 def _vc_dev(c, fm, postfilter, delta, call):
@@ -79,7 +71,7 @@ def _vc_dev(c, fm, postfilter, delta, call):
     D = c._dim() // 2
     if rows != (D if delta else 2 * D) + 1:
         raise _lib.DimensionMismatch("Inconsistent dimentions.")
-    s2 = _sigma2(postfilter, D)
+    s2 = sigma2_arg(postfilter, D)
     buf = torch.empty((T, D + 1), dtype=torch.float64, device=fm.device)
     _lib.check(call(ptr, ld, T, int(bool(delta)), s2, buf.data_ptr(), D + 1, current_stream_ptr()))
     return buf.t()
@@ -147,23 +139,10 @@ class TrajectoryGMMMap(TrajectoryConverter):
                 return _lib.lib.vcmi_vc_traj_dev(self._h, *args)
 
             return _vc_dev(self, fm, postfilter, delta, entry)
-        if delta:
-            fm, D, s2 = _vc_static_args(self, fm, postfilter)
-            out = np.empty_like(fm, order="F")
-            _lib.check(_lib.lib.vcmi_vc_traj_static(self._h, _lib.dptr(fm), fm.shape[1], s2, _lib.dptr(out)))
-            return out
-        fm = jl_matrix(fm, "fm")
-        D2 = self._dim()
-        if fm.shape[0] != D2 + 1:
-            raise _lib.DimensionMismatch("Inconsistent dimentions.")
-        T = fm.shape[1]
-        out = np.empty((D2 // 2 + 1, T), order="F")
-        if postfilter is None:
-            _lib.check(_lib.lib.vcmi_vc_traj(self._h, _lib.dptr(fm), T, _lib.dptr(out)))
-        else:       # fvpostf! (src/gv.jl:10-15) on the converted rows before the download
-            if postfilter.sigma2.shape != (D2 // 2,):
-                raise _lib.DimensionMismatch("sigma2 must have one entry per converted feature row")
-            _lib.check(_lib.lib.vcmi_vc_traj_postf(self._h, _lib.dptr(fm), T, _lib.dptr(postfilter.sigma2), _lib.dptr(out)))
+        fm, D, s2 = _vc_host_args(self, fm, postfilter, delta)
+        out = np.empty((D + 1, fm.shape[1]), order="F")
+        entry = _lib.lib.vcmi_vc_traj_static if delta else _lib.lib.vcmi_vc_traj_postf      # (NULL sigma2: vcmi_vc_traj)
+        _lib.check(entry(self._h, _lib.dptr(fm), fm.shape[1], s2, _lib.dptr(out)))
         return out
 
 
@@ -231,24 +210,15 @@ class TrajectoryGVGMMMap(TrajectoryConverter):
 
             return _vc_dev(self, fm, postfilter, delta, entry)
         if delta or postfilter is not None or (epochs, alpha) != (100, 1.0e-5):
-            D = self._dim() // 2
-            if delta:
-                fm, D, s2 = _vc_static_args(self, fm, postfilter)
-            else:
-                fm = jl_matrix(fm, "fm")
-                if fm.shape[0] != 2 * D + 1:
-                    raise _lib.DimensionMismatch("Inconsistent dimentions.")
-                s2 = _sigma2(postfilter, D)
+            fm, D, s2 = _vc_host_args(self, fm, postfilter, delta)
             out = np.empty((D + 1, fm.shape[1]), order="F")
             _lib.check(_lib.lib.vcmi_vc_trajgv(self._h, _lib.dptr(fm), fm.shape[1], int(bool(delta)), int(epochs), float(alpha), s2,
                                                _lib.dptr(out)))
             return out
-        fm = jl_matrix(fm, "fm")
-        D2 = self._dim()
-        if fm.shape[0] != D2 + 1:
-            raise _lib.DimensionMismatch("Inconsistent dimentions.")
+        # (not vcmi_vc_trajgv: this loop shards over a device group and leaves len(c) alone)
+        fm, D, _ = _vc_host_args(self, fm, None, False)
         T, L = fm.shape[1], len(self)
-        out = np.empty((D2 // 2 + 1, T), order="F")
+        out = np.empty((D + 1, T), order="F")
         chunks = [np.asfortranarray(fm[1:, b:min(b + L, T)]) for b in range(0, T, L)]
         for k, y in enumerate(self.fvconvert_batch(chunks)):
             out[1:, k * L:k * L + y.shape[1]] = y
