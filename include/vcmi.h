@@ -195,6 +195,8 @@ int vcmi_estep_diag(const double *X, int64_t N, int Dj, int M, const double *w, 
  * statistics within 1e-12 of each other).  VCMI_ESTEP_AUTO (default) decides per call, on the device, from a sample of the call's
  * own frames (16 chunks of 1024: at most a quarter without an owner -> the hard-assignment path); vcmi_estep_set_path pins
  * VCMI_ESTEP_HARD or VCMI_ESTEP_SOFT for the calling thread (training loops that must take the same path on every rank).
+ * Under VCMI_ESTEP_AUTO a model of at most 16 mixtures never takes the hard-assignment path: its one-tile kernel is the faster
+ * one whatever the data (csrc/estep.hip, estep_mfma_launch).
  * Log-densities of competing mixtures are evaluated term by term, (x - mu)^2 / var, wherever the expanded form's
  * rounding-error bound exceeds 1e-10 (variances near min_covar).
  * Accuracy, per mixture m (each of S0[m], S1[:,m], S2[:,m] relative to that mixture's own largest value -- the M-step divides by

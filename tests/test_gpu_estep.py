@@ -118,6 +118,32 @@ def test_device_resident_deterministic_and_additive(vc):
     assert np.max(np.abs(mu2[:, big] - mu.T[:, big])) < 0.2
 
 
+def test_parameter_staging_ring_reused_by_both_launchers(vc):
+    """The one-kernel launcher and the launcher of the mixture groups (M > 128) stage their parameters through the same ring of
+    eight pinned slots: 24 calls queued back to back on one stream, cycling through a shared-tile shape, a grouped one and a
+    one-tile one (blocks of different lengths, so the slots' device copies overlap from call to call), without reading
+    anything back in between.  Every result equals, bit for bit, the first result of its shape."""
+    import torch
+    from oracle import np_oracle as npo
+    N = 200
+    cases = []
+    for k, (Dj, M) in enumerate([(32, 130), (34, 40), (32, 16)]):      # the largest block first: the ring has its full size
+        w, mu, _ = npo.synth_model(300 + k, Dj, M)
+        rg = np.random.default_rng(310 + k)
+        var = np.exp(rg.uniform(np.log(1e-2), 0.0, (M, Dj)))
+        comp = rg.choice(M, size=N, p=w)
+        X = torch.from_numpy(mu[comp] + rg.standard_normal((N, Dj)) * np.sqrt(var[comp])).cuda()
+        first = vc.estep_diag_dev(X.t(), w, mu.T, var.T).cpu()
+        assert abs(float(first[:M].sum()) - N) < 1e-6 * N
+        cases.append((X, w, mu.T, var.T, first))
+    outs = [torch.empty(vc.stats_len(c[0].shape[1], len(c[1])), dtype=torch.float64, device="cuda") for _ in range(8) for c in cases]
+    for i, out in enumerate(outs):
+        X, w, mu, var, _ = cases[i % 3]
+        vc.estep_diag_dev(X.t(), w, mu, var, out=out)
+    for i, out in enumerate(outs):
+        assert torch.equal(out.cpu(), cases[i % 3][4]), (i, i % 3)
+
+
 def test_errors(vc):
     with pytest.raises(vc.PosDefException):
         vc.estep_diag(np.zeros((4, 10)), np.ones(2) / 2, np.zeros((4, 2)), np.zeros((4, 2)))

@@ -18,9 +18,7 @@
 //    so results are bit-identical run to run (no FP64 atomics).
 //  * generic kernels (any Dj, M): gamma to an HBM workspace in chunks, then per-(m,d) sequential accumulation
 //    over fixed frame segments, then a fixed-order reduction.
-#include "vcmi_common.hpp"
-#include <atomic>
-#include "gmmmap_handle.hpp"
+#include "estep_internal.hpp"
 #include "devgroup.hpp"
 #include "hostpipe.hpp"
 #define VCMI_DPP_NO_COPY 1           // (fp64_exp.hpp: lane permutations without the copy of the old value)
@@ -31,6 +29,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <type_traits>
 
 namespace vcmi {
 
@@ -126,8 +125,7 @@ estep_reduce_kernel(const double *__restrict__ part, int nrows, int64_t plen, do
   __syncthreads();
   if (q == 0 && e < plen) stats[e] = (accumulate ? stats[e] : 0.0) + ((psum[0][el] + psum[1][el]) + (psum[2][el] + psum[3][el]));
 }
-static inline void estep_reduce_launch(const double *part, int nrows, int64_t plen, double *stats, hipStream_t st, int accumulate = 1,
-                                       const int64_t *only_if = nullptr) {
+void estep_reduce_launch(const double *part, int nrows, int64_t plen, double *stats, hipStream_t st, int accumulate, const int64_t *only_if) {
   hipLaunchKernelGGL(estep_reduce_kernel, dim3((unsigned)((plen + 63) / 64)), dim3(256), 0, st, part, nrows, plen, stats, accumulate, only_if);
 }
 
@@ -179,7 +177,23 @@ estep_group_reduce_kernel(const double *__restrict__ part, int nrows, int64_t pl
   stats[dst] += s;
 }
 
-__global__ void estep_sum_kernel(const double *__restrict__ v, int64_t n, double *__restrict__ out);
+// deterministic sum of n doubles into out[0] (+=): one workgroup, strided partials then a sequential tail
+__global__ void __launch_bounds__(256)
+estep_sum_kernel(const double *__restrict__ v, int64_t n, double *__restrict__ out) {
+  __shared__ double part[256];
+  double s = 0.0;
+  for (int64_t i = threadIdx.x; i < n; i += 256) s += v[i];
+  part[threadIdx.x] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double t = out[0];
+    for (int i = 0; i < 256; ++i) t += part[i];
+    out[0] = t;
+  }
+}
+void estep_sum_launch(const double *v, int64_t n, double *out, hipStream_t st) {
+  hipLaunchKernelGGL(estep_sum_kernel, dim3(1), dim3(256), 0, st, v, n, out);
+}
 
 // Odd joint dimension: the MFMA kernels stream X by 16-byte LDS-DMA rows, i.e. need an even row length.  The frames are
 // copied with one extra dimension that is identically 0 under a unit-variance, zero-mean parameter: it adds
@@ -670,7 +684,7 @@ struct EstepStaging {
 };
 
 struct EstepScratch {
-  DevBuf<double> mu, iv, cst, G, LSE, part, Wpack, cinit, X, stats, raw, refiv, refc, Xpad, statsp;
+  DevBuf<double> mu, iv, cst, G, LSE, part, Wpack, cinit, raw, refiv, refc, Xpad, statsp;
   DevBuf<unsigned long long> mfma_count;      // optional measurement counter (vcmi_debug_estep_mfma); null: the kernels count nothing
   // the hard-assignment path (estep_hard.hpp, estep_path.hpp): operands, the sample's histograms, the path control words, sort
   // scratch, pieces and the soft frames' matrix
@@ -681,6 +695,7 @@ struct EstepScratch {
   DevBuf<double> hpart, hllm, Xsoft;
   bool last_hard = false;                      // the last diagonal E-step of this thread launched the hard-assignment path's kernels
   EstepStaging stage;
+  std::vector<double> hblock;                  // estep_device_block: the host copy of a device parameter block
   StreamOrder order;   // calls of one thread on different streams share the buffers above
 };
 static EstepScratch &scratch() {
@@ -693,14 +708,40 @@ static int &estep_path_choice_ref() {
   static thread_local int p = VCMI_ESTEP_AUTO;
   return p;
 }
-static int estep_path_choice() { return estep_path_choice_ref(); }
-
 
 // model parameters: pinned host slot -> device
 __global__ void __launch_bounds__(256) estep_param_copy_kernel(const double *__restrict__ src, double *__restrict__ dst, size_t n) {
   const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
   if (i < n) dst[i] = src[i];
 }
+// One block of n parameters through the ring: fill(h) writes the next pinned slot, the copy kernel takes it to the slot's own
+// device copy -> *dblock.  The host waits only for the copy that last used the slot (eight calls ago).
+template <class Fill>
+static int estep_stage_params(EstepScratch &sc, size_t n, hipStream_t st, const Fill &fill, const double **dblock) {
+  VCMI_TRY(sc.raw.reserve(EstepStaging::kSlots * n));    // one device copy per staging buffer
+  VCMI_TRY(sc.stage.reserve(n));
+  const int b = sc.stage.next;
+  sc.stage.next = (sc.stage.next + 1) % EstepStaging::kSlots;
+  VCMI_HIP(hipEventSynchronize(sc.stage.copied[b]));
+  double *h = sc.stage.host[b], *dslot = sc.raw.p + (size_t)b * n;
+  fill(h);
+  // (a copy kernel reading the pinned slot, not hipMemcpyAsync: the copy engine's hand-over to the compute queue costs
+  // ~20 us of idle GPU per call, a kernel on the same queue a few.  Round 4 let the prep kernel read the pinned slot itself
+  // and write the device copy -- one launch less -- and lost 7 us per call: its threads read every parameter three or four
+  // times, across the link.)
+  hipLaunchKernelGGL(estep_param_copy_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, h, dslot, n);
+  VCMI_HIP(hipEventRecord(sc.stage.copied[b], st));
+  *dblock = dslot;
+  return VCMI_OK;
+}
+
+// Where a call's model parameters are: three host arrays, or one DEVICE block [w (M) | mu (dj,M) | var (dj,M)] that the caller
+// keeps alive and orders on the call's stream (vcmi_gmm_em_diag: the M-step kernel wrote it).
+struct EstepParams {
+  const double *w = nullptr, *mu = nullptr, *var = nullptr, *block = nullptr;
+  static EstepParams host(const double *w, const double *mu, const double *var) { return {w, mu, var, nullptr}; }
+  static EstepParams device(const double *block) { return {nullptr, nullptr, nullptr, block}; }
+};
 
 // raw = [w (M) | mu (DJ,M) | var (DJ,M)] on the device -> the MFMA kernel's operands:
 //   Wpack[mt][ks][lane]: A-operand fragments of W[m][k], k < DJ -> -1/(2 var) (multiplies x^2), k >= DJ -> mu/var
@@ -763,13 +804,12 @@ estep_prep_kernel(const double *__restrict__ raw, int M, int dj, double *__restr
 
 // The MFMA path for one joint dimension (parameters staged through pinned buffers, prep kernel, the E-step kernel with one
 // workgroup per CU, fixed-order reduction of the workgroups' partial statistics).
-// `dparams` (optional): the parameters as a DEVICE block [w (M) | mu (dj,M) | var (dj,M)] that the caller keeps alive and orders
-// on `st` (vcmi_gmm_em_diag: the M-step kernel wrote it).  The prep kernels then read that block: no staging slot, no copies, no
-// event, nothing the host waits for -- w / mu / var are not looked at.  Everything from the prep kernels on is the same code on the
-// same operands: the same parameter values give the same bits through either entry.
+// A device parameter block (EstepParams) is read by the prep kernels where it is: no staging slot, no copies, no event, nothing
+// the host waits for.  Everything from the prep kernels on is the same code on the same operands: the same parameter values
+// give the same bits from either source.
 template <int DJ>
-static int estep_mfma_launch(EstepScratch &sc, const double *dX, int64_t N, int dj, int M, const double *w, const double *mu,
-                             const double *var, double *dstats, int64_t plen, hipStream_t st, const double *dparams = nullptr) {
+static int estep_mfma_launch(EstepScratch &sc, const double *dX, int64_t N, int dj, int M, const EstepParams &prm, double *dstats,
+                             int64_t plen, hipStream_t st) {
   using C = EstepCfg<DJ>;
   int dev = 0, cus = 256;
   (void)hipGetDevice(&dev);
@@ -777,7 +817,6 @@ static int estep_mfma_launch(EstepScratch &sc, const double *dX, int64_t N, int 
   const int64_t nblocks = (N + C::FB - 1) / C::FB;
   const int grid = (int)std::min<int64_t>(nblocks, cus);
   const size_t nraw = (size_t)M * (1 + 2 * dj);
-  if (!dparams) VCMI_TRY(sc.raw.reserve(EstepStaging::kSlots * nraw));    // one device copy per staging buffer
   VCMI_TRY(sc.Wpack.reserve((size_t)8 * C::KS * 64));
   VCMI_TRY(sc.cinit.reserve((size_t)C::MMAX));
   VCMI_TRY(sc.refiv.reserve((size_t)M * dj));
@@ -787,24 +826,13 @@ static int estep_mfma_launch(EstepScratch &sc, const double *dX, int64_t N, int 
   while (16 * mtp < M) mtp *= 2;
   const int wpt = 8 / mtp;
   VCMI_TRY(sc.part.reserve((size_t)grid * wpt * plen));
-  const double *draw = dparams;
-  if (!dparams) {
-    VCMI_TRY(sc.stage.reserve(nraw));
-    const int b = sc.stage.next;
-    sc.stage.next = (sc.stage.next + 1) % EstepStaging::kSlots;
-    VCMI_HIP(hipEventSynchronize(sc.stage.copied[b]));   // the copy that last used this slot (eight calls ago) is done
-    double *h = sc.stage.host[b], *dslot = sc.raw.p + (size_t)b * nraw;
-    memcpy(h, w, sizeof(double) * M);
-    memcpy(h + M, mu, sizeof(double) * M * dj);
-    memcpy(h + M + (size_t)M * dj, var, sizeof(double) * M * dj);
-    // (a copy kernel reading the pinned slot, not hipMemcpyAsync: the copy engine's hand-over to the compute queue costs
-    // ~20 us of idle GPU per call, a kernel on the same queue a few.  Round 4 let the prep kernel read the pinned slot itself
-    // and write the device copy -- one launch less -- and lost 7 us per call: its threads read every parameter three or four
-    // times, across the link.)
-    hipLaunchKernelGGL(estep_param_copy_kernel, dim3((unsigned)((nraw + 255) / 256)), dim3(256), 0, st, h, dslot, nraw);
-    VCMI_HIP(hipEventRecord(sc.stage.copied[b], st));
-    draw = dslot;
-  }
+  const double *draw = prm.block;
+  if (!draw)
+    VCMI_TRY(estep_stage_params(sc, nraw, st, [&](double *h) {
+      memcpy(h, prm.w, sizeof(double) * M);
+      memcpy(h + M, prm.mu, sizeof(double) * M * dj);
+      memcpy(h + M + (size_t)M * dj, prm.var, sizeof(double) * M * dj);
+    }, &draw));
   hipLaunchKernelGGL(estep_prep_kernel<DJ>, dim3((8 * C::KS * 64 + 255) / 256), dim3(256), 0, st, draw, M, dj, sc.Wpack.p,
                      sc.cinit.p, sc.refiv.p, sc.refc.p);
   VCMI_HIP(hipGetLastError());
@@ -846,7 +874,7 @@ static int estep_mfma_launch(EstepScratch &sc, const double *dX, int64_t N, int 
     // the screen on a SAMPLE of 16 chunks spread over the frames (~20 us), estep_path_decide_kernel writes the control words,
     // every kernel of either path starts with a look at them -- the launch sequence is fixed, nothing waits for the GPU, and
     // identical inputs give identical bits whatever this thread (or any other) ran before.  vcmi_estep_set_path pins one.
-    const int path = debug_flag(kDbgEstepNoHard) ? VCMI_ESTEP_SOFT : estep_path_choice();
+    const int path = debug_flag(kDbgEstepNoHard) ? VCMI_ESTEP_SOFT : estep_path_choice_ref();
     bool hard_on = N >= kHardMinFrames && N < ((int64_t)1 << 31) && M <= kHardMaxM && path != VCMI_ESTEP_SOFT;
     // One mixture tile (M <= 16, the size bin/train_gmm.jl defaults to): estep_small_kernel takes 0.30 ms per 1.25e6 frames
     // whatever the data, the hard-assignment path 0.42 where every frame has an owner -- nothing to decide, and the sample screen,
@@ -957,8 +985,8 @@ static int estep_mfma_launch(EstepScratch &sc, const double *dX, int64_t N, int 
 // in fixed order into the full layout).  Every log-density within 36 nats of its group's maximum is re-evaluated term by
 // term (the kernel's refinement, unconditional in PHASE 3), so mixtures that compete across two groups are exact as well.
 template <int DJ>
-static int estep_mfma_groups_launch(EstepScratch &sc, const double *dX, int64_t N, int dj, int M, const double *w, const double *mu,
-                                    const double *var, double *dstats, int64_t plen, hipStream_t st) {
+static int estep_mfma_groups_launch(EstepScratch &sc, const double *dX, int64_t N, int dj, int M, const EstepParams &prm, double *dstats,
+                                    int64_t plen, hipStream_t st) {
   using C = EstepCfg<DJ>;
   int dev = 0, cus = 256;
   (void)hipGetDevice(&dev);
@@ -967,7 +995,6 @@ static int estep_mfma_groups_launch(EstepScratch &sc, const double *dX, int64_t 
   const int64_t chunk = std::min<int64_t>(N, (int64_t)1 << 18);
   const size_t nraw = (size_t)M * (1 + 2 * dj), wlen = (size_t)8 * C::KS * 64;
   constexpr int kCombineGrid = 1024;
-  VCMI_TRY(sc.raw.reserve(EstepStaging::kSlots * nraw));
   VCMI_TRY(sc.Wpack.reserve(wlen * ng));
   VCMI_TRY(sc.cinit.reserve((size_t)C::MMAX * ng));
   VCMI_TRY(sc.refiv.reserve((size_t)M * dj));
@@ -975,24 +1002,18 @@ static int estep_mfma_groups_launch(EstepScratch &sc, const double *dX, int64_t 
   VCMI_TRY(sc.G.reserve((size_t)ng * chunk * C::MMAX));
   VCMI_TRY(sc.LSE.reserve((size_t)ng * chunk + kCombineGrid));
   VCMI_TRY(sc.part.reserve((size_t)cus * ((size_t)C::MMAX * (1 + 2 * dj) + 1)));
-  VCMI_TRY(sc.stage.reserve(nraw));
-  const int b = sc.stage.next;
-  sc.stage.next = (sc.stage.next + 1) % EstepStaging::kSlots;
-  VCMI_HIP(hipEventSynchronize(sc.stage.copied[b]));
-  double *h = sc.stage.host[b], *draw = sc.raw.p + (size_t)b * nraw;
+  const double *draw = nullptr;
   std::vector<size_t> goff((size_t)ng + 1, 0);
-  for (int g = 0; g < ng; ++g) {      // every group's [w | mu (dj,Mg) | var (dj,Mg)] contiguous
-    const int m0 = g * C::MMAX, Mg = std::min(C::MMAX, M - m0);
-    double *hg = h + goff[(size_t)g];
-    memcpy(hg, w + m0, sizeof(double) * Mg);
-    memcpy(hg + Mg, mu + (size_t)dj * m0, sizeof(double) * Mg * dj);
-    memcpy(hg + Mg + (size_t)Mg * dj, var + (size_t)dj * m0, sizeof(double) * Mg * dj);
-    goff[(size_t)g + 1] = goff[(size_t)g] + (size_t)Mg * (1 + 2 * dj);
-  }
-  // (a copy kernel reading the pinned slot, not hipMemcpyAsync: the copy engine's hand-over to the compute queue costs
-  // ~20 us of idle GPU per call, a kernel on the same queue a few)
-  hipLaunchKernelGGL(estep_param_copy_kernel, dim3((unsigned)((nraw + 255) / 256)), dim3(256), 0, st, h, draw, nraw);
-  VCMI_HIP(hipEventRecord(sc.stage.copied[b], st));
+  VCMI_TRY(estep_stage_params(sc, nraw, st, [&](double *h) {
+    for (int g = 0; g < ng; ++g) {      // every group's [w | mu (dj,Mg) | var (dj,Mg)] contiguous
+      const int m0 = g * C::MMAX, Mg = std::min(C::MMAX, M - m0);
+      double *hg = h + goff[(size_t)g];
+      memcpy(hg, prm.w + m0, sizeof(double) * Mg);
+      memcpy(hg + Mg, prm.mu + (size_t)dj * m0, sizeof(double) * Mg * dj);
+      memcpy(hg + Mg + (size_t)Mg * dj, prm.var + (size_t)dj * m0, sizeof(double) * Mg * dj);
+      goff[(size_t)g + 1] = goff[(size_t)g] + (size_t)Mg * (1 + 2 * dj);
+    }
+  }, &draw));
   for (int g = 0; g < ng; ++g) {
     const int m0 = g * C::MMAX, Mg = std::min(C::MMAX, M - m0);
     hipLaunchKernelGGL(estep_prep_kernel<DJ>, dim3((unsigned)((wlen + 255) / 256)), dim3(256), 0, st, draw + goff[(size_t)g], Mg, dj,
@@ -1015,7 +1036,7 @@ static int estep_mfma_groups_launch(EstepScratch &sc, const double *dX, int64_t 
     }
     hipLaunchKernelGGL(estep_group_combine_kernel, dim3(kCombineGrid), dim3(256), 0, st, sc.G.p, sc.LSE.p, ng, nfr,
                        (int64_t)chunk * C::MMAX, llpart);
-    hipLaunchKernelGGL(estep_sum_kernel, dim3(1), dim3(256), 0, st, llpart, (int64_t)kCombineGrid, dstats + (plen - 1));
+    estep_sum_launch(llpart, (int64_t)kCombineGrid, dstats + (plen - 1), st);
     for (int g = 0; g < ng; ++g) {
       const int m0 = g * C::MMAX, Mg = std::min(C::MMAX, M - m0);
       const int64_t plen_g = (int64_t)Mg * (1 + 2 * dj) + 1;
@@ -1029,55 +1050,50 @@ static int estep_mfma_groups_launch(EstepScratch &sc, const double *dX, int64_t 
   return VCMI_OK;
 }
 
-static int estep_device_run(const double *dX, int64_t N, int Dj, int M, const double *w, const double *mu, const double *var,
-                            double *dstats, hipStream_t st);
-
-// the shapes estep_mfma_launch serves: at most 128 mixtures, an even joint dimension up to 160
-static bool estep_mfma_shape(int Dj, int M) {
-  return M <= EstepCfg<80>::MMAX && Dj % 2 == 0 && Dj <= 160 && !debug_flag(kDbgEstepGeneric);
+// The joint dimensions the MFMA kernels serve: even (the rows of X are 16-byte aligned for the LDS-DMA), up to 160 ...
+static bool mfma_dims(int Dj) { return Dj % 2 == 0 && Dj <= 160 && !debug_flag(kDbgEstepGeneric); }
+// ... and the shapes estep_mfma_launch serves among them: at most 128 mixtures (more run as groups of 128)
+static bool estep_mfma_shape(int Dj, int M) { return M <= EstepCfg<80>::MMAX && mfma_dims(Dj); }
+// f(std::integral_constant<int, DJ>) for the smallest instantiation DJ that holds Dj (mfma_dims): 32, 48, 64, 80 (one
+// kernel), then the two-kernel form -- 112 for the dimensions between (Dj = 82 ... 112 ran in the 160-wide one: 1.5 x the work)
+template <class F>
+static int with_mfma_dj(int Dj, const F &f) {
+  if (Dj <= 32) return f(std::integral_constant<int, 32>{});
+  if (Dj <= 48) return f(std::integral_constant<int, 48>{});
+  if (Dj <= 64) return f(std::integral_constant<int, 64>{});
+  if (Dj <= 80) return f(std::integral_constant<int, 80>{});
+  if (Dj <= 112) return f(std::integral_constant<int, 112>{});
+  return f(std::integral_constant<int, 160>{});
 }
-// ... and the instantiation that runs one of them, from host parameters or from a device block (estep_mfma_launch)
-static int estep_mfma_dispatch(EstepScratch &sc, const double *dX, int64_t N, int Dj, int M, const double *w, const double *mu,
-                               const double *var, double *dstats, int64_t plen, hipStream_t st, const double *dparams) {
-  // the smallest instantiation that holds Dj (an even Dj keeps the rows of X 16-byte aligned for the LDS-DMA)
-  if (Dj <= 32) return estep_mfma_launch<32>(sc, dX, N, Dj, M, w, mu, var, dstats, plen, st, dparams);
-  if (Dj <= 48) return estep_mfma_launch<48>(sc, dX, N, Dj, M, w, mu, var, dstats, plen, st, dparams);
-  if (Dj <= 64) return estep_mfma_launch<64>(sc, dX, N, Dj, M, w, mu, var, dstats, plen, st, dparams);
-  if (Dj <= 80) return estep_mfma_launch<80>(sc, dX, N, Dj, M, w, mu, var, dstats, plen, st, dparams);
-  // (the two-kernel form beyond 80; 112 for the dimensions between -- Dj = 82 ... 112 ran in the 160-wide one: 1.5 x the work)
-  if (Dj <= 112) return estep_mfma_launch<112>(sc, dX, N, Dj, M, w, mu, var, dstats, plen, st, dparams);
-  return estep_mfma_launch<160>(sc, dX, N, Dj, M, w, mu, var, dstats, plen, st, dparams);
+// The E-step of a dimension the MFMA kernels serve (mfma_dims(Dj), N > 0) -> dstats.  (estep_mfma_launch's first reduction
+// overwrites dstats: no memset -- two fill kernels -- in front of it; the groups add into it.)
+static int estep_mfma(EstepScratch &sc, const double *dX, int64_t N, int Dj, int M, const EstepParams &prm, double *dstats, hipStream_t st) {
+  const int64_t plen = (int64_t)M * (1 + 2 * Dj) + 1;
+  const bool groups = !estep_mfma_shape(Dj, M);
+  if (groups) VCMI_HIP(hipMemsetAsync(dstats, 0, plen * sizeof(double), st));
+  return with_mfma_dj(Dj, [&](auto dj_c) -> int {
+    constexpr int DJ = decltype(dj_c)::value;
+    return groups ? estep_mfma_groups_launch<DJ>(sc, dX, N, Dj, M, prm, dstats, plen, st)
+                  : estep_mfma_launch<DJ>(sc, dX, N, Dj, M, prm, dstats, plen, st);
+  });
 }
 
-static int estep_device(const double *dX, int64_t N, int Dj, int M, const double *w, const double *mu, const double *var,
-                        double *dstats, hipStream_t st) {
-  EstepScratch &sc = scratch();
-  VCMI_TRY(sc.order.enter(st));
-  const int rc = estep_device_run(dX, N, Dj, M, w, mu, var, dstats, st);
-  (void)sc.order.leave(st);
-  return rc;
-}
-
-static int estep_device_run(const double *dX, int64_t N, int Dj, int M, const double *w, const double *mu, const double *var,
-                            double *dstats, hipStream_t st) {
-  if (N < 0 || Dj < 1 || M < 1) return fail(VCMI_ERR_DIM, "E-step: N=%lld Dj=%d M=%d invalid", (long long)N, Dj, M);
+// One E-step from host parameters inside the caller's StreamOrderScope
+static int estep_run(EstepScratch &sc, const double *dX, int64_t N, int Dj, int M, const double *w, const double *mu, const double *var,
+                     double *dstats, hipStream_t st) {
+  VCMI_TRY(estep_check_dims(N, Dj, M));
   if (!w || !mu || !var || !dstats || (N > 0 && !dX)) return fail(VCMI_ERR_ARG, "E-step: NULL argument");
-  EstepScratch &sc = scratch();
   sc.last_hard = false;            // (vcmi_debug_estep_last_soft: the groups and the generic kernels never take the hard path)
   const int64_t plen = (int64_t)M * (1 + 2 * Dj) + 1;
-  for (int m = 0; m < M; ++m)
-    for (int d = 0; d < Dj; ++d)
-      if (!(var[d + (size_t)Dj * m] > 0.0))
-        return fail(VCMI_ERR_NOT_PD, "E-step: variance (%d,%d) is not positive", d + 1, m + 1);
-  // (estep_mfma_launch's first reduction overwrites dstats: no memset -- two fill kernels -- in front of it)
-  const bool overwrites = N > 0 && M <= EstepCfg<80>::MMAX && Dj % 2 == 0 && Dj <= 160 && !debug_flag(kDbgEstepGeneric);
-  if (!overwrites) VCMI_HIP(hipMemsetAsync(dstats, 0, plen * sizeof(double), st));
+  const int64_t bad = first_bad_variance(var, Dj, M);
+  if (bad >= 0) return fail(VCMI_ERR_NOT_PD, "E-step: variance (%d,%d) is not positive", (int)(bad % Dj) + 1, (int)(bad / Dj) + 1);
+  if (N > 0 && mfma_dims(Dj)) return estep_mfma(sc, dX, N, Dj, M, EstepParams::host(w, mu, var), dstats, st);
+  VCMI_HIP(hipMemsetAsync(dstats, 0, plen * sizeof(double), st));
   if (N == 0) return VCMI_OK;
 
-  // MFMA instantiations for Dj = 32, 48, 64, 80 (one kernel) and 160 (two kernels); any even Dj up to 160 runs in the next
-  // larger one with zero weights in the padding dimensions; odd Dj, Dj > 160 and M > 128 take the generic kernels below.
-  if (Dj % 2 == 1 && Dj + 1 <= 160 && !debug_flag(kDbgEstepGeneric)) {
-    // odd joint dimension: one zero dimension more (see estep_pad_x_kernel), in chunks that bound the padded copy
+  if (mfma_dims(Dj + 1)) {
+    // odd joint dimension: one zero dimension more (see estep_pad_x_kernel), in chunks that bound the padded copy; what is
+    // left after it (Dj > 160) takes the generic kernels
     const int djp = Dj + 1;
     const int64_t plen_p = (int64_t)M * (1 + 2 * djp) + 1, chunk = std::min<int64_t>(N, (int64_t)1 << 20);
     std::vector<double> mup((size_t)M * djp, 0.0), varp((size_t)M * djp, 1.0);
@@ -1092,7 +1108,7 @@ static int estep_device_run(const double *dX, int64_t N, int Dj, int M, const do
       const int64_t nfr = std::min(chunk, N - n0);
       hipLaunchKernelGGL(estep_pad_x_kernel, dim3((unsigned)std::min<int64_t>((nfr * djp + 255) / 256, 65536)), dim3(256), 0, st,
                          dX + n0 * Dj, nfr, Dj, sc.Xpad.p);
-      VCMI_TRY(estep_device_run(sc.Xpad.p, nfr, djp, M, w, mup.data(), varp.data(), sc.statsp.p, st));     // (zeroes statsp first)
+      VCMI_TRY(estep_mfma(sc, sc.Xpad.p, nfr, djp, M, EstepParams::host(w, mup.data(), varp.data()), sc.statsp.p, st));
       hipLaunchKernelGGL(estep_unpad_stats_kernel, dim3((unsigned)(((int64_t)M * Dj + 255) / 256)), dim3(256), 0, st, sc.statsp.p, M, Dj,
                          nfr, dstats);
       VCMI_HIP(hipGetLastError());
@@ -1100,30 +1116,19 @@ static int estep_device_run(const double *dX, int64_t N, int Dj, int M, const do
     // (mup / varp are staged into pinned memory by the inner call before it returns)
     return VCMI_OK;
   }
-  if (M > EstepCfg<80>::MMAX && Dj % 2 == 0 && Dj <= 160 && !debug_flag(kDbgEstepGeneric)) {      // groups of 128 mixtures
-    if (Dj <= 32) return estep_mfma_groups_launch<32>(sc, dX, N, Dj, M, w, mu, var, dstats, plen, st);
-    if (Dj <= 48) return estep_mfma_groups_launch<48>(sc, dX, N, Dj, M, w, mu, var, dstats, plen, st);
-    if (Dj <= 64) return estep_mfma_groups_launch<64>(sc, dX, N, Dj, M, w, mu, var, dstats, plen, st);
-    if (Dj <= 80) return estep_mfma_groups_launch<80>(sc, dX, N, Dj, M, w, mu, var, dstats, plen, st);
-    if (Dj <= 112) return estep_mfma_groups_launch<112>(sc, dX, N, Dj, M, w, mu, var, dstats, plen, st);
-    return estep_mfma_groups_launch<160>(sc, dX, N, Dj, M, w, mu, var, dstats, plen, st);
-  }
-  if (estep_mfma_shape(Dj, M)) return estep_mfma_dispatch(sc, dX, N, Dj, M, w, mu, var, dstats, plen, st, nullptr);
 
-  std::vector<double> hiv((size_t)M * Dj), hc(M);
+  // generic path
+  std::vector<double> hmu((size_t)M * Dj), hiv((size_t)M * Dj), hc(M);
   for (int m = 0; m < M; ++m) {
     double sl = 0.0;
     for (int d = 0; d < Dj; ++d) {
       const double v = var[d + (size_t)Dj * m];
       sl += std::log(v);
       hiv[(size_t)m * Dj + d] = 1.0 / v;
+      hmu[(size_t)m * Dj + d] = mu[d + (size_t)Dj * m];
     }
     hc[m] = (w[m] > 0.0 ? std::log(w[m]) : -INFINITY) - 0.5 * (Dj * kLog2Pi + sl);
   }
-  // generic path
-  std::vector<double> hmu((size_t)M * Dj);
-  for (int m = 0; m < M; ++m)
-    for (int d = 0; d < Dj; ++d) hmu[(size_t)m * Dj + d] = mu[d + (size_t)Dj * m];
   const size_t shmem = (size_t)Dj * 64 * sizeof(double);
   if (shmem > 150 * 1024) return fail(VCMI_ERR_ARG, "E-step: joint dimension %d too large", Dj);
   VCMI_TRY(sc.mu.reserve(hmu.size()));
@@ -1154,703 +1159,114 @@ static int estep_device_run(const double *dX, int64_t N, int Dj, int M, const do
   return VCMI_OK;
 }
 
-
-// ================================================================================================
-// Full-covariance E-step -- what `gmm[:fit](dataset.X')` does per EM iteration in the reference as shipped
-// (bin/train_gmm.jl:84-89 builds sklearn.mixture.GMM(covariance_type="full"); :103 runs EM).  SURVEY 8(f) rank 1.
-//   l_nm = log w_m + log N(x_n; mu_m, Sigma_m)   (Cholesky whitening, the fvconvert log-density kernel, MODE 1)
-//   gamma = softmax_m(l),  S0_m = sum gamma,  S1_m = sum gamma x,  S2_m = sum gamma x x',  loglik = sum_n lse_n
-// Output buffer: [S0 (M) | S1 (Dj,M) | S2 (Dj,Dj,M) | loglik] (one all-reduce).  S2_m is a weighted Gram matrix:
-// wave w of an 8-wave workgroup owns mixture 8*mg + w and accumulates the 15 lower 16x16 tiles of its 80x80 S2 with
-// v_mfma_f64_16x16x4_f64 (A operand = gamma_f * x_f[i], B operand = x_f[j], k = 4 frames per step); the x tile
-// loaded for the A operand is the same register as the B operand of the matching column tile, so a k-step costs
-// Dj/16 LDS reads + Dj/16 multiplies for Dj/16*(Dj/16+1)/2 MFMAs.  S0/S1 ride along as per-lane sums of the A operands.
-// Per-(mixture group, frame segment) partials are reduced in fixed order -> bit-identical run to run.
-// ================================================================================================
-
-// log-weighted densities (n,M) -> gamma in place; wave per frame (lanes across mixtures: coalesced rows), fixed grid.
-// The per-frame log-sum-exp values are summed per wave in frame order, then per workgroup: lsepart[blockIdx.x].
-static constexpr int kSoftmaxGrid = 2048;
-__global__ void __launch_bounds__(256)
-estep_full_softmax_kernel(double *__restrict__ LP, int M, int64_t n, double *__restrict__ lsepart, unsigned *__restrict__ fmask,
-                          int nm) {
-  // fmask (optional; mixture groups of nm, at most 32 of them): bit g of fmask[frame] = some mixture of group g has a
-  // responsibility that is not exactly zero -- the statistics kernel then visits, per group, only those frames
-  __shared__ double wsum[4];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  double acc = 0.0;
-  if (M <= 32) {
-    // Small models (the reference's own: 16 mixtures by default, 32 in its trained ones): 8, 16 or 32 lanes per frame, so a
-    // wave takes 8, 4 or 2 frames per turn instead of leaving most of its lanes idle.  The butterflies over lpf lanes give
-    // the bits of the 64-lane ones (those only add the zeros of the idle lanes first).
-    const int lpf = M <= 8 ? 8 : (M <= 16 ? 16 : 32), fpw = 64 / lpf, sub = lane / lpf, sl = lane % lpf;
-    for (int64_t f0 = ((int64_t)blockIdx.x * 4 + wave) * fpw; f0 < n; f0 += (int64_t)gridDim.x * 4 * fpw) {
-      const int64_t fr = f0 + sub;
-      const bool on = fr < n && sl < M;
-      double *l = LP + (fr < n ? fr : n - 1) * M;
-      const double lv = on ? l[sl] : -INFINITY;
-      double u = lv;
-      for (int o = lpf / 2; o >= 1; o >>= 1) u = fmax(u, __shfl_xor(u, o));
-      double sm = on ? exp(lv - u) : 0.0;
-      for (int o = lpf / 2; o >= 1; o >>= 1) sm += __shfl_xor(sm, o);
-      const double ls = u + log(sm);
-      unsigned bits = 0;
-      if (on) {
-        const double gm = exp(lv - ls);
-        l[sl] = gm;
-        if (gm != 0.0) bits = 1u << ((sl / nm) & 31);
-      }
-      if (fmask) {
-        for (int o = lpf / 2; o >= 1; o >>= 1) bits |= (unsigned)__shfl_xor((int)bits, o);
-        if (sl == 0 && fr < n) fmask[fr] = bits;
-      }
-      if (fr < n) acc += ls;
-    }
-    // the sub-groups' sums in sub-group order (lanes 0, lpf, 2 lpf, ...)
-    double t = 0.0;
-    for (int sg = 0; sg < fpw; ++sg) t += __shfl(acc, sg * lpf);
-    acc = t;
-  } else
-  for (int64_t fr = (int64_t)blockIdx.x * 4 + wave; fr < n; fr += (int64_t)gridDim.x * 4) {
-    double *l = LP + fr * M;
-    double u = -INFINITY;
-    for (int m = lane; m < M; m += 64) u = fmax(u, l[m]);
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) u = fmax(u, __shfl_xor(u, o));
-    double sm = 0.0;
-    for (int m = lane; m < M; m += 64) sm += exp(l[m] - u);
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) sm += __shfl_xor(sm, o);
-    const double ls = u + log(sm);
-    unsigned bits = 0;
-    for (int m = lane; m < M; m += 64) {
-      const double gm = exp(l[m] - ls);
-      l[m] = gm;
-      if (gm != 0.0) bits |= 1u << ((m / nm) & 31);
-    }
-    if (fmask) {
-#pragma unroll
-      for (int o = 32; o >= 1; o >>= 1) bits |= (unsigned)__shfl_xor((int)bits, o);
-      if (lane == 0) fmask[fr] = bits;
-    }
-    acc += ls;
-  }
-  if (lane == 0) wsum[wave] = acc;
-  __syncthreads();
-  if (threadIdx.x == 0) lsepart[blockIdx.x] = (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]);
+static int estep_device(const double *dX, int64_t N, int Dj, int M, const double *w, const double *mu, const double *var,
+                        double *dstats, hipStream_t st) {
+  EstepScratch &sc = scratch();
+  StreamOrderScope use(sc.order, st);
+  VCMI_TRY(use.status());
+  return estep_run(sc, dX, N, Dj, M, w, mu, var, dstats, st);
 }
 
-// deterministic sum of n doubles into out[0] (+=): one workgroup, strided partials then a sequential tail
-__global__ void __launch_bounds__(256)
-estep_sum_kernel(const double *__restrict__ v, int64_t n, double *__restrict__ out) {
-  __shared__ double part[256];
-  double s = 0.0;
-  for (int64_t i = threadIdx.x; i < n; i += 256) s += v[i];
-  part[threadIdx.x] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double t = out[0];
-    for (int i = 0; i < 256; ++i) t += part[i];
-    out[0] = t;
+int estep_device_block(const double *dX, int64_t N, int Dj, int M, const double *dparams, double *dstats, hipStream_t st) {
+  if (N == 0) {
+    VCMI_HIP(hipMemsetAsync(dstats, 0, vcmi_estep_stats_len(Dj, M) * sizeof(double), st));
+    return VCMI_OK;
   }
-}
-
-// ---- frame lists of the statistics kernel (round 4).  Its workgroup (a mixture group, a frame segment) used to stage EVERY
-// frame of its segment -- X travels once per mixture group, 8 x 320 MB through the L2 at M = 64 -- to find that 94 % of the
-// 4-frame k-steps carry only exact zeros for its mixtures: the kernel was bound by the fetch / stash / barrier chain of the
-// blocks it then skipped.  With fmask (softmax kernel) the frames of a group are listed once -- in frame order: chunk
-// histograms, a prefix per group, a stable compaction by ballot / mbcnt, nothing depends on the scheduler -- and the
-// statistics kernel walks its group's list.  list[g * n + pos] = frame; total[g] = length.
-constexpr int kListChunk = 1024;
-__global__ void __launch_bounds__(256)
-estep_full_list_count_kernel(const unsigned *__restrict__ fmask, int64_t n, int G, int *__restrict__ chunkcnt) {
-  __shared__ int hist[32];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  if (tid < 32) hist[tid] = 0;
-  __syncthreads();
-  const int64_t f0 = (int64_t)blockIdx.x * kListChunk;
-  for (int i = 0; i < kListChunk / 256; ++i) {
-    const int64_t fr = f0 + 64 * (wave + 4 * i) + lane;
-    const unsigned b = fr < n ? fmask[fr] : 0u;
-    for (int g = 0; g < G; ++g) {
-      const int c = __builtin_popcountll(__builtin_amdgcn_ballot_w64((b >> g) & 1u));
-      if (lane == 0 && c) atomicAdd(&hist[g], c);
-    }
-  }
-  __syncthreads();
-  if (tid < G) chunkcnt[(size_t)blockIdx.x * G + tid] = hist[tid];
-}
-// one workgroup per group: exclusive prefix of chunkcnt[.][g] over the chunks (in place), total[g]
-__global__ void __launch_bounds__(256)
-estep_full_list_scan_kernel(int *__restrict__ chunkcnt, int64_t nchunks, int G, int *__restrict__ total) {
-  __shared__ int part[256];
-  const int g = blockIdx.x, tid = threadIdx.x;
-  const int64_t per = (nchunks + 255) / 256, lo = std::min<int64_t>(nchunks, tid * per), hi = std::min<int64_t>(nchunks, lo + per);
-  int sum = 0;
-  for (int64_t c = lo; c < hi; ++c) sum += chunkcnt[c * G + g];
-  part[tid] = sum;
-  __syncthreads();
-  if (tid == 0) {
-    int run = 0;
-    for (int i = 0; i < 256; ++i) {
-      const int v = part[i];
-      part[i] = run;
-      run += v;
-    }
-    total[g] = run;
-  }
-  __syncthreads();
-  int run = part[tid];
-  for (int64_t c = lo; c < hi; ++c) {
-    const int v = chunkcnt[c * G + g];
-    chunkcnt[c * G + g] = run;
-    run += v;
-  }
-}
-__global__ void __launch_bounds__(256)
-estep_full_list_fill_kernel(const unsigned *__restrict__ fmask, int64_t n, int G, const int *__restrict__ chunkoff,
-                            int *__restrict__ list) {
-  __shared__ int rowcnt[16][32];           // frames of group g in row r of the chunk -> exclusive prefix over the rows
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int64_t f0 = (int64_t)blockIdx.x * kListChunk;
-  unsigned b[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int r = wave + 4 * i;
-    const int64_t fr = f0 + 64 * r + lane;
-    b[i] = fr < n ? fmask[fr] : 0u;
-    for (int g = 0; g < G; ++g) {
-      const int c = __builtin_popcountll(__builtin_amdgcn_ballot_w64((b[i] >> g) & 1u));
-      if (lane == 0) rowcnt[r][g] = c;
-    }
-  }
-  __syncthreads();
-  if (tid < G) {
-    int run = 0;
-    for (int r = 0; r < 16; ++r) {
-      const int v = rowcnt[r][tid];
-      rowcnt[r][tid] = run;
-      run += v;
-    }
-  }
-  __syncthreads();
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int r = wave + 4 * i;
-    const int64_t fr = f0 + 64 * r + lane;
-    for (int g = 0; g < G; ++g) {
-      const unsigned long long mask = __builtin_amdgcn_ballot_w64((b[i] >> g) & 1u);
-      if ((b[i] >> g) & 1u) {
-        const int below = __builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0));
-        list[(size_t)g * n + chunkoff[(size_t)blockIdx.x * G + g] + rowcnt[r][g] + below] = (int)fr;
-      }
-    }
-  }
-}
-
-static constexpr int kFullFB = 32;   // frames per staged block (double-buffered in LDS)
-
-// lower tiles of a (16 NTL)^2 symmetric matrix in row-major order: tile t -> (row tile a, column tile j <= a)
-__host__ __device__ constexpr int full_tile_a(int t) {
-  int a = 0;
-  while ((a + 1) * (a + 2) / 2 <= t) ++a;
-  return a;
-}
-__host__ __device__ constexpr int full_tile_j(int t) { return t - full_tile_a(t) * (full_tile_a(t) + 1) / 2; }
-
-// the tiles [T0, T0 + NTP) as compile-time tables: row / column tile of each, and which x tiles they read as rows / columns
-template <int T0, int NTP>
-struct FullTileList {
-  int a[NTP > 0 ? NTP : 1], j[NTP > 0 ? NTP : 1];
-  unsigned rows, cols;
-  constexpr FullTileList() : a{}, j{}, rows(0), cols(0) {
-    for (int t = 0; t < NTP; ++t) {
-      a[t] = full_tile_a(T0 + t);
-      j[t] = full_tile_j(T0 + t);
-      rows |= 1u << a[t];
-      cols |= 1u << j[t];
-    }
-  }
-};
-
-template <int DJ, int PARTS>
-struct FullStatsCfg {
-  static constexpr int NTL = DJ / 16, NTILES = NTL * (NTL + 1) / 2;
-  static constexpr int TPP = (NTILES + PARTS - 1) / PARTS;     // tiles per part (consecutive tiles: few distinct operands)
-  static constexpr int NM = 8 / PARTS;                          // mixtures per workgroup
-  // row stride == 16 (mod 32) doubles: the four 16-lane groups of an operand read (4 consecutive frames) then fall in
-  // disjoint halves of the 64 LDS banks per half-wave
-  static constexpr int RSX = (DJ % 32 == 16) ? DJ : DJ + 16;
-  static constexpr size_t LDS_BYTES = ((size_t)2 * kFullFB * RSX + 2 * kFullFB * 8) * sizeof(double);
-};
-
-// The body of one wave: mixture `m`, tiles [PART TPP, (PART+1) TPP) of its S2 (and, for the last part, S0 and S1).
-// Wave w of an 8-wave workgroup owns mixture NM mg + w / PARTS and part w % PARTS: at DJ = 80 one wave holds all 15 lower
-// tiles of its mixture (PARTS = 1); at DJ = 160 the 55 tiles (220 accumulator registers) are shared by four waves.
-template <int DJ, int PARTS, int PART>
-__device__ __forceinline__ void estep_full_stats_body(const double *__restrict__ X, int64_t n0, int64_t f_begin, int64_t f_end,
-                                                      int M, int mg, const double *__restrict__ G, double *__restrict__ P,
-                                                      double *xs, double *gs, int dj, const int *__restrict__ lst,
-                                                      unsigned long long *__restrict__ mfma_count) {
-  // lst (optional): positions [f_begin, f_end) index this mixture group's frame list instead of the frames themselves
-  using C = FullStatsCfg<DJ, PARTS>;
-  constexpr int NTL = C::NTL, RSX = C::RSX, FB = kFullFB, NM = C::NM;
-  constexpr int T0 = PART * C::TPP, T1 = (T0 + C::TPP < C::NTILES) ? T0 + C::TPP : C::NTILES, NTP = T1 - T0;
-  constexpr bool kFirstMoments = PART == PARTS - 1;        // the last part has the fewest tiles: it also sums S0 and S1
-  constexpr int NPF = (FB * DJ + 511) / 512;               // staged doubles per thread per block
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int lcol = lane & 15, lgrp = lane >> 4;
-  const int ml = wave / PARTS, m = mg * NM + ml;           // this wave's mixture (may be >= M: then gamma is staged as 0)
-
-  d4 acc[NTP > 0 ? NTP : 1];
-#pragma unroll
-  for (int t = 0; t < NTP; ++t) acc[t] = d4{0, 0, 0, 0};
-  double s1[NTL], s0 = 0.0;
-#pragma unroll
-  for (int a = 0; a < NTL; ++a) s1[a] = 0.0;
-  int nmfma = 0;               // MFMAs this wave issued (measurement: mfma_count, optional)
-
-  double pf[NPF], pg = 0.0;
-  const int gf = tid / NM, gq = tid % NM;                 // gamma staging: FB frames x NM mixtures
-  const int gm_idx = mg * NM + gq;
-  // element i of this thread: row (frame of the block) and column of the staged image (dj <= DJ is the data's dimension;
-  // the columns dj .. DJ-1 of the LDS image are never written: they only reach accumulators that are not stored)
-  int rowi[NPF], coli[NPF];
-#pragma unroll
-  for (int i = 0; i < NPF; ++i) {
-    const int e = tid + 512 * i;
-    rowi[i] = e / dj;
-    coli[i] = e - rowi[i] * dj;
-  }
-  // the frames of the block that is fetched NEXT (list mode: read one block ahead of the rows they address)
-  int fidx[NPF], gfidx = 0;                               // (a call's chunk has at most 2^20 frames)
-  auto load_idx = [&](int64_t fb) {
-#pragma unroll
-    for (int i = 0; i < NPF; ++i) {
-      const int64_t pos = fb + rowi[i];
-      fidx[i] = (lst && rowi[i] < FB && pos < f_end) ? lst[pos] : (int)pos;
-    }
-    gfidx = (lst && tid < FB * NM && fb + gf < f_end) ? lst[fb + gf] : (int)(fb + gf);
-  };
-  auto fetch = [&](int64_t fb) {                           // global -> registers
-#pragma unroll
-    for (int i = 0; i < NPF; ++i)
-      pf[i] = (rowi[i] < FB && fb + rowi[i] < f_end) ? X[(n0 + (int64_t)fidx[i]) * dj + coli[i]] : 0.0;
-    pg = (tid < FB * NM && fb + gf < f_end && gm_idx < M) ? G[(int64_t)gfidx * M + gm_idx] : 0.0;
-  };
-  auto stash = [&](int buf) {                              // registers -> LDS
-#pragma unroll
-    for (int i = 0; i < NPF; ++i)
-      if (rowi[i] < FB) xs[buf * FB * RSX + rowi[i] * RSX + coli[i]] = pf[i];
-    if (tid < FB * NM) gs[buf * FB * 8 + gf * NM + gq] = pg;
-  };
-  constexpr FullTileList<T0, NTP> TL{};                   // which x tiles this part reads, which of them it scales by gamma
-
-  if (dj < DJ) {                                          // padding columns: finite values (they are multiplied, never stored)
-    for (int e = tid; e < 2 * FB * RSX; e += 512) xs[e] = 0.0;
-    __syncthreads();
-  }
-  if (f_begin < f_end) {
-    load_idx(f_begin);
-    fetch(f_begin);
-    stash(0);
-    load_idx(f_begin + FB);
-  }
-  __syncthreads();
-  int buf = 0;
-  for (int64_t fb = f_begin; fb < f_end; fb += FB, buf ^= 1) {
-    const bool more = fb + FB < f_end;
-    if (more) {
-      fetch(fb + FB);
-      load_idx(fb + 2 * FB);
-    }
-    const double *xb = xs + buf * FB * RSX, *gb = gs + buf * FB * 8;
-#pragma unroll 2
-    for (int ks = 0; ks < FB / 4; ++ks) {
-      const int f = 4 * ks + lgrp;
-      const double gm = gb[f * NM + ml];
-      // the four frames of the k-step all have gamma == 0 exactly for this wave's mixture (l_m more than 745 nats under
-      // the frame's maximum): the products add exactly nothing -- skipped (wave-uniform; bit-identical statistics)
-      if (__builtin_amdgcn_ballot_w64(gm != 0.0) == 0) continue;
-      nmfma += NTP;
-      const double *xr = xb + f * RSX + lcol;
-      double xv[NTL], ax[NTL];
-#pragma unroll
-      for (int a = 0; a < NTL; ++a) {
-        if (kFirstMoments || (((TL.rows | TL.cols) >> a) & 1u)) xv[a] = xr[16 * a];
-        if (kFirstMoments || ((TL.rows >> a) & 1u)) ax[a] = gm * xv[a];
-        if (kFirstMoments) s1[a] += ax[a];
-      }
-      if (kFirstMoments) s0 += gm;
-#pragma unroll
-      for (int t = 0; t < NTP; ++t)
-        acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(ax[TL.a[t]], xv[TL.j[t]], acc[t], 0, 0, 0);
-    }
-    if (more) stash(buf ^ 1);
-    __syncthreads();
-  }
-  if (mfma_count && lane == 0) atomicAdd(mfma_count, (unsigned long long)nmfma);
-  if (m >= M) return;
-  // partial statistics of this (mixture, segment) in the final layout [S0 | S1 | S2 | loglik]
-  if (kFirstMoments) {
-    s0 += __shfl_xor(s0, 16);
-    s0 += __shfl_xor(s0, 32);
-    if (lane == 0) P[m] = s0;
-#pragma unroll
-    for (int a = 0; a < NTL; ++a) {
-      double v = s1[a];
-      v += __shfl_xor(v, 16);
-      v += __shfl_xor(v, 32);
-      if (lgrp == 0 && 16 * a + lcol < dj) P[M + (size_t)m * dj + 16 * a + lcol] = v;
-    }
-  }
-  double *S2 = P + M + (size_t)M * dj + (size_t)m * dj * dj;      // (dj,dj) column-major
-#pragma unroll
-  for (int t = 0; t < NTP; ++t) {
-    const int a = TL.a[t], j = TL.j[t];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int i = 16 * a + lgrp + 4 * r, jc = 16 * j + lcol;    // D[i][jc]
-      if ((a != j || i >= jc) && i < dj && jc < dj) {              // diagonal tiles: lower part only, then mirrored
-        S2[i + (size_t)dj * jc] = acc[t][r];
-        S2[jc + (size_t)dj * i] = acc[t][r];
-      }
-    }
-  }
-}
-
-template <int DJ, int PARTS>
-__global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2)))
-estep_full_stats_kernel(const double *__restrict__ X, int64_t n0, int64_t n, int M, const double *__restrict__ G,
-                        double *__restrict__ part, int64_t plen, int dj, const int *__restrict__ lists,
-                        const int *__restrict__ totals, unsigned long long *__restrict__ mfma_count) {
-  static_assert(DJ % 16 == 0, "full-covariance MFMA statistics need Dj to be a multiple of 16");
-  static_assert(PARTS == 1 || PARTS == 2 || PARTS == 4, "waves per mixture");
-  using C = FullStatsCfg<DJ, PARTS>;
-  extern __shared__ double fsm[];
-  double *xs = fsm;                                     // [2][FB][RSX]
-  double *gs = fsm + 2 * kFullFB * C::RSX;              // [2][FB][8]
-  // grid = (frame segments, mixture groups): consecutive workgroups go to consecutive XCDs, so with the segment as the
-  // FAST index the mixture groups that read one segment of X share an XCD (when the segment count is a multiple of 8)
-  // and X reaches that L2 once instead of once per mixture group
-  const int mg = blockIdx.y, seg = blockIdx.x, nsegs = gridDim.x;
-  // with frame lists the segment is a range of POSITIONS in this mixture group's list (its length is on the device)
-  const int64_t len = lists ? (int64_t)totals[mg] : n;
-  const int *lst = lists ? lists + (size_t)mg * n : nullptr;
-  const int64_t seglen = (len + nsegs - 1) / nsegs;
-  const int64_t f_begin = std::min<int64_t>(len, seg * seglen), f_end = (f_begin + seglen < len) ? f_begin + seglen : len;
-  double *P = part + (size_t)seg * plen;
-  const int prt = (threadIdx.x >> 6) % PARTS;          // wave-uniform; every branch runs the same number of barriers
-  if (PARTS == 1 || prt == 0) estep_full_stats_body<DJ, PARTS, 0>(X, n0, f_begin, f_end, M, mg, G, P, xs, gs, dj, lst, mfma_count);
-  else if (PARTS == 2 || prt == 1) estep_full_stats_body<DJ, PARTS, 1>(X, n0, f_begin, f_end, M, mg, G, P, xs, gs, dj, lst, mfma_count);
-  else if (prt == 2) estep_full_stats_body<DJ, PARTS, (PARTS > 2 ? 2 : 0)>(X, n0, f_begin, f_end, M, mg, G, P, xs, gs, dj, lst, mfma_count);
-  else estep_full_stats_body<DJ, PARTS, (PARTS > 3 ? 3 : 0)>(X, n0, f_begin, f_end, M, mg, G, P, xs, gs, dj, lst, mfma_count);
-}
-
-// generic statistics (any Dj): thread per lower-triangle element of one mixture's S2 (+ S1, S0), sequential over the
-// frames of one segment
-__global__ void __launch_bounds__(256)
-estep_full_stats_generic_kernel(const double *__restrict__ X, int64_t n0, int64_t n, int Dj, int M,
-                                const double *__restrict__ G, double *__restrict__ part, int64_t plen) {
-  const int m = blockIdx.x;
-  const int64_t seglen = (n + gridDim.y - 1) / gridDim.y;
-  const int64_t f_begin = blockIdx.y * seglen, f_end = (f_begin + seglen < n) ? f_begin + seglen : n;
-  double *P = part + (size_t)blockIdx.y * plen;
-  double *S2 = P + M + (size_t)M * Dj + (size_t)m * Dj * Dj;
-  const int ntri = Dj * (Dj + 1) / 2;
-  for (int e = threadIdx.x; e < ntri + Dj + 1; e += 256) {
-    double s = 0.0;
-    if (e < ntri) {
-      int i = (int)((sqrt(8.0 * e + 1.0) - 1.0) / 2.0);
-      while (i * (i + 1) / 2 > e) --i;
-      while ((i + 1) * (i + 2) / 2 <= e) ++i;
-      const int j = e - i * (i + 1) / 2;
-      for (int64_t f = f_begin; f < f_end; ++f) s = fma(G[f * M + m] * X[(n0 + f) * Dj + i], X[(n0 + f) * Dj + j], s);
-      S2[i + (size_t)Dj * j] = s;
-      S2[j + (size_t)Dj * i] = s;
-    } else if (e < ntri + Dj) {
-      const int d = e - ntri;
-      for (int64_t f = f_begin; f < f_end; ++f) s = fma(G[f * M + m], X[(n0 + f) * Dj + d], s);
-      P[M + (size_t)m * Dj + d] = s;
-    } else {
-      for (int64_t f = f_begin; f < f_end; ++f) s += G[f * M + m];
-      P[m] = s;
-    }
-  }
-}
-
-struct EstepFullScratch {
-  DevBuf<double> LP, lse, part, X, stats, params;
-  DevBuf<int> flag;
-  DevBuf<unsigned long long> mfma_count;   // optional measurement counter of the statistics kernel (vcmi_debug_estep_full_mfma)
-  DevBuf<int> lists;        // frame lists of the statistics kernel: [fmask (n) | chunk counts (nchunks, G) | totals (G) | lists (G, n)]
-  vcmi_gmmmap *px = nullptr;
-  StreamOrder order;   // calls of one thread on different streams share the buffers above
-  ~EstepFullScratch() { delete px; }
-};
-static EstepFullScratch &full_scratch() {
-  static thread_local EstepFullScratch s;
-  return s;
-}
-
-// statistics of N device-resident frames under the prepared p(x) handle -> dstats (zeroed here); asynchronous on st
-static int estep_full_core_run(vcmi_gmmmap *px, const double *dX, int64_t N, int Dj, int M, double *dstats, hipStream_t st);
-
-static int estep_full_core(vcmi_gmmmap *px, const double *dX, int64_t N, int Dj, int M, double *dstats, hipStream_t st) {
-  EstepFullScratch &sc = full_scratch();
-  VCMI_TRY(sc.order.enter(st));
-  const int rc = estep_full_core_run(px, dX, N, Dj, M, dstats, st);
-  (void)sc.order.leave(st);
-  return rc;
-}
-
-static int estep_full_core_run(vcmi_gmmmap *px, const double *dX, int64_t N, int Dj, int M, double *dstats, hipStream_t st) {
-  const int64_t plen = (int64_t)M * (1 + Dj + (int64_t)Dj * Dj) + 1;
-  VCMI_HIP(hipMemsetAsync(dstats, 0, plen * sizeof(double), st));
-  if (N == 0) return VCMI_OK;
-  EstepFullScratch &sc = full_scratch();
-  const int64_t chunk = std::min<int64_t>(N, (int64_t)1 << 20);
-  VCMI_TRY(sc.LP.reserve((size_t)chunk * M));
-  VCMI_TRY(sc.lse.reserve((size_t)kSoftmaxGrid));
-  // frame segments (grid.x): one 8-wave workgroup per CU in a single round, whatever the mixture count; a workgroup
-  // holds 8 mixtures up to Dj = 80 and 2 (four waves per mixture) beyond
-  // MFMA statistics for every Dj <= 160, in the smallest of the instantiations 32, 48, 64, 80 (one wave per mixture) and
-  // 96, 128, 160 (four) that holds it
-  const bool mfma = Dj <= 160 && !debug_flag(kDbgEstepGeneric);
-  const int nm = (!mfma || Dj <= 80) ? 8 : 2;
-  const int mgroups = (M + nm - 1) / nm;
-  const int nseg = std::max(1, (256 + mgroups - 1) / mgroups);
-  VCMI_TRY(sc.part.reserve((size_t)nseg * plen));
-  for (int64_t n0 = 0; n0 < N; n0 += chunk) {
-    const int64_t n = std::min<int64_t>(chunk, N - n0);
-    VCMI_TRY(gmmmap_logdens_device(px, dX + n0 * Dj, Dj, n, sc.LP.p, st));
-    // frame lists per mixture group (MFMA statistics, at most 32 groups, enough frames to matter)
-    const bool use_lists = mfma && mgroups <= 32 && n >= 4096 && !debug_flag(kDbgEstepFullNoLists);
-    unsigned *fmask = nullptr;
-    int *chunkcnt = nullptr, *totals = nullptr, *lists = nullptr;
-    const int64_t nlc = (n + kListChunk - 1) / kListChunk;
-    if (use_lists) {
-      VCMI_TRY(sc.lists.reserve((size_t)n + (size_t)nlc * mgroups + mgroups + (size_t)mgroups * n));
-      fmask = reinterpret_cast<unsigned *>(sc.lists.p);
-      chunkcnt = sc.lists.p + n;
-      totals = chunkcnt + (size_t)nlc * mgroups;
-      lists = totals + mgroups;
-    }
-    hipLaunchKernelGGL(estep_full_softmax_kernel, dim3(kSoftmaxGrid), dim3(256), 0, st, sc.LP.p, M, n, sc.lse.p, fmask, nm);
-    hipLaunchKernelGGL(estep_sum_kernel, dim3(1), dim3(256), 0, st, sc.lse.p, (int64_t)kSoftmaxGrid, dstats + (plen - 1));
-    if (use_lists) {
-      hipLaunchKernelGGL(estep_full_list_count_kernel, dim3((unsigned)nlc), dim3(256), 0, st, fmask, n, mgroups, chunkcnt);
-      hipLaunchKernelGGL(estep_full_list_scan_kernel, dim3((unsigned)mgroups), dim3(256), 0, st, chunkcnt, nlc, mgroups, totals);
-      hipLaunchKernelGGL(estep_full_list_fill_kernel, dim3((unsigned)nlc), dim3(256), 0, st, fmask, n, mgroups, chunkcnt, lists);
-    }
-    VCMI_HIP(hipMemsetAsync(sc.part.p, 0, (size_t)nseg * plen * sizeof(double), st));
-    const dim3 grid(nseg, mgroups);
-    if (mfma) {
-      auto launch = [&](auto kern, size_t lds) -> int {
-        static std::atomic<bool> attr_done[64];           // per instantiation (the lambda is generic) and per device
-        int dev = 0;
-        (void)hipGetDevice(&dev);
-        if (!attr_done[dev & 63].load(std::memory_order_acquire)) {
-          VCMI_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-          attr_done[dev & 63].store(true, std::memory_order_release);
-        }
-        hipLaunchKernelGGL(kern, grid, dim3(512), lds, st, dX, n0, n, M, sc.LP.p, sc.part.p, plen, Dj, (const int *)lists,
-                           (const int *)totals, sc.mfma_count.p);
-        return VCMI_OK;
-      };
-      if (Dj <= 32) VCMI_TRY(launch(estep_full_stats_kernel<32, 1>, FullStatsCfg<32, 1>::LDS_BYTES));
-      else if (Dj <= 48) VCMI_TRY(launch(estep_full_stats_kernel<48, 1>, FullStatsCfg<48, 1>::LDS_BYTES));
-      else if (Dj <= 64) VCMI_TRY(launch(estep_full_stats_kernel<64, 1>, FullStatsCfg<64, 1>::LDS_BYTES));
-      else if (Dj <= 80) VCMI_TRY(launch(estep_full_stats_kernel<80, 1>, FullStatsCfg<80, 1>::LDS_BYTES));
-      else if (Dj <= 96) VCMI_TRY(launch(estep_full_stats_kernel<96, 4>, FullStatsCfg<96, 4>::LDS_BYTES));
-      else if (Dj <= 128) VCMI_TRY(launch(estep_full_stats_kernel<128, 4>, FullStatsCfg<128, 4>::LDS_BYTES));
-      else VCMI_TRY(launch(estep_full_stats_kernel<160, 4>, FullStatsCfg<160, 4>::LDS_BYTES));
-    } else {
-      hipLaunchKernelGGL(estep_full_stats_generic_kernel, dim3(M, nseg), dim3(256), 0, st, dX, n0, n, Dj, M, sc.LP.p,
-                         sc.part.p, plen);
-    }
-    // the loglik slot of the partial rows is zero, so the generic reduction leaves dstats[plen-1] (set above) intact
-    estep_reduce_launch(sc.part.p, nseg, plen, dstats, st);
-    VCMI_HIP(hipGetLastError());
-  }
-  return VCMI_OK;
-}
-
-static int read_pd_flag(const int *d_flag, hipStream_t st) {
-  int h = 0;
-  VCMI_HIP(hipMemcpyAsync(&h, d_flag, sizeof(int), hipMemcpyDeviceToHost, st));
-  VCMI_HIP(hipStreamSynchronize(st));
-  if (h) return fail(VCMI_ERR_NOT_PD, "covariance of mixture %d is not positive definite", h);
-  return VCMI_OK;
-}
-
-// one E-step from HOST parameters: upload (Dj*Dj*M doubles), Cholesky whitening of every mixture on the device
-// (px_prep_kernel; host fallback for very large Dj), statistics, then the stream is drained (the p(x) handle and the
-// parameter staging buffers persist per host thread and are rewritten by the next call).
-static int estep_full_device(const double *dX, int64_t N, int Dj, int M, const double *w, const double *mu,
-                             const double *sigma, double *dstats, hipStream_t st) {
-  if (N < 0 || Dj < 1 || M < 1) return fail(VCMI_ERR_DIM, "E-step: N=%lld Dj=%d M=%d invalid", (long long)N, Dj, M);
-  if (!w || !mu || !sigma || !dstats || (N > 0 && !dX)) return fail(VCMI_ERR_ARG, "E-step: NULL argument");
-  EstepFullScratch &sc = full_scratch();
-  if (N == 0) return estep_full_core(nullptr, dX, 0, Dj, M, dstats, st);
-  VCMI_TRY(sc.order.enter(st));   // the parameter staging and the p(x) handle are rewritten before the core runs
-  if (gmm_px_device_prepare_supported(Dj)) {
-    const size_t dd = (size_t)Dj * Dj;
-    VCMI_TRY(sc.params.reserve((size_t)M * (1 + Dj + dd)));
-    VCMI_TRY(sc.flag.reserve(1));
-    double *dw = sc.params.p, *dmu = dw + M, *dsig = dmu + (size_t)M * Dj;
-    VCMI_TRY(staged_upload(dw, w, sizeof(double) * M, st));      // (through the pinned ring: hostpipe.hpp, upload_now)
-    VCMI_TRY(staged_upload(dmu, mu, sizeof(double) * M * Dj, st));      // (through the pinned ring: hostpipe.hpp, upload_now)
-    VCMI_TRY(staged_upload(dsig, sigma, sizeof(double) * M * dd, st));      // (through the pinned ring: hostpipe.hpp, upload_now)
-    VCMI_HIP(hipMemsetAsync(sc.flag.p, 0, sizeof(int), st));
-    VCMI_TRY(gmm_px_prepare_device(&sc.px, dw, dmu, dsig, Dj, M, sc.flag.p, st));
-    VCMI_TRY(estep_full_core(sc.px, dX, N, Dj, M, dstats, st));
-    return read_pd_flag(sc.flag.p, st);
-  }
-  VCMI_TRY(gmm_px_create(w, mu, sigma, Dj, M, &sc.px));
-  VCMI_TRY(estep_full_core(sc.px, dX, N, Dj, M, dstats, st));
-  VCMI_HIP(hipStreamSynchronize(st));
-  return VCMI_OK;
-}
-
-// ------------------------------------------------------------------------------------------------
-// EM state resident on the device (bin/train_gmm.jl:84-103: sklearn.mixture.GMM(covariance_type="full",
-// min_covar).fit): parameters, statistics and whitening blocks stay in HBM; one iteration is
-//   estep (local statistics) -> [caller all-reduces the statistics buffer over RCCL] -> mstep (+ whitening prep).
-// ------------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(256)
-em_mstep_full_kernel(const double *__restrict__ stats, int Dj, int M, double min_covar, double *__restrict__ w,
-                     double *__restrict__ mu, double *__restrict__ sigma, const int *__restrict__ flag) {
-  __shared__ double red[256];
-  __shared__ double mus[256];
-  const int tid = threadIdx.x, m = blockIdx.x;
-  // a covariance of the CURRENT parameters was reported not positive definite: the statistics computed under them are NaN
-  // for every mixture.  Keep the parameters, so that the preparation that follows reports the same mixture again (and not
-  // the last one of a model that is NaN throughout) and vcmi_gmm_em_get still shows the model that failed.
-  if (*flag) return;
-  const double eps = 2.220446049250313e-16;
-  double t = 0.0;
-  for (int k = tid; k < M; k += 256) t += stats[k];
-  red[tid] = t;
-  __syncthreads();
-  for (int o = 128; o >= 1; o >>= 1) {
-    if (tid < o) red[tid] += red[tid + o];
-    __syncthreads();
-  }
-  const double tot = red[0], s0 = stats[m];
-  const double inv = 1.0 / (s0 + 10 * eps);
-  const double *S1 = stats + M + (size_t)m * Dj;
-  const double *S2 = stats + M + (size_t)M * Dj + (size_t)m * Dj * Dj;
-  for (int d = tid; d < Dj; d += 256) {
-    const double v = S1[d] * inv;
-    mus[d] = v;
-    mu[(size_t)m * Dj + d] = v;
-  }
-  if (tid == 0) w[m] = s0 / (tot + 10 * eps) + eps;
-  __syncthreads();
-  for (int e = tid; e < Dj * Dj; e += 256) {
-    const int c = e / Dj, r = e - c * Dj;
-    sigma[(size_t)m * Dj * Dj + e] = S2[e] * inv - mus[r] * mus[c] + (r == c ? min_covar : 0.0);
-  }
-}
-
-// The diagonal twin (estep.py:mstep_diag, operation for operation; the old sklearn GMM's covariance_type="diag" update):
-//   stats = [S0 (M) | S1 (Dj,M) | S2 (Dj,M) | loglik]  ->  raw = [w (M) | mu (Dj,M) | var (Dj,M)], the block the diagonal E-step's
-//   prep kernels read (estep_prep_kernel, estep_hard_prep_kernel).
-// One workgroup per mixture, thread d owns dimension d (Dj <= 256); the total over M in the fixed order of em_mstep_full_kernel
-// (256 strided partial sums, a tree): no floating-point atomics, the same statistics give the same bits.  The five roundings of
-// the variance are the five of the numpy expression -- no contraction into FMAs.  A variance that is not > 0 (a NaN included)
-// is reported through ctl: ctl[1] receives the smallest 1 + d + Dj m (an integer minimum: the same answer whatever the order
-// of the workgroups).  ctl[0] is the latch of an EARLIER failed M-step: the kernel then leaves `raw` alone.  ctl[2..3] carry the
-// log-likelihood of the statistics, so that the host reads it and the report in one copy.
-__global__ void __launch_bounds__(256)
-em_mstep_diag_kernel(const double *__restrict__ stats, int Dj, int M, double min_covar, double *__restrict__ raw, int *__restrict__ ctl) {
-#pragma clang fp contract(off)
-  __shared__ double red[256];
-  const int tid = threadIdx.x, m = blockIdx.x;
-  if (m == 0 && tid == 0) *reinterpret_cast<double *>(ctl + 2) = stats[(size_t)M * (1 + 2 * (size_t)Dj)];
-  if (ctl[0]) return;
-  const double eps = 2.220446049250313e-16;
-  double t = 0.0;
-  for (int k = tid; k < M; k += 256) t += stats[k];
-  red[tid] = t;
-  __syncthreads();
-  for (int o = 128; o >= 1; o >>= 1) {
-    if (tid < o) red[tid] += red[tid + o];
-    __syncthreads();
-  }
-  const double tot = red[0], s0 = stats[m];
-  const double inv = 1.0 / (s0 + 10 * eps);
-  if (tid == 0) raw[m] = s0 / (tot + 10 * eps) + eps;
-  if (tid < Dj) {
-    const size_t e = (size_t)m * Dj + tid;
-    const double s1 = stats[M + e], s2 = stats[M + (size_t)M * Dj + e];
-    const double mean = s1 * inv;
-    const double v = s2 * inv - ((2.0 * mean) * s1) * inv + mean * mean + min_covar;
-    raw[M + e] = mean;
-    raw[M + (size_t)M * Dj + e] = v;
-    if (!(v > 0.0)) atomicMin(ctl + 1, (int)(1 + e));
-  }
-}
-
-}  // namespace vcmi
-
-struct vcmi_gmm_em {
-  int Dj = 0, M = 0, device = 0;
-  double min_covar = 0.0;
-  bool prepared = false;
-  vcmi::DevBuf<double> params;   // [w (M) | mu (Dj,M) | sigma (Dj,Dj,M)]
-  vcmi::DevBuf<int> flag;
-  vcmi_gmmmap *px = nullptr;
-  ~vcmi_gmm_em() { delete px; }
-  double *w() { return params.p; }
-  double *mu() { return params.p + M; }
-  double *sigma() { return params.p + M + (size_t)M * Dj; }
-  int64_t plen() const { return (int64_t)M * (1 + Dj + (int64_t)Dj * Dj) + 1; }
-};
-
-namespace vcmi {
-static int em_prepare(vcmi_gmm_em *h, hipStream_t st) {
-  // a host preparation that fails (not positive definite) deletes the handle: the state is unprepared until one succeeds,
-  // so that the next E-step prepares (and reports) again instead of running on a handle that is gone
-  h->prepared = false;
-  if (gmm_px_device_prepare_supported(h->Dj)) {
-    VCMI_TRY(gmm_px_prepare_device(&h->px, h->w(), h->mu(), h->sigma(), h->Dj, h->M, h->flag.p, st));
-  } else {
-    // dimensions without a device preparation (198 < Dj <= 256: px_prep_kernel serves Dj <= 99, px_prep_packed_kernel
-    // 100 <= Dj <= 198 -- and 99 < Dj whose padded size has an MFMA instantiation; there is none today): Cholesky on the
-    // host, with a stream synchronisation
-    const size_t dd = (size_t)h->Dj * h->Dj;
-    std::vector<double> hw(h->M), hmu((size_t)h->M * h->Dj), hs((size_t)h->M * dd);
+  EstepScratch &sc = scratch();
+  if (!estep_mfma_shape(Dj, M)) {
+    // odd Dj, M > 128, Dj > 160: the host code of these shapes pads, regroups or transposes the parameters
+    const size_t nraw = (size_t)M * (1 + 2 * (size_t)Dj);
+    sc.hblock.resize(nraw);
+    VCMI_HIP(hipMemcpyAsync(sc.hblock.data(), dparams, nraw * sizeof(double), hipMemcpyDeviceToHost, st));
     VCMI_HIP(hipStreamSynchronize(st));
-    VCMI_HIP(hipMemcpy(hw.data(), h->w(), hw.size() * 8, hipMemcpyDeviceToHost));
-    VCMI_HIP(hipMemcpy(hmu.data(), h->mu(), hmu.size() * 8, hipMemcpyDeviceToHost));
-    VCMI_HIP(hipMemcpy(hs.data(), h->sigma(), hs.size() * 8, hipMemcpyDeviceToHost));
-    VCMI_TRY(gmm_px_create(hw.data(), hmu.data(), hs.data(), h->Dj, h->M, &h->px));
+    const double *hw = sc.hblock.data(), *hmu = hw + M, *hvar = hmu + (size_t)M * Dj;
+    return estep_device(dX, N, Dj, M, hw, hmu, hvar, dstats, st);
   }
-  h->prepared = true;
+  StreamOrderScope use(sc.order, st);
+  VCMI_TRY(use.status());
+  sc.last_hard = false;
+  return estep_mfma(sc, dX, N, Dj, M, EstepParams::device(dparams), dstats, st);
+}
+
+// Host-pointer E-step shared by the diagonal and the full-covariance entry points: X goes up through the pinned staging
+// ring; with a device group (vcmi_set_devices) member i takes the contiguous frame block [lo, hi), computes its local
+// statistics, and ONE ncclAllReduce(sum) of the packed buffer over RCCL leaves the global statistics on every member
+// (SURVEY 8e) -- member 0 returns them.  Two group phases, so that a member that failed never leaves the others
+// waiting inside the collective.
+struct EstepHostBuffers {
+  DevBuf<double> X, stats;      // a member's frames and its packed statistics
+};
+static EstepHostBuffers &host_buffers() {      // (of the calling thread without a group, of each member's thread with one)
+  static thread_local EstepHostBuffers b;
+  return b;
+}
+int estep_host(EstepDeviceFn dev, const double *X, int64_t N, int Dj, int M, const double *w, const double *mu, const double *cov,
+               int64_t plen, size_t s2len, double *S0, double *S1, double *S2, double *loglik) {
+  std::vector<double> h((size_t)plen, 0.0);
+  auto local = [&](int64_t lo, int64_t hi) -> int {
+    EstepHostBuffers &buf = host_buffers();
+    const int64_t n = hi - lo;
+    VCMI_TRY(buf.X.reserve((size_t)std::max<int64_t>(n, 1) * Dj));
+    VCMI_TRY(buf.stats.reserve((size_t)plen));
+    if (n > 0) VCMI_TRY(staged_upload(buf.X.p, X + (size_t)lo * Dj, (size_t)n * Dj * 8, nullptr));
+    VCMI_TRY(dev(buf.X.p, n, Dj, M, w, mu, cov, buf.stats.p, nullptr));
+    VCMI_HIP(hipStreamSynchronize(nullptr));
+    return VCMI_OK;
+  };
+  const int m = group_size();
+  if (m == 0) {
+    VCMI_TRY(check_device());
+    VCMI_TRY(local(0, N));
+    VCMI_HIP(hipMemcpy(h.data(), host_buffers().stats.p, (size_t)plen * 8, hipMemcpyDeviceToHost));
+  } else {
+    VCMI_TRY(group_run(m, [&](int i) -> int {
+      int64_t lo, hi;
+      shard_range(N, i, m, &lo, &hi);
+      return local(lo, hi);
+    }));
+    VCMI_TRY(group_run(m, [&](int i) -> int {
+      EstepHostBuffers &buf = host_buffers();
+      VCMI_TRY(group_allreduce_sum(i, buf.stats.p, (size_t)plen, nullptr));
+      if (i == 0) VCMI_HIP(hipMemcpy(h.data(), buf.stats.p, (size_t)plen * 8, hipMemcpyDeviceToHost));
+      return VCMI_OK;
+    }));
+  }
+  memcpy(S0, h.data(), sizeof(double) * M);
+  memcpy(S1, h.data() + M, sizeof(double) * M * Dj);
+  memcpy(S2, h.data() + M + (size_t)M * Dj, sizeof(double) * s2len);
+  *loglik = h[(size_t)plen - 1];
   return VCMI_OK;
 }
-}  // namespace vcmi
 
-// The diagonal EM state.  `raw` holds TWO parameter blocks [w | mu (Dj,M) | var (Dj,M)]: the E-step reads block `cur`, the M-step
-// kernel writes the other one, and vcmi_gmm_em_diag_mstep -- which synchronises anyway -- makes that one current only when no
-// variance was reported.  So a failed M-step leaves the parameters its statistics were computed under, whichever workgroup
-// found the variance and whichever had already written.
-struct vcmi_gmm_em_diag {
-  int Dj = 0, M = 0, device = 0, cur = 0;
-  double min_covar = 0.0;
-  bool failed = false;           // an M-step reported a variance: the state takes no further E-step
-  int bad = 0;                   // ... 1 + d + Dj m of that variance
-  vcmi::DevBuf<double> raw;      // 2 x M (1 + 2 Dj)
-  vcmi::DevBuf<int> ctl;         // [latch | smallest bad index (INT_MAX: none) | loglik (a double)]
-  std::vector<double> host;      // the current block on the host, for the shapes without a device-parameter route
-  size_t nraw() const { return (size_t)M * (1 + 2 * (size_t)Dj); }
-  double *params() { return raw.p + (size_t)cur * nraw(); }
-  int not_pd() const {
-    return vcmi::fail(VCMI_ERR_NOT_PD, "M-step: variance (%d,%d) is not positive", (bad - 1) % Dj + 1, (bad - 1) / Dj + 1);
+int estep_check_dims(int64_t N, int Dj, int M) {
+  if (N < 0 || Dj < 1 || M < 1) return fail(VCMI_ERR_DIM, "E-step: N=%lld Dj=%d M=%d invalid", (long long)N, Dj, M);
+  return VCMI_OK;
+}
+int64_t first_bad_variance(const double *var, int Dj, int M) {
+  for (int64_t e = 0; e < (int64_t)Dj * M; ++e)
+    if (!(var[e] > 0.0)) return e;
+  return -1;
+}
+
+int mfma_count_hook(DevBuf<unsigned long long> &count, int enable, int64_t *issued) {
+  if (issued) {
+    *issued = 0;
+    if (count.p) {
+      unsigned long long h = 0;
+      VCMI_HIP(hipMemcpy(&h, count.p, sizeof(h), hipMemcpyDeviceToHost));
+      *issued = (int64_t)h;
+    }
   }
-};
+  if (enable) {
+    if (!count.p) VCMI_TRY(count.alloc(1));
+    VCMI_HIP(hipMemset(count.p, 0, sizeof(unsigned long long)));
+  } else {
+    count.release();
+  }
+  return VCMI_OK;
+}
+
+}  // namespace vcmi
 
 using namespace vcmi;
 
@@ -1861,298 +1277,23 @@ extern "C" int vcmi_estep_diag_dev(const double *dX, int64_t N, int Dj, int M, c
   return estep_device(dX, N, Dj, M, w, mu, var, dstats, as_stream(stream));
 }
 
-// Host-pointer E-step shared by the diagonal and the full-covariance entry points: X goes up through the pinned staging
-// ring; with a device group (vcmi_set_devices) member i takes the contiguous frame block [lo, hi), computes its local
-// statistics, and ONE ncclAllReduce(sum) of the packed buffer over RCCL leaves the global statistics on every member
-// (SURVEY 8e) -- member 0 returns them.  Two group phases, so that a member that failed never leaves the others
-// waiting inside the collective.
-template <class Scratch, class DevFn>
-static int estep_host(Scratch &(*get_scratch)(), const double *X, int64_t N, int Dj, int64_t plen, const DevFn &dev_fn,
-                      std::vector<double> &h) {
-  h.assign((size_t)plen, 0.0);
-  auto local = [&](int64_t lo, int64_t hi) -> int {
-    Scratch &sc = get_scratch();
-    const int64_t n = hi - lo;
-    VCMI_TRY(sc.X.reserve((size_t)std::max<int64_t>(n, 1) * Dj));
-    VCMI_TRY(sc.stats.reserve((size_t)plen));
-    if (n > 0) VCMI_TRY(staged_upload(sc.X.p, X + (size_t)lo * Dj, (size_t)n * Dj * 8, nullptr));
-    VCMI_TRY(dev_fn(sc.X.p, n, sc.stats.p));
-    VCMI_HIP(hipStreamSynchronize(nullptr));
-    return VCMI_OK;
-  };
-  const int m = group_size();
-  if (m == 0) {
-    VCMI_TRY(check_device());
-    VCMI_TRY(local(0, N));
-    VCMI_HIP(hipMemcpy(h.data(), get_scratch().stats.p, (size_t)plen * 8, hipMemcpyDeviceToHost));
-    return VCMI_OK;
-  }
-  VCMI_TRY(group_run(m, [&](int i) -> int {
-    int64_t lo, hi;
-    shard_range(N, i, m, &lo, &hi);
-    return local(lo, hi);
-  }));
-  return group_run(m, [&](int i) -> int {
-    Scratch &sc = get_scratch();
-    VCMI_TRY(group_allreduce_sum(i, sc.stats.p, (size_t)plen, nullptr));
-    if (i == 0) VCMI_HIP(hipMemcpy(h.data(), sc.stats.p, (size_t)plen * 8, hipMemcpyDeviceToHost));
-    return VCMI_OK;
-  });
-}
-
 extern "C" int vcmi_estep_diag(const double *X, int64_t N, int Dj, int M, const double *w, const double *mu,
                                const double *var, double *S0, double *S1, double *S2, double *loglik) {
   if (!S0 || !S1 || !S2 || !loglik) return fail(VCMI_ERR_ARG, "vcmi_estep_diag: NULL output");
-  if (N < 0 || Dj < 1 || M < 1) return fail(VCMI_ERR_DIM, "E-step: N=%lld Dj=%d M=%d invalid", (long long)N, Dj, M);
+  VCMI_TRY(estep_check_dims(N, Dj, M));
   if (N > 0 && !X) return fail(VCMI_ERR_ARG, "vcmi_estep_diag: NULL frames");
-  const int64_t plen = vcmi_estep_stats_len(Dj, M);
-  std::vector<double> h;
-  VCMI_TRY(estep_host<EstepScratch>(scratch, X, N, Dj, plen, [&](const double *dX, int64_t n, double *dstats) -> int {
-    return estep_device(dX, n, Dj, M, w, mu, var, dstats, nullptr);
-  }, h));
-  memcpy(S0, h.data(), sizeof(double) * M);
-  memcpy(S1, h.data() + M, sizeof(double) * M * Dj);
-  memcpy(S2, h.data() + M + (size_t)M * Dj, sizeof(double) * M * Dj);
-  *loglik = h[(size_t)plen - 1];
-  return VCMI_OK;
-}
-
-extern "C" int64_t vcmi_estep_full_stats_len(int Dj, int M) { return (int64_t)M * (1 + Dj + (int64_t)Dj * Dj) + 1; }
-
-extern "C" int vcmi_estep_full_dev(const double *dX, int64_t N, int Dj, int M, const double *w, const double *mu,
-                                   const double *sigma, double *dstats, void *stream) {
-  return estep_full_device(dX, N, Dj, M, w, mu, sigma, dstats, as_stream(stream));
-}
-
-extern "C" int vcmi_estep_full(const double *X, int64_t N, int Dj, int M, const double *w, const double *mu,
-                               const double *sigma, double *S0, double *S1, double *S2, double *loglik) {
-  if (!S0 || !S1 || !S2 || !loglik) return fail(VCMI_ERR_ARG, "vcmi_estep_full: NULL output");
-  if (N < 0 || Dj < 1 || M < 1) return fail(VCMI_ERR_DIM, "E-step: N=%lld Dj=%d M=%d invalid", (long long)N, Dj, M);
-  if (N > 0 && !X) return fail(VCMI_ERR_ARG, "vcmi_estep_full: NULL frames");
-  const int64_t plen = vcmi_estep_full_stats_len(Dj, M);
-  std::vector<double> h;
-  VCMI_TRY(estep_host<EstepFullScratch>(full_scratch, X, N, Dj, plen, [&](const double *dX, int64_t n, double *dstats) -> int {
-    return estep_full_device(dX, n, Dj, M, w, mu, sigma, dstats, nullptr);
-  }, h));
-  memcpy(S0, h.data(), sizeof(double) * M);
-  memcpy(S1, h.data() + M, sizeof(double) * M * Dj);
-  memcpy(S2, h.data() + M + (size_t)M * Dj, sizeof(double) * M * Dj * Dj);
-  *loglik = h[(size_t)plen - 1];
-  return VCMI_OK;
-}
-
-// ---- device-resident EM state --------------------------------------------------------------------
-extern "C" int vcmi_gmm_em_create(int Dj, int M, const double *w, const double *mu, const double *sigma, double min_covar,
-                                  vcmi_gmm_em **out) {
-  if (!w || !mu || !sigma || !out) return fail(VCMI_ERR_ARG, "vcmi_gmm_em_create: NULL argument");
-  *out = nullptr;
-  if (Dj < 1 || M < 1) return fail(VCMI_ERR_DIM, "vcmi_gmm_em_create: Dj=%d M=%d invalid", Dj, M);
-  if (Dj > 256)   // em_mstep_full_kernel stages the mean vector in a 256-entry LDS array
-    return fail(VCMI_ERR_DIM, "vcmi_gmm_em_create: joint dimension %d exceeds the device EM limit (256)", Dj);
-  if (!(min_covar >= 0.0)) return fail(VCMI_ERR_ARG, "vcmi_gmm_em_create: min_covar must be >= 0");
-  VCMI_TRY(check_device());
-  vcmi_gmm_em *h = new (std::nothrow) vcmi_gmm_em();
-  if (!h) return fail(VCMI_ERR_OOM, "out of host memory");
-  h->Dj = Dj;
-  h->M = M;
-  h->min_covar = min_covar;
-  (void)hipGetDevice(&h->device);
-  const size_t dd = (size_t)Dj * Dj;
-  int rc = h->params.alloc((size_t)M * (1 + Dj + dd));
-  if (rc == VCMI_OK) rc = h->flag.alloc(1);
-  if (rc != VCMI_OK) {
-    delete h;
-    return rc;
-  }
-  hipError_t e = upload_now_hip(h->w(), w, sizeof(double) * M);
-  if (e == hipSuccess) e = upload_now_hip(h->mu(), mu, sizeof(double) * M * Dj);
-  if (e == hipSuccess) e = upload_now_hip(h->sigma(), sigma, sizeof(double) * M * dd);
-  if (e == hipSuccess) e = hipMemset(h->flag.p, 0, sizeof(int));
-  if (e != hipSuccess) {
-    delete h;
-    return fail(VCMI_ERR_HIP, "vcmi_gmm_em_create: %s", hipGetErrorString(e));
-  }
-  *out = h;
-  return VCMI_OK;
-}
-
-extern "C" int vcmi_gmm_em_destroy(vcmi_gmm_em *h) {
-  delete h;
-  return VCMI_OK;
-}
-
-extern "C" int vcmi_gmm_em_estep_dev(vcmi_gmm_em *h, const double *dX, int64_t N, double *dstats, void *stream) {
-  if (!h || !dstats) return fail(VCMI_ERR_ARG, "vcmi_gmm_em_estep_dev: NULL argument");
-  if (N < 0 || (N > 0 && !dX)) return fail(VCMI_ERR_ARG, "vcmi_gmm_em_estep_dev: bad frame block");
-  hipStream_t st = as_stream(stream);
-  if (!h->prepared) VCMI_TRY(em_prepare(h, st));
-  return estep_full_core(h->px, dX, N, h->Dj, h->M, dstats, st);
-}
-
-extern "C" int vcmi_gmm_em_mstep(vcmi_gmm_em *h, const double *dstats, void *stream, double *loglik) {
-  if (!h || !dstats) return fail(VCMI_ERR_ARG, "vcmi_gmm_em_mstep: NULL argument");
-  hipStream_t st = as_stream(stream);
-  hipLaunchKernelGGL(em_mstep_full_kernel, dim3(h->M), dim3(256), 0, st, dstats, h->Dj, h->M, h->min_covar, h->w(), h->mu(),
-                     h->sigma(), h->flag.p);
-  VCMI_HIP(hipGetLastError());
-  VCMI_TRY(em_prepare(h, st));
-  double ll = 0.0;
-  VCMI_HIP(hipMemcpyAsync(&ll, dstats + (h->plen() - 1), sizeof(double), hipMemcpyDeviceToHost, st));
-  VCMI_TRY(read_pd_flag(h->flag.p, st));   // synchronises: covers the initial and the new parameters
-  if (loglik) *loglik = ll;
-  return VCMI_OK;
-}
-
-extern "C" int vcmi_gmm_em_get(vcmi_gmm_em *h, double *w, double *mu, double *sigma) {
-  if (!h || !w || !mu || !sigma) return fail(VCMI_ERR_ARG, "vcmi_gmm_em_get: NULL argument");
-  VCMI_HIP(hipDeviceSynchronize());
-  const size_t dd = (size_t)h->Dj * h->Dj;
-  VCMI_HIP(hipMemcpy(w, h->w(), sizeof(double) * h->M, hipMemcpyDeviceToHost));
-  VCMI_HIP(hipMemcpy(mu, h->mu(), sizeof(double) * h->M * h->Dj, hipMemcpyDeviceToHost));
-  VCMI_HIP(hipMemcpy(sigma, h->sigma(), sizeof(double) * h->M * dd, hipMemcpyDeviceToHost));
-  return VCMI_OK;
-}
-
-// ---- device-resident diagonal EM state -----------------------------------------------------------
-extern "C" int vcmi_gmm_em_diag_create(int Dj, int M, const double *w, const double *mu, const double *var, double min_covar,
-                                       vcmi_gmm_em_diag **out) {
-  if (!w || !mu || !var || !out) return fail(VCMI_ERR_ARG, "vcmi_gmm_em_diag_create: NULL argument");
-  *out = nullptr;
-  if (Dj < 1 || M < 1) return fail(VCMI_ERR_DIM, "vcmi_gmm_em_diag_create: Dj=%d M=%d invalid", Dj, M);
-  if (Dj > 256)   // em_mstep_diag_kernel: one thread of a 256-thread workgroup per dimension
-    return fail(VCMI_ERR_DIM, "vcmi_gmm_em_diag_create: joint dimension %d exceeds the device EM limit (256)", Dj);
-  if ((int64_t)M * Dj >= INT32_MAX) return fail(VCMI_ERR_DIM, "vcmi_gmm_em_diag_create: Dj=%d M=%d too large", Dj, M);
-  if (!(min_covar >= 0.0)) return fail(VCMI_ERR_ARG, "vcmi_gmm_em_diag_create: min_covar must be >= 0");
-  for (int m = 0; m < M; ++m)
-    for (int d = 0; d < Dj; ++d)
-      if (!(var[d + (size_t)Dj * m] > 0.0))
-        return fail(VCMI_ERR_NOT_PD, "vcmi_gmm_em_diag_create: variance (%d,%d) is not positive", d + 1, m + 1);
-  VCMI_TRY(check_device());
-  vcmi_gmm_em_diag *h = new (std::nothrow) vcmi_gmm_em_diag();
-  if (!h) return fail(VCMI_ERR_OOM, "out of host memory");
-  h->Dj = Dj;
-  h->M = M;
-  h->min_covar = min_covar;
-  (void)hipGetDevice(&h->device);
-  int rc = h->raw.alloc(2 * h->nraw());
-  if (rc == VCMI_OK) rc = h->ctl.alloc(4);
-  if (rc != VCMI_OK) {
-    delete h;
-    return rc;
-  }
-  const int ctl0[4] = {0, INT32_MAX, 0, 0};
-  hipError_t e = upload_now_hip(h->raw.p, w, sizeof(double) * M);
-  if (e == hipSuccess) e = upload_now_hip(h->raw.p + M, mu, sizeof(double) * M * Dj);
-  if (e == hipSuccess) e = upload_now_hip(h->raw.p + M + (size_t)M * Dj, var, sizeof(double) * M * Dj);
-  if (e == hipSuccess) e = upload_now_hip(h->ctl.p, ctl0, sizeof(ctl0));
-  if (e != hipSuccess) {
-    delete h;
-    return fail(VCMI_ERR_HIP, "vcmi_gmm_em_diag_create: %s", hipGetErrorString(e));
-  }
-  *out = h;
-  return VCMI_OK;
-}
-
-extern "C" int vcmi_gmm_em_diag_destroy(vcmi_gmm_em_diag *h) {
-  delete h;
-  return VCMI_OK;
-}
-
-extern "C" int vcmi_gmm_em_diag_estep_dev(vcmi_gmm_em_diag *h, const double *dX, int64_t N, double *dstats, void *stream) {
-  if (!h || !dstats) return fail(VCMI_ERR_ARG, "vcmi_gmm_em_diag_estep_dev: NULL argument");
-  if (N < 0 || (N > 0 && !dX)) return fail(VCMI_ERR_ARG, "vcmi_gmm_em_diag_estep_dev: bad frame block");
-  if (h->failed) return h->not_pd();
-  hipStream_t st = as_stream(stream);
-  const int Dj = h->Dj, M = h->M;
-  const int64_t plen = vcmi_estep_stats_len(Dj, M);
-  if (N == 0) {
-    VCMI_HIP(hipMemsetAsync(dstats, 0, plen * sizeof(double), st));
-    return VCMI_OK;
-  }
-  if (estep_mfma_shape(Dj, M)) {
-    // the parameters never leave the device: the prep kernels read the block the M-step kernel wrote (its variances are
-    // positive: vcmi_gmm_em_diag_create and every M-step since have checked them)
-    EstepScratch &sc = scratch();
-    VCMI_TRY(sc.order.enter(st));
-    sc.last_hard = false;
-    const int rc = estep_mfma_dispatch(sc, dX, N, Dj, M, nullptr, nullptr, nullptr, dstats, plen, st, h->params());
-    (void)sc.order.leave(st);
-    return rc;
-  }
-  // odd Dj, M > 128, Dj > 160: the host code of these shapes pads, regroups or transposes the parameters -- copy the block
-  // down (one stream synchronisation per E-step) and take the host-parameter path
-  h->host.resize(h->nraw());
-  VCMI_HIP(hipMemcpyAsync(h->host.data(), h->params(), h->nraw() * sizeof(double), hipMemcpyDeviceToHost, st));
-  VCMI_HIP(hipStreamSynchronize(st));
-  const double *hw = h->host.data(), *hmu = hw + M, *hvar = hmu + (size_t)M * Dj;
-  return estep_device(dX, N, Dj, M, hw, hmu, hvar, dstats, st);
-}
-
-extern "C" int vcmi_gmm_em_diag_mstep(vcmi_gmm_em_diag *h, const double *dstats, void *stream, double *loglik) {
-  if (!h || !dstats) return fail(VCMI_ERR_ARG, "vcmi_gmm_em_diag_mstep: NULL argument");
-  hipStream_t st = as_stream(stream);
-  double *next = h->raw.p + (size_t)(1 - h->cur) * h->nraw();
-  hipLaunchKernelGGL(em_mstep_diag_kernel, dim3(h->M), dim3(256), 0, st, dstats, h->Dj, h->M, h->min_covar, next, h->ctl.p);
-  VCMI_HIP(hipGetLastError());
-  struct {
-    int latch, bad;
-    double ll;
-  } r = {0, 0, 0.0};
-  static_assert(sizeof(r) == 16, "the control block is two ints and a double");
-  VCMI_HIP(hipMemcpyAsync(&r, h->ctl.p, sizeof(r), hipMemcpyDeviceToHost, st));
-  VCMI_HIP(hipStreamSynchronize(st));
-  if (loglik) *loglik = r.ll;
-  if (r.bad != INT32_MAX) {
-    if (!h->failed) {      // latch it on the device too: a later M-step kernel returns before it writes
-      const int one = 1;
-      VCMI_HIP(hipMemcpy(h->ctl.p, &one, sizeof(int), hipMemcpyHostToDevice));
-    }
-    h->failed = true;
-    h->bad = r.bad;
-    return h->not_pd();
-  }
-  h->cur = 1 - h->cur;
-  return VCMI_OK;
-}
-
-extern "C" int vcmi_gmm_em_diag_get(vcmi_gmm_em_diag *h, double *w, double *mu, double *var) {
-  if (!h || !w || !mu || !var) return fail(VCMI_ERR_ARG, "vcmi_gmm_em_diag_get: NULL argument");
-  VCMI_HIP(hipDeviceSynchronize());
-  const size_t md = (size_t)h->M * h->Dj;
-  VCMI_HIP(hipMemcpy(w, h->params(), sizeof(double) * h->M, hipMemcpyDeviceToHost));
-  VCMI_HIP(hipMemcpy(mu, h->params() + h->M, sizeof(double) * md, hipMemcpyDeviceToHost));
-  VCMI_HIP(hipMemcpy(var, h->params() + h->M + md, sizeof(double) * md, hipMemcpyDeviceToHost));
-  return VCMI_OK;
+  return estep_host(estep_device, X, N, Dj, M, w, mu, var, vcmi_estep_stats_len(Dj, M), (size_t)M * Dj, S0, S1, S2, loglik);
 }
 
 // Measurement hook (not part of include/vcmi.h; bench.py prices the diagonal E-step's matrix pipe with it): *issued (may be
 // NULL) receives the v_mfma_f64_16x16x4 instructions the MFMA E-step kernels of THIS host thread have issued since the
 // counter was last enabled; then enable != 0 (re)starts it at zero, enable == 0 switches it off.  Synchronises.
-extern "C" int vcmi_debug_estep_mfma(int enable, int64_t *issued) {
-  using namespace vcmi;
-  EstepScratch &sc = scratch();
-  if (issued) {
-    *issued = 0;
-    if (sc.mfma_count.p) {
-      unsigned long long h = 0;
-      VCMI_HIP(hipMemcpy(&h, sc.mfma_count.p, sizeof(h), hipMemcpyDeviceToHost));
-      *issued = (int64_t)h;
-    }
-  }
-  if (enable) {
-    if (!sc.mfma_count.p) VCMI_TRY(sc.mfma_count.alloc(1));
-    VCMI_HIP(hipMemset(sc.mfma_count.p, 0, sizeof(unsigned long long)));
-  } else {
-    sc.mfma_count.release();
-  }
-  return VCMI_OK;
-}
+extern "C" int vcmi_debug_estep_mfma(int enable, int64_t *issued) { return vcmi::mfma_count_hook(vcmi::scratch().mfma_count, enable, issued); }
 
 // Measurement hook (not part of include/vcmi.h): did the last diagonal E-step of this host thread take the hard-assignment
 // path (estep_hard.hpp), and how many of its frames were soft (went through estep_mfma_kernel)?  *soft = -1: the one-kernel
 // path.  Synchronises with the device.
 extern "C" int vcmi_debug_estep_last_soft(int64_t *soft) {
-  using namespace vcmi;
   if (!soft) return fail(VCMI_ERR_ARG, "vcmi_debug_estep_last_soft: NULL argument");
   EstepScratch &sc = scratch();
   *soft = -1;
@@ -2166,36 +1307,13 @@ extern "C" int vcmi_debug_estep_last_soft(int64_t *soft) {
 }
 
 extern "C" int vcmi_estep_set_path(int path) {
-  using namespace vcmi;
   if (path != VCMI_ESTEP_AUTO && path != VCMI_ESTEP_HARD && path != VCMI_ESTEP_SOFT)
     return fail(VCMI_ERR_ARG, "vcmi_estep_set_path: %d is not VCMI_ESTEP_AUTO / _HARD / _SOFT", path);
   estep_path_choice_ref() = path;
   return VCMI_OK;
 }
 extern "C" int vcmi_estep_get_path(int *path) {
-  using namespace vcmi;
   if (!path) return fail(VCMI_ERR_ARG, "vcmi_estep_get_path: NULL argument");
   *path = estep_path_choice_ref();
-  return VCMI_OK;
-}
-
-// The same for the full-covariance STATISTICS kernel (its log-density kernel issues a fixed, known number of MFMAs).
-extern "C" int vcmi_debug_estep_full_mfma(int enable, int64_t *issued) {
-  using namespace vcmi;
-  EstepFullScratch &sc = full_scratch();
-  if (issued) {
-    *issued = 0;
-    if (sc.mfma_count.p) {
-      unsigned long long h = 0;
-      VCMI_HIP(hipMemcpy(&h, sc.mfma_count.p, sizeof(h), hipMemcpyDeviceToHost));
-      *issued = (int64_t)h;
-    }
-  }
-  if (enable) {
-    if (!sc.mfma_count.p) VCMI_TRY(sc.mfma_count.alloc(1));
-    VCMI_HIP(hipMemset(sc.mfma_count.p, 0, sizeof(unsigned long long)));
-  } else {
-    sc.mfma_count.release();
-  }
   return VCMI_OK;
 }

@@ -1,4 +1,4 @@
-// gmmmap_handle.hpp -- the opaque vcmi_gmmmap handle (shared by gmmmap.hip, gmmmap_prepare.cpp, estep.hip and traj.hip).
+// gmmmap_handle.hpp -- the opaque vcmi_gmmmap handle (shared by gmmmap.hip, gmmmap_prepare.cpp, estep_full.hip, gmm_em.hip and traj.hip).
 #pragma once
 #include "vcmi_common.hpp"
 #include "gmmmap_layout.hpp"
@@ -97,12 +97,12 @@ namespace vcmi {
 // Host-side preparation (gmmmap_prepare.cpp): factorises the joint GMM (weights (M), mu (Dj,M), sigma (Dj,Dj,M), Julia
 // memory images), profiles it, and packs and uploads every device image of g on the current device.
 // px_only: (mu, sigma) describe a plain GMM p(x) of dimension Dj (no target half): only the whitening side is prepared
-// (used by the full-covariance E-step, estep.hip); the regression blocks stay zero and the convert layouts are skipped.
+// (used by the full-covariance E-step, estep_full.hip); the regression blocks stay zero and the convert layouts are skipped.
 int gmmmap_prepare(vcmi_gmmmap *g, const double *w, const double *mu, const double *sigma, int Dj, int M, int swap,
                    bool px_only = false);
 // *inout becomes a handle on the current device: the existing one if it lives there, else a new one (the old one deleted)
 int gmm_px_handle_here(vcmi_gmmmap **inout);
-// p(x)-only handle over a plain GMM of dimension D (weights (M), mu (D,M), sigma (D,D,M)); used by estep.hip.
+// p(x)-only handle over a plain GMM of dimension D (weights (M), mu (D,M), sigma (D,D,M)); used by estep_full.hip and gmm_em.hip.
 // *out == nullptr creates a handle; otherwise the existing handle (same device) is re-prepared in place, reusing its
 // device buffers -- the caller must have drained every stream that still reads them.
 int gmm_px_create(const double *w, const double *mu, const double *sigma, int D, int M, vcmi_gmmmap **out);

@@ -414,7 +414,7 @@ std::vector<double> transpose_A(const HostModel &hm) {
 }
 
 // ------------------------------------------------------------------------------------------------
-// the sequence, and the handles of estep.hip
+// the sequence, and the p(x) handles of estep_full.hip and gmm_em.hip
 // ------------------------------------------------------------------------------------------------
 int gmmmap_prepare(vcmi_gmmmap *g, const double *w, const double *mu, const double *sigma, int Dj, int M, int swap, bool px_only) {
   HostModel hm;

@@ -91,6 +91,19 @@ struct StreamOrder {
     return VCMI_OK;
   }
 };
+// One call's use of the workspace: enter() here, leave() on every way out of the scope.  Check status() before any work.
+struct StreamOrderScope {
+  StreamOrder &order;
+  hipStream_t st;
+  int rc;
+  StreamOrderScope(StreamOrder &o, hipStream_t s) : order(o), st(s), rc(o.enter(s)) {}
+  StreamOrderScope(const StreamOrderScope &) = delete;
+  StreamOrderScope &operator=(const StreamOrderScope &) = delete;
+  ~StreamOrderScope() {
+    if (rc == VCMI_OK) (void)order.leave(st);
+  }
+  int status() const { return rc; }
+};
 
 // Test hook (vcmi_debug_force, not part of include/vcmi.h): forces the fallback kernels that a given shape would not
 // select by itself, so that the parity tests cover them.  Nothing on the call path reads the environment.

@@ -50,40 +50,52 @@ def unpack_stats(stats, Dj, M):
     return S0, S1, S2, stats[M + 2 * M * Dj]
 
 
-def estep_diag_dev(X, w, mu, var, out=None):
-    """Device-resident E-step: X is a (Dj,N) torch tensor (unit stride along Dj, dense: ld == Dj).
-    Returns the packed statistics as a device tensor of stats_len(Dj,M) doubles."""
-    import torch
-
-    w, mu, var, Dj, M = _params(w, mu, var)
+def _dense_frames(X, Dj):
+    """Device pointer and frame count of a dense (Dj,N) device matrix (unit stride along Dj, ld == Dj)."""
     ptr, D, N, ld = dev_matrix(X, "X")
     if D != Dj or (N > 1 and ld != Dj):
         raise _lib.DimensionMismatch("X must be a dense (Dj,N) matrix matching the model dimension")
+    return ptr, N
+
+
+def _estep_dev(entry, length, params, X, out):
+    """vcmi_estep_diag_dev / vcmi_estep_full_dev (`entry`) on checked parameters (w, mu, var or sigma, Dj, M)."""
+    import torch
+
+    w, mu, cov, Dj, M = params
+    ptr, N = _dense_frames(X, Dj)
     if out is None:
-        out = torch.empty(stats_len(Dj, M), dtype=torch.float64, device=X.device)
-    _lib.check(_lib.lib.vcmi_estep_diag_dev(ptr, N, Dj, M, _lib.dptr(w), _lib.dptr(mu), _lib.dptr(var), out.data_ptr(),
-                                            current_stream_ptr()))
+        out = torch.empty(length(Dj, M), dtype=torch.float64, device=X.device)
+    _lib.check(entry(ptr, N, Dj, M, _lib.dptr(w), _lib.dptr(mu), _lib.dptr(cov), out.data_ptr(), current_stream_ptr()))
     return out
 
 
-def estep_diag(X, w, mu, var):
+def _estep(entry, dev, unpack, params, X):
+    """vcmi_estep_diag / vcmi_estep_full (`entry`) for host frames, `dev` + `unpack` for a device tensor."""
+    w, mu, cov, Dj, M = params
     if is_torch(X):
-        w_, mu_, var_, Dj, M = _params(w, mu, var)
-        st = estep_diag_dev(X, w_, mu_, var_).cpu().numpy()
-        S0, S1, S2, ll = unpack_stats(st, Dj, M)
+        S0, S1, S2, ll = unpack(dev(X, w, mu, cov).cpu().numpy(), Dj, M)
         return S0.copy(), np.asfortranarray(S1), np.asfortranarray(S2), float(ll)
-    w, mu, var, Dj, M = _params(w, mu, var)
     X = jl_matrix(X, "X")
     if X.shape[0] != Dj:
         raise _lib.DimensionMismatch("X must be (Dj,N)")
-    N = X.shape[1]
     S0 = np.empty(M)
     S1 = np.empty((Dj, M), order="F")
-    S2 = np.empty((Dj, M), order="F")
+    S2 = np.empty(cov.shape, order="F")
     ll = np.zeros(1)
-    _lib.check(_lib.lib.vcmi_estep_diag(_lib.dptr(X), N, Dj, M, _lib.dptr(w), _lib.dptr(mu), _lib.dptr(var),
-                                        _lib.dptr(S0), _lib.dptr(S1), _lib.dptr(S2), _lib.dptr(ll)))
+    _lib.check(entry(_lib.dptr(X), X.shape[1], Dj, M, _lib.dptr(w), _lib.dptr(mu), _lib.dptr(cov),
+                     _lib.dptr(S0), _lib.dptr(S1), _lib.dptr(S2), _lib.dptr(ll)))
     return S0, S1, S2, float(ll[0])
+
+
+def estep_diag_dev(X, w, mu, var, out=None):
+    """Device-resident E-step: X is a (Dj,N) torch tensor (unit stride along Dj, dense: ld == Dj).
+    Returns the packed statistics as a device tensor of stats_len(Dj,M) doubles."""
+    return _estep_dev(_lib.lib.vcmi_estep_diag_dev, stats_len, _params(w, mu, var), X, out)
+
+
+def estep_diag(X, w, mu, var):
+    return _estep(_lib.lib.vcmi_estep_diag, estep_diag_dev, unpack_stats, _params(w, mu, var), X)
 
 
 def estep_diag_allreduce(X_shard, w, mu, var, group=None):
@@ -133,36 +145,12 @@ def unpack_full_stats(stats, Dj, M):
 def estep_full_dev(X, w, mu, sigma, out=None):
     """Device-resident full-covariance E-step: X is a dense (Dj,N) torch tensor.  Returns the packed statistics
     as a device tensor of full_stats_len(Dj,M) doubles."""
-    import torch
-
-    w, mu, sigma, Dj, M = _params_full(w, mu, sigma)
-    ptr, D, N, ld = dev_matrix(X, "X")
-    if D != Dj or (N > 1 and ld != Dj):
-        raise _lib.DimensionMismatch("X must be a dense (Dj,N) matrix matching the model dimension")
-    if out is None:
-        out = torch.empty(full_stats_len(Dj, M), dtype=torch.float64, device=X.device)
-    _lib.check(_lib.lib.vcmi_estep_full_dev(ptr, N, Dj, M, _lib.dptr(w), _lib.dptr(mu), _lib.dptr(sigma),
-                                            out.data_ptr(), current_stream_ptr()))
-    return out
+    return _estep_dev(_lib.lib.vcmi_estep_full_dev, full_stats_len, _params_full(w, mu, sigma), X, out)
 
 
 def estep_full(X, w, mu, sigma):
     """estep_full(X (Dj,N), w (M,), mu (Dj,M), sigma (Dj,Dj,M)) -> S0 (M,), S1 (Dj,M), S2 (Dj,Dj,M), loglik."""
-    w, mu, sigma, Dj, M = _params_full(w, mu, sigma)
-    if is_torch(X):
-        st = estep_full_dev(X, w, mu, sigma).cpu().numpy()
-        S0, S1, S2, ll = unpack_full_stats(st, Dj, M)
-        return S0.copy(), np.asfortranarray(S1), np.asfortranarray(S2), float(ll)
-    X = jl_matrix(X, "X")
-    if X.shape[0] != Dj:
-        raise _lib.DimensionMismatch("X must be (Dj,N)")
-    S0 = np.empty(M)
-    S1 = np.empty((Dj, M), order="F")
-    S2 = np.empty((Dj, Dj, M), order="F")
-    ll = np.zeros(1)
-    _lib.check(_lib.lib.vcmi_estep_full(_lib.dptr(X), X.shape[1], Dj, M, _lib.dptr(w), _lib.dptr(mu), _lib.dptr(sigma),
-                                        _lib.dptr(S0), _lib.dptr(S1), _lib.dptr(S2), _lib.dptr(ll)))
-    return S0, S1, S2, float(ll[0])
+    return _estep(_lib.lib.vcmi_estep_full, estep_full_dev, unpack_full_stats, _params_full(w, mu, sigma), X)
 
 
 def estep_full_allreduce(X_shard, w, mu, sigma, group=None):

@@ -24,101 +24,87 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._arrays import current_stream_ptr, dev_matrix, jl_matrix, jl_vector
-from .estep import estep_diag_dev, estep_full_dev, full_stats_len, stats_len, unpack_full_stats, unpack_stats
+from ._arrays import current_stream_ptr, jl_matrix, jl_vector
+from .estep import _dense_frames, estep_diag_dev, estep_full_dev, full_stats_len, stats_len, unpack_full_stats, unpack_stats
 from .kmeans import kmeans
 
 
-class EMState:
-    """Device-resident (w, mu, Sigma) + whitening blocks of a full-covariance GMM (vcmi_gmm_em_*)."""
+class _EMState:
+    """The handle of a device-resident EM state and the calls of one iteration.  A subclass supplies its C entries (create,
+    destroy, estep_dev, mstep, get), the length of its statistics and the shape of its third parameter."""
+    _entries = _stats_len = None
 
-    def __init__(self, w, mu, sigma, min_covar=1e-7):
+    @staticmethod
+    def _third_shape(Dj, M):
+        raise NotImplementedError
+
+    def _create(self, w, mu, third, name, min_covar):
         w = jl_vector(w)
         mu = jl_matrix(mu, "mu")
-        sigma = np.asfortranarray(np.asarray(sigma, dtype=np.float64))
+        third = np.asfortranarray(np.asarray(third, dtype=np.float64))
         Dj, M = mu.shape
-        if sigma.ndim != 3 or sigma.shape != (Dj, Dj, M) or w.shape != (M,):
-            raise _lib.DimensionMismatch(f"w {w.shape}, mu {mu.shape}, sigma {sigma.shape} are inconsistent")
+        if third.shape != self._third_shape(Dj, M) or w.shape != (M,):
+            raise _lib.DimensionMismatch(f"w {w.shape}, mu {mu.shape}, {name} {third.shape} are inconsistent")
         self.Dj, self.M = Dj, M
         h = C.c_void_p()
-        _lib.check(_lib.lib.vcmi_gmm_em_create(Dj, M, _lib.dptr(w), _lib.dptr(mu), _lib.dptr(sigma), float(min_covar), C.byref(h)))
+        _lib.check(self._entries[0](Dj, M, _lib.dptr(w), _lib.dptr(mu), _lib.dptr(third), float(min_covar), C.byref(h)))
         self._h = h
 
-    def __del__(self, _destroy=_lib.lib.vcmi_gmm_em_destroy):     # bound at definition: module globals may be gone at exit
+    def __del__(self):     # (the entries are bound when the subclass is defined: module globals may be gone at exit)
         h, self._h = getattr(self, "_h", None), None
         if h:
-            _destroy(h)
+            self._entries[1](h)
 
     def estep(self, X, out=None):
         """Local statistics of the (Dj,N) device block X -> packed device tensor [S0 | S1 | S2 | loglik]."""
         import torch
 
-        ptr, D, N, ld = dev_matrix(X, "X")
-        if D != self.Dj or (N > 1 and ld != self.Dj):
-            raise _lib.DimensionMismatch("X must be a dense (Dj,N) matrix matching the model dimension")
+        ptr, N = _dense_frames(X, self.Dj)
         if out is None:
-            out = torch.empty(full_stats_len(self.Dj, self.M), dtype=torch.float64, device=X.device)
-        _lib.check(_lib.lib.vcmi_gmm_em_estep_dev(self._h, ptr, N, out.data_ptr(), current_stream_ptr()))
+            out = torch.empty(self._stats_len(self.Dj, self.M), dtype=torch.float64, device=X.device)
+        _lib.check(self._entries[2](self._h, ptr, N, out.data_ptr(), current_stream_ptr()))
         return out
 
     def mstep(self, stats):
         """Parameters <- statistics (already summed over ranks); returns the log-likelihood they carry."""
         ll = np.zeros(1)
-        _lib.check(_lib.lib.vcmi_gmm_em_mstep(self._h, stats.data_ptr(), current_stream_ptr(), _lib.dptr(ll)))
+        _lib.check(self._entries[3](self._h, stats.data_ptr(), current_stream_ptr(), _lib.dptr(ll)))
         return float(ll[0])
 
     def get(self):
         w = np.empty(self.M)
         mu = np.empty((self.Dj, self.M), order="F")
-        sigma = np.empty((self.Dj, self.Dj, self.M), order="F")
-        _lib.check(_lib.lib.vcmi_gmm_em_get(self._h, _lib.dptr(w), _lib.dptr(mu), _lib.dptr(sigma)))
-        return w, mu, sigma
+        third = np.empty(self._third_shape(self.Dj, self.M), order="F")
+        _lib.check(self._entries[4](self._h, _lib.dptr(w), _lib.dptr(mu), _lib.dptr(third)))
+        return w, mu, third
 
 
-class DiagEMState:
+class EMState(_EMState):
+    """Device-resident (w, mu, Sigma) + whitening blocks of a full-covariance GMM (vcmi_gmm_em_*)."""
+    _entries = (_lib.lib.vcmi_gmm_em_create, _lib.lib.vcmi_gmm_em_destroy, _lib.lib.vcmi_gmm_em_estep_dev,
+                _lib.lib.vcmi_gmm_em_mstep, _lib.lib.vcmi_gmm_em_get)
+    _stats_len = staticmethod(full_stats_len)
+
+    @staticmethod
+    def _third_shape(Dj, M):
+        return (Dj, Dj, M)
+
+    def __init__(self, w, mu, sigma, min_covar=1e-7):
+        self._create(w, mu, sigma, "sigma", min_covar)
+
+
+class DiagEMState(_EMState):
     """Device-resident (w, mu, var) of a diagonal-covariance GMM (vcmi_gmm_em_diag_*): mu, var are (Dj,M)."""
+    _entries = (_lib.lib.vcmi_gmm_em_diag_create, _lib.lib.vcmi_gmm_em_diag_destroy, _lib.lib.vcmi_gmm_em_diag_estep_dev,
+                _lib.lib.vcmi_gmm_em_diag_mstep, _lib.lib.vcmi_gmm_em_diag_get)
+    _stats_len = staticmethod(stats_len)
+
+    @staticmethod
+    def _third_shape(Dj, M):
+        return (Dj, M)
 
     def __init__(self, w, mu, var, min_covar=1e-7):
-        w = jl_vector(w)
-        mu = jl_matrix(mu, "mu")
-        var = np.asfortranarray(np.asarray(var, dtype=np.float64))
-        Dj, M = mu.shape
-        if var.shape != (Dj, M) or w.shape != (M,):
-            raise _lib.DimensionMismatch(f"w {w.shape}, mu {mu.shape}, var {var.shape} are inconsistent")
-        self.Dj, self.M = Dj, M
-        h = C.c_void_p()
-        _lib.check(_lib.lib.vcmi_gmm_em_diag_create(Dj, M, _lib.dptr(w), _lib.dptr(mu), _lib.dptr(var), float(min_covar), C.byref(h)))
-        self._h = h
-
-    def __del__(self, _destroy=_lib.lib.vcmi_gmm_em_diag_destroy):     # bound at definition: module globals may be gone at exit
-        h, self._h = getattr(self, "_h", None), None
-        if h:
-            _destroy(h)
-
-    def estep(self, X, out=None):
-        """Local statistics of the (Dj,N) device block X -> packed device tensor [S0 | S1 | S2 | loglik] (stats_len)."""
-        import torch
-
-        ptr, D, N, ld = dev_matrix(X, "X")
-        if D != self.Dj or (N > 1 and ld != self.Dj):
-            raise _lib.DimensionMismatch("X must be a dense (Dj,N) matrix matching the model dimension")
-        if out is None:
-            out = torch.empty(stats_len(self.Dj, self.M), dtype=torch.float64, device=X.device)
-        _lib.check(_lib.lib.vcmi_gmm_em_diag_estep_dev(self._h, ptr, N, out.data_ptr(), current_stream_ptr()))
-        return out
-
-    def mstep(self, stats):
-        """Parameters <- statistics (already summed over ranks); returns the log-likelihood they carry."""
-        ll = np.zeros(1)
-        _lib.check(_lib.lib.vcmi_gmm_em_diag_mstep(self._h, stats.data_ptr(), current_stream_ptr(), _lib.dptr(ll)))
-        return float(ll[0])
-
-    def get(self):
-        w = np.empty(self.M)
-        mu = np.empty((self.Dj, self.M), order="F")
-        var = np.empty((self.Dj, self.M), order="F")
-        _lib.check(_lib.lib.vcmi_gmm_em_diag_get(self._h, _lib.dptr(w), _lib.dptr(mu), _lib.dptr(var)))
-        return w, mu, var
+        self._create(w, mu, var, "var", min_covar)
 
 
 def expand_diag(covars):
