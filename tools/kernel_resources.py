@@ -1,0 +1,51 @@
+#!/usr/bin/env python3
+"""Resource lines of every kernel in the device assembly that `hipcc --save-temps` (or `--offload-device-only -S`) leaves for a
+translation unit, and, given a second file, the kernels whose lines differ between the two:
+
+    hipcc -O3 -std=c++17 --offload-arch=gfx950 -fno-fast-math -mllvm -amdgpu-mfma-vgpr-form --offload-device-only -S \\
+        voiceconversion.jl_amd/csrc/gmmmap.hip -o gmmmap.s
+    tools/kernel_resources.py parent/gmmmap.s gmmmap.s
+
+A kernel is marked when it spills where the other build did not, gained a private segment, or needs more 8-register
+allocation granules than a step of waves per SIMD allows (512 registers per lane and SIMD)."""
+import re
+import subprocess
+import sys
+
+
+def parse(path):
+    s = open(path).read()
+    out = {}
+    for blk in s[s.index("amdhsa.kernels:"):].split("  - .agpr_count:")[1:]:
+        g = lambda k: re.search(r"\.%s:\s+(\S+)" % k, blk).group(1)          # noqa: E731
+        out[g("name")] = dict(vgpr=int(g("vgpr_count")), sgpr=int(g("sgpr_count")), spill=int(g("vgpr_spill_count")),
+                              lds=int(g("group_segment_fixed_size")), private=int(g("private_segment_fixed_size")))
+    return out
+
+
+def waves(vgpr):
+    return min(8, 512 // ((vgpr + 7) // 8 * 8))
+
+
+def main():
+    a = parse(sys.argv[1])
+    b = parse(sys.argv[2]) if len(sys.argv) > 2 else None
+    names = sorted(set(a) | set(b or {}))
+    dem = subprocess.run(["c++filt"] + names, capture_output=True, text=True).stdout.split("\n")
+    worse = 0
+    for n, d in zip(names, dem):
+        d = re.sub(r"\(.*", "", d).replace("void vcmi::", "")
+        x, y = a.get(n), (b or {}).get(n)
+        if b is None:
+            print(d, x)
+        elif x != y:
+            bad = x and y and (waves(y["vgpr"]) < waves(x["vgpr"]) or y["spill"] > x["spill"] or y["private"] > x["private"])
+            worse += bool(bad)
+            print(f"{d}\n   {x}\n   {y}{'   <-- worse' if bad else ''}")
+    if b is not None:
+        print(f"{sum(a.get(n) != b.get(n) for n in names)} of {len(names)} kernels differ, {worse} for the worse")
+    return 1 if worse else 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -149,6 +149,90 @@ __device__ __forceinline__ void load_frame_row(const double *row, bool live, boo
     }
   }
 }
+// x[f][ks] = row[f][4 ks + lgrp] for the lane's frame of tile f (`row[f]` = its first feature; zero when !live[f] or beyond D), in
+// two halves, so that ALL tiles' rows are in flight before the wave waits for the first (one memory round trip instead of one
+// per tile) and the caller can issue more between the halves.  request_frame_rows only issues the loads, into the registers
+// of x themselves: 32 contiguous bytes per block of the line path (LINES), single features of its tail and of the other
+// path.  Every address is valid whatever `live` says: a frame that is not live passes any valid row, a feature beyond D reads
+// feature 0 (only the last k-step can hold one: D > 4 (KS - 1)) -- a load under an exec branch is one the compiler does not
+// batch with its neighbours.  finish_frame_rows does the transposes and the masking in place.  ALL lanes of the wave must
+// call both (the transpose exchanges registers across lanes).  LINES is a template argument so that a caller branches ONCE
+// around request, whatever it issues in between, and finish: with the branch inside the halves the compiler merges the two
+// paths' tails and puts a wait between a tile's blocks and its tail.
+template <int KS, int FT, bool LINES>
+__device__ __forceinline__ void request_frame_rows(const double *const (&row)[FT], int D, int lgrp, double (&x)[FT][KS]) {
+  constexpr int NB = KS / 4;
+  if constexpr (LINES) {
+    typedef double xd2 __attribute__((ext_vector_type(2)));
+#pragma unroll
+    for (int f = 0; f < FT; ++f) {
+#pragma unroll
+      for (int b = 0; b < NB; ++b) {
+        const xd2 v0 = *reinterpret_cast<const xd2 *>(row[f] + 16 * b + 4 * lgrp);
+        const xd2 v1 = *reinterpret_cast<const xd2 *>(row[f] + 16 * b + 4 * lgrp + 2);
+        x[f][4 * b] = v0.x;
+        x[f][4 * b + 1] = v0.y;
+        x[f][4 * b + 2] = v1.x;
+        x[f][4 * b + 3] = v1.y;
+      }
+#pragma unroll
+      for (int ks = 4 * NB; ks < KS; ++ks) x[f][ks] = row[f][4 * ks + lgrp];      // (LINES: D is the padded dimension)
+    }
+  } else {
+    const int klast = (4 * (KS - 1) + lgrp < D) ? 4 * (KS - 1) + lgrp : 0;
+#pragma unroll
+    for (int f = 0; f < FT; ++f) {
+#pragma unroll
+      for (int ks = 0; ks < KS - 1; ++ks) x[f][ks] = row[f][4 * ks + lgrp];
+      x[f][KS - 1] = row[f][klast];
+    }
+  }
+}
+template <int KS, int FT, bool LINES>
+__device__ __forceinline__ void finish_frame_rows(const bool (&live)[FT], int D, int lgrp, double (&x)[FT][KS]) {
+  constexpr int NB = KS / 4;
+#pragma unroll
+  for (int f = 0; f < FT; ++f) {
+    if constexpr (LINES) {
+#pragma unroll
+      for (int b = 0; b < NB; ++b) {
+        double e0 = x[f][4 * b], e1 = x[f][4 * b + 1], e2 = x[f][4 * b + 2], e3 = x[f][4 * b + 3];
+        transpose_lane_groups4(e0, e1, e2, e3);
+        x[f][4 * b] = live[f] ? e0 : 0.0;
+        x[f][4 * b + 1] = live[f] ? e1 : 0.0;
+        x[f][4 * b + 2] = live[f] ? e2 : 0.0;
+        x[f][4 * b + 3] = live[f] ? e3 : 0.0;
+      }
+#pragma unroll
+      for (int ks = 4 * NB; ks < KS; ++ks) x[f][ks] = live[f] ? x[f][ks] : 0.0;
+    } else {
+#pragma unroll
+      for (int ks = 0; ks < KS; ++ks) x[f][ks] = (live[f] && (ks < KS - 1 || 4 * ks + lgrp < D)) ? x[f][ks] : 0.0;
+    }
+  }
+}
+// both halves with `between()` issued after the requests (more loads, a DMA, a wait): one branch on `lines` around the three
+template <int KS, int FT, class Between>
+__device__ __forceinline__ void load_frame_rows(const double *const (&row)[FT], const bool (&live)[FT], bool lines, int D, int lgrp,
+                                                double (&x)[FT][KS], Between &&between) {
+  if (lines) {
+    request_frame_rows<KS, FT, true>(row, D, lgrp, x);
+    between();
+    finish_frame_rows<KS, FT, true>(live, D, lgrp, x);
+  } else {
+    request_frame_rows<KS, FT, false>(row, D, lgrp, x);
+    between();
+    finish_frame_rows<KS, FT, false>(live, D, lgrp, x);
+  }
+  // (each value through an empty asm: the finished operands are then registers of their own.  Without it they stay tied to the
+  // 128-bit load tuples, all of which are in flight at once here, and the two-tile screen kernel at D = 40, which has no register
+  // to spare at three waves per SIMD, spills 46 of them)
+#pragma unroll
+  for (int f = 0; f < FT; ++f) {
+#pragma unroll
+    for (int ks = 0; ks < KS; ++ks) asm volatile("" : "+v"(x[f][ks]));
+  }
+}
 // row[4 j + lgrp] = yo[j] for the lane's frame; ALL lanes of the wave must call it
 template <int KS>
 __device__ __forceinline__ void store_frame_row(double *row, bool live, bool lines, int D, int lgrp, const double (&yo)[KS]) {
@@ -1756,8 +1840,10 @@ static int dispatch_screen_argmax(const vcmi_gmmmap *g, const double *dX, int64_
 
 static constexpr double kScreenArgmaxFrac = 0.10;      // predict: screened arg-max when at most this fraction of the mixtures survives the screen
 static constexpr double kBroadModelFrac = 0.35;
-// shape 3 pays while the survivors of the four-row screen stay few: a survivor costs a whole mixture (42 MFMA steps at D = 40)
-// for every wave of its workgroup, a screened mixture 2.5 -- against the 10 of shape 2's last-tile test
+// shape 3 pays while the survivors of the four-row screen stay few: a survivor costs its workgroup a block DMA and a barrier,
+// and a whole mixture (42 MFMA steps at D = 40) every wave one of whose own frames let it through (the other waves skip it: the
+// MFMA count at nreg[1] no longer holds their 22 whitening steps); a screened mixture 2.5 -- against the 10 of shape 2's
+// last-tile test
 static constexpr double kScreenModelFrac = 0.05;
 // Which loop shape converts with this handle (gmmmap_mfma_kernel's PRUNE): 2 "peaked" when, for the model's own frames, the
 // last whitening tile's share of |z|^2 alone puts most mixtures e^-prune under the best one (model.undecided, estimated

@@ -16,7 +16,9 @@
 //   2. every quad of mixtures is screened against (running maximum - prune); a mixture that no frame of the workgroup lets
 //      through contributes less than e^-prune to every frame: exactly the terms the other shapes skip.  Survivors go into a
 //      bitmap in LDS (rare: one or two per workgroup on the SURVEY 8d model);
-//   3. the survivors are evaluated in full, in index order, with the "broad" loop's per-wave test in front of the regression.
+//   3. the survivors are evaluated in full, in index order, with the "broad" loop's per-wave test in front of the regression --
+//      With two tiles per wave: by the waves that have a frame of their own which let the mixture through (a second bitmap per
+//      wave) -- for the others the bound already certifies what the exact test would find after 44 whitening MFMAs.
 // The running maximum only grows, so a mixture screened out against the maximum of step 1 is below e^-prune of the final
 // maximum as well: the result is the dense loop's to rounding (the order of the sum differs: survivors in index order after
 // the group's mixture).  Stages of QS quads are staged by LDS-DMA, double-buffered, one barrier per stage (16 mixtures).
@@ -63,6 +65,7 @@ gmmmap_screen_kernel(const double *__restrict__ packed, const double *__restrict
   __shared__ double etab[64];
   __shared__ unsigned survivors[32];                            // bit m: mixture m passed the screen on some frame of the workgroup (M <= 1024)
   __shared__ unsigned keys[32];                                 // bit m: m is the group of some frame of the workgroup (evaluated in step 1)
+  __shared__ unsigned wsurv[PAIRED ? WAVES : 1][32];            // two tiles: bit m of row w: m passed the screen on some frame of wave w
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wave_u = __builtin_amdgcn_readfirstlane(wave);
@@ -71,22 +74,7 @@ gmmmap_screen_kernel(const double *__restrict__ packed, const double *__restrict
   const int64_t frame0 = ((int64_t)blockIdx.x * WAVES + wave) * (16 * FT);
   const unsigned lds0 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char *)(reinterpret_cast<char *>(smem));
 
-  // the groups of the workgroup's positions -> `keys` (every word that is read later is written here: nothing to zero), and the
-  // group of its first one: the mixture evaluated first.  The loads of gbase are the kernel's first, so the DMA of that block
-  // goes out after ONE short latency (it used to be the chain perm[f0] -> gkey[...] -> DMA, and a gather of gkey per frame)
-  // (the table of vc_exp_tab is requested in front of them, so that it arrives in the same wait)
-  const double etv = (tid < 64) ? kExp2Tab[tid] : 0.0;
-  const int64_t f0 = (int64_t)blockIdx.x * WAVES * (16 * FT);
-  const int64_t f1 = (f0 + WAVES * (16 * FT) < T) ? f0 + WAVES * (16 * FT) : T;
-  const int mg = groups_in_range(gbase, M, (int)f0, (int)f1, lane, [&](int w, unsigned lo, unsigned hi) {
-    if (tid == 0) {
-      keys[w] = lo;
-      keys[w + 1] = hi;
-    }
-  });
-  if (tid < 64) etab[tid] = etv;
-  if (tid < 32) survivors[tid] = 0u;
-  // block mg -> buffer 0, stage 0 -> buffer 1 (each wave issues every WAVES-th KB)
+  // block m -> a buffer, stage s -> a buffer (each wave issues every WAVES-th KB)
   auto dma_block = [&](int m, int buf) {
     const char *gb = reinterpret_cast<const char *>(packed + (size_t)m * BLK);
     const unsigned lb = lds0 + (unsigned)buf * (BUF * 8u);
@@ -105,30 +93,89 @@ gmmmap_screen_kernel(const double *__restrict__ packed, const double *__restrict
       if (k < NI_STG) dma_1k(gb + 1024 * k, lb + 1024u * k, lane_off);
     }
   };
-  dma_block(mg, 0);
-  dma_stage(0, 1);
-  __builtin_amdgcn_sched_barrier(0);
-
-  // B operands: xb[f][ks] = X[k = 4 ks + lgrp][frame], zero outside (D, T)
-  double xb[FT][KS];
-  int64_t frow[FT];
+  double xb[FT][KS];             // B operands: xb[f][ks] = X[k = 4 ks + lgrp][frame], zero outside (D, T)
+  using row_t = std::conditional_t<PAIRED, int, int64_t>;       // (two tiles: perm's 32 bits, not their sign extension -- registers)
+  row_t frow[FT];                // the frame a tile column stands for
   unsigned tiles_in_range = 0;
-#pragma unroll
-  for (int f = 0; f < FT; ++f) {
-    const int64_t fr = frame0 + 16 * f + lcol;
-    frow[f] = (fr < T) ? (int64_t)perm[fr] : fr;
-    if (frame0 + 16 * f < T) tiles_in_range |= 1u << f;
-  }
-  // (round 6: rows as whole 128-byte lines where they are 16-byte aligned and unpadded -- load_frame_row, gmmmap.hip)
+  int mg;
+  const int64_t f0 = (int64_t)blockIdx.x * WAVES * (16 * FT);
+  const int64_t f1 = (f0 + WAVES * (16 * FT) < T) ? f0 + WAVES * (16 * FT) : T;
+  // the groups of the workgroup's positions -> `keys` (every word that is read later is written here: nothing to zero), and the
+  // group of its first one: the mixture evaluated first
+  auto find_groups = [&]() {
+    return groups_in_range(gbase, M, (int)f0, (int)f1, lane, [&](int w, unsigned lo, unsigned hi) {
+      if (tid == 0) {
+        keys[w] = lo;
+        keys[w + 1] = hi;
+      }
+    });
+  };
+  // (round 6: rows as whole 128-byte lines where they are 16-byte aligned and unpadded -- load_frame_row(s), gmmmap.hip)
   const bool xlines = rows_as_lines(X, ldx, D, DP);
-  auto load_x = [&]() {
+  // one tile per wave: the rows of x, requested and finished in one call (also the reload of step 3)
+  auto load_x1 = [&]() {
 #pragma unroll
     for (int f = 0; f < FT; ++f) {
       const int64_t fr = frame0 + 16 * f + lcol;
       load_frame_row<KS>(X + (fr < T ? frow[f] : (int64_t)0) * ldx, fr < T, xlines, D, lgrp, xb[f]);
     }
   };
-  load_x();
+  // two tiles per wave: the rows of both -> xb, with `between()` issued behind the requests (also the reload of step 3)
+  auto load_x2 = [&](auto &&between) {
+    const double *xrow[FT];
+    bool xlive[FT];
+#pragma unroll
+    for (int f = 0; f < FT; ++f) {
+      xlive[f] = frame0 + 16 * f + lcol < T;
+      int pr = (int)frow[f];
+      asm volatile("" : "+v"(pr));                               // (the address is formed again for the reload, not kept in registers)
+      xrow[f] = X + (int64_t)pr * ldx;
+    }
+    load_frame_rows<KS, FT>(xrow, xlive, xlines, D, lgrp, xb, between);
+  };
+  if constexpr (PAIRED) {
+    // The two-tile prologue is TWO memory round trips, which is what its data flow needs (it used to be five: gbase, perm of
+    // tile 0, perm of tile 1, rows of tile 0, rows of tile 1 -- each wait also waiting for both DMAs, the counter being in order):
+    //   stage 0 -> buffer 1 first (it depends on nothing but the arguments);
+    //   one batch: perm of both tiles, the table of vc_exp_tab, the gbase words of groups_in_range -- one wait;
+    //   the rows of both tiles, then block mg -> buffer 0; the transposes, vmcnt(0), the barrier.
+    // Positions beyond T read position T - 1 (clamped, selected afterwards: a load under an exec branch is not batched).
+    dma_stage(0, 1);
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int f = 0; f < FT; ++f) {
+      const int64_t fr = frame0 + 16 * f + lcol;
+      frow[f] = perm[fr < T ? fr : T - 1];
+      if (frame0 + 16 * f < T) tiles_in_range |= 1u << f;
+    }
+    const double etv = kExp2Tab[lane];
+    mg = find_groups();
+    if (tid < 64) etab[tid] = etv;
+    if (tid < 32) survivors[tid] = 0u;
+    if (tid < 32 * WAVES) (&wsurv[0][0])[tid] = 0u;
+    load_x2([&]() {
+      dma_block(mg, 0);
+      __builtin_amdgcn_sched_barrier(0);
+    });
+  } else {
+    // One tile per wave (calls of at most kSmallCallFrames frames): there is no second tile to overlap, and the batched form and
+    // the per-wave bitmap cost these instantiations registers (occupancy steps at DP = 16 and 20, spills at 28 and 36), so
+    // they keep the single load_frame_row and the workgroup's bitmap alone: the loads of gbase first, then the DMAs, perm, the rows.  (the table of vc_exp_tab is requested in front of them, so that it arrives in the same wait)
+    const double etv = (tid < 64) ? kExp2Tab[tid] : 0.0;
+    mg = find_groups();
+    if (tid < 64) etab[tid] = etv;
+    if (tid < 32) survivors[tid] = 0u;
+    dma_block(mg, 0);
+    dma_stage(0, 1);
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int f = 0; f < FT; ++f) {
+      const int64_t fr = frame0 + 16 * f + lcol;
+      frow[f] = (fr < T) ? (int64_t)perm[fr] : fr;
+      if (frame0 + 16 * f < T) tiles_in_range |= 1u << f;
+    }
+    load_x1();
+  }
   // (no barrier here: keys, survivors and etab are complete before the barrier in front of the first block, and nothing reads
   // or updates them earlier)
   double yacc[FT][KS];
@@ -249,7 +296,12 @@ gmmmap_screen_kernel(const double *__restrict__ packed, const double *__restrict
   // ---- every mixture of a bitmap (except `skip`) in full, in index order; blocks alternate between the buffers starting with
   // `first_buf`, which every wave must have left (the caller's barrier); ends with everyone out of both buffers' readers... the
   // bitmap must be complete and visible (a barrier since its last update)
-  auto eval_bitmap = [&](const unsigned *bm, int first_buf, int skip, bool reload_x) -> int {
+  // `own` (the survivors): this wave's bitmap beside the workgroup's -- the blocks, the DMA and the barriers follow `bm`, every
+  // wave taking part in them, but a wave none of whose own frames let mixture m through the screen is certified not to need it
+  // (the bound was below the running maximum of step 1 less prune on each of its frames, and the maximum only grows): it skips
+  // the whitening that the per-wave test would throw away.  `reload_x`: the rows of x are requested again behind the first
+  // block's DMA and (two tiles) finished under that block's wait.
+  auto eval_bitmap = [&](const unsigned *bm, const unsigned *own, int first_buf, int skip, bool reload_x) -> int {
     const int nwords = (M + 31) / 32;
     int w = 0;
     unsigned bits = __builtin_amdgcn_readfirstlane(bm[0]);
@@ -269,15 +321,22 @@ gmmmap_screen_kernel(const double *__restrict__ packed, const double *__restrict
     __syncthreads();                                             // everyone has left buffer p
     dma_block(cur_m, p);
     // (B16: the FP64 operands of x were given up for the screen -- the survivors are rare -- and come back from L2 here)
-    if (reload_x) load_x();
+    if (reload_x) {
+      if constexpr (PAIRED)
+        load_x2([&]() {
+          asm volatile("s_waitcnt vmcnt(0)" ::: "memory");         // (the wait of the loop's first turn, taken here)
+        });
+      else load_x1();
+    }
     while (cur_m >= 0) {
       ++n;
       const int nxt_m = next();
       const double lc = packed_c[(size_t)cur_m * BLK + TL::LC_OFF];
+      const bool mine = own == nullptr || (__builtin_amdgcn_readfirstlane(own[cur_m >> 5]) >> (cur_m & 31) & 1u) != 0u;
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       __syncthreads();                                           // block cur_m is in buffer p; everyone has left buffer p ^ 1
       if (nxt_m >= 0) dma_block(nxt_m, p ^ 1);
-      full_mixture(smem + p * BUF, lc, true);
+      if (mine) full_mixture(smem + p * BUF, lc, true);
       cur_m = nxt_m;
       p ^= 1;
     }
@@ -291,7 +350,7 @@ gmmmap_screen_kernel(const double *__restrict__ packed, const double *__restrict
   full_mixture(smem, lc_g, false);
   // the other groups present in the workgroup (it straddles a group boundary: rare on large calls, the rule on small ones)
   // (blocks go to buffer 0, 1, 0, ...: from the second one on they overwrite stage 0, which is then fetched again)
-  const int nkeys = eval_bitmap(keys, 0, mg, false);
+  const int nkeys = eval_bitmap(keys, nullptr, 0, mg, false);
   // the thresholds of the screen, per tile in every lane (a lane group of a screening tile is a MIXTURE, not a tile)
   double thr[FT];
   if constexpr (PAIRED) {
@@ -459,7 +518,10 @@ gmmmap_screen_kernel(const double *__restrict__ packed, const double *__restrict
         const int bit = __builtin_ctz(lanebits);
         lanebits &= lanebits - 1u;
         const int m = (QS * s + (bit >> 2)) * mpt + per * lgrp + (bit & 3);
-        if (m < M && !(keys[m >> 5] >> (m & 31) & 1u)) atomicOr(&survivors[m >> 5], 1u << (m & 31));
+        if (m < M && !(keys[m >> 5] >> (m & 31) & 1u)) {
+          atomicOr(&survivors[m >> 5], 1u << (m & 31));
+          if constexpr (PAIRED) atomicOr(&wsurv[wave][m >> 5], 1u << (m & 31));
+        }
       }
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -467,7 +529,7 @@ gmmmap_screen_kernel(const double *__restrict__ packed, const double *__restrict
   }
 
   // ---- 3. the survivors in full, in index order (the bitmap is complete and visible: the loop above ended with a barrier)
-  eval_bitmap(survivors, 0, -1, B16);
+  eval_bitmap(survivors, PAIRED ? wsurv[wave] : nullptr, 0, -1, B16);
 
   if (nreg && lane == 0) {
     atomicAdd(nreg, (unsigned long long)nreg_wave);
@@ -486,7 +548,7 @@ gmmmap_screen_kernel(const double *__restrict__ packed, const double *__restrict
     double yo[KS];
 #pragma unroll
     for (int j = 0; j < KS; ++j) yo[j] = yacc[f][j] * inv;
-    store_frame_row<KS>(Y + (fr < T ? frow[f] : (int64_t)0) * ldy, fr < T, rows_as_lines(Y, ldy, D, DP), D, lgrp, yo);
+    store_frame_row<KS>(Y + (fr < T ? (int64_t)frow[f] : (int64_t)0) * ldy, fr < T, rows_as_lines(Y, ldy, D, DP), D, lgrp, yo);
   }
 }
 
