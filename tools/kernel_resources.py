@@ -6,6 +6,7 @@ translation unit, and, given a second file, the kernels whose lines differ betwe
         voiceconversion.jl_amd/csrc/gmmmap.hip -o gmmmap.s
     tools/kernel_resources.py parent/gmmmap.s gmmmap.s
 
+Kernels are matched by their demangled name without the argument list, so a kernel whose signature changed still lines up.
 A kernel is marked when it spills where the other build did not, gained a private segment, or needs more 8-register
 allocation granules than a step of waves per SIMD allows (512 registers per lane and SIMD)."""
 import re
@@ -27,15 +28,20 @@ def waves(vgpr):
     return min(8, 512 // ((vgpr + 7) // 8 * 8))
 
 
-def main():
-    a = parse(sys.argv[1])
-    b = parse(sys.argv[2]) if len(sys.argv) > 2 else None
-    names = sorted(set(a) | set(b or {}))
+def short_names(d):
+    """mangled name -> the demangled one without its argument list: a kernel whose signature changed still lines up"""
+    names = sorted(d)
     dem = subprocess.run(["c++filt"] + names, capture_output=True, text=True).stdout.split("\n")
+    return {re.sub(r"\(.*", "", x).replace("void vcmi::", ""): d[n] for n, x in zip(names, dem)}
+
+
+def main():
+    a = short_names(parse(sys.argv[1]))
+    b = short_names(parse(sys.argv[2])) if len(sys.argv) > 2 else None
+    names = sorted(set(a) | set(b or {}))
     worse = 0
-    for n, d in zip(names, dem):
-        d = re.sub(r"\(.*", "", d).replace("void vcmi::", "")
-        x, y = a.get(n), (b or {}).get(n)
+    for d in names:
+        x, y = a.get(d), (b or {}).get(d)
         if b is None:
             print(d, x)
         elif x != y:

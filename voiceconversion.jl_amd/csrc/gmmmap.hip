@@ -1777,7 +1777,7 @@ static int launch_screen(const vcmi_gmmmap *g, const double *dX, int64_t ldx, in
   }
   const int64_t per_wg = (int64_t)16 * FT * WAVES;
   hipLaunchKernelGGL(kern, dim3((unsigned)((T + per_wg - 1) / per_wg)), dim3(WAVES * 64), shmem, st, g->packed.p, B16 ? g->packedQ16.p : g->packedQ.p, g->screen_rpm,
-                     g->M, g->D, dX, ldx, T, dY, ldy, g->prune, g->prune_count.p, perm, gbase);
+                     g->M, g->D, dX, ldx, T, dY, ldy, g->prune, g->prune_count.p, perm, gbase, B16 ? g->packedQ2.p : nullptr);
   VCMI_HIP(hipGetLastError());
   return VCMI_OK;
 }
@@ -1785,7 +1785,7 @@ static int dispatch_screen(const vcmi_gmmmap *g, const double *dX, int64_t ldx, 
                            const int *perm, const int *gbase) {
   const bool narrow = T <= kSmallCallFrames && !debug_flag(kDbgConvertWideTiles);     // one frame tile per wave, as dispatch_mfma
   // the screen on the BF16 matrix pipe (certified bound from split operands) where it exists: four rows per mixture, DP <= 40
-  if (g->packedQ16.p && g->screen_rpm == 4 && screen16_has(g->DP) && !debug_flag(kDbgScreenFp64)) {
+  if (g->packedQ16.p && g->packedQ2.p && g->screen_rpm == 4 && screen16_has(g->DP) && !debug_flag(kDbgScreenFp64)) {
     switch (g->DP) {
 #define VCMI_CASE(DPV) \
   case DPV: return narrow ? launch_screen<DPV, 1, true>(g, dX, ldx, T, dY, ldy, st, perm, gbase) : launch_screen<DPV, 2, true>(g, dX, ldx, T, dY, ldy, st, perm, gbase);

@@ -50,6 +50,7 @@ struct vcmi_gmmmap {
   vcmi::DevBuf<double> packedU;   // U_m tiles only (log-density / posterior / argmax)
   vcmi::DevBuf<double> packedQ;   // stages of the screen: 4 tiles x (screen_rpm rows of 16 / screen_rpm mixtures) per stage (convert, shape 3)
   vcmi::DevBuf<double> packedQ16;  // the four-row screen split into bf16 hi + lo (screen on the BF16 matrix pipe; DP <= 40)
+  vcmi::DevBuf<double> packedQ2;   // sixteen rows per mixture, one tile each: the second look of that screen (uploaded with packedQ16)
   vcmi::DevBuf<double> packedQA;  // stages of predict's screen: four rows per mixture, every tile-kernel dimension (gmmmap_screen_argmax_kernel)
   vcmi::DevBuf<double> packedU2;  // U_m tiles only, tile by tile, last tile first (predict with early exit; host-prepared handles)
   // fvconvert's frame grouping (gmmmap_group_key_kernel): nearest-source-mean operand [-2 mu | |mu|^2] in MFMA fragment order,

@@ -146,6 +146,20 @@ __host__ __device__ constexpr int screen16_tile_doubles() { return 3 * 128; }
 __host__ __device__ constexpr int screen16_stage_doubles(int DP) { return screen_quads(DP) * (screen16_tile_doubles() + 32); }
 __host__ __device__ constexpr bool screen16_has(int DP) { return DP >= 16 && DP <= 40 && DP % 4 == 0; }
 
+// ---- the second look of the bf16 screen: sixteen rows of ONE mixture per tile (packedQ2, pack_screen2_bf16) ----------------
+// A mixture that its four strongest rows do not rule out is looked at once more with the min(16, D) strongest rows of the same
+// eigen-expansion before it becomes a survivor: the same four instructions against the same B operands, the same margins per
+// row, so  lc - sum_{i < 16} max(|a^_i| - eps_i, 0)^2 / 2  is an upper bound of the log-density as well, and never above the
+// four-row one (rows 0..3 are the four-row screen's, the other terms are >= 0).  One tile per mixture in the layout of one
+// tile of a bf16 stage: [Ph main | Pl main | tail] as 3 x 1 KB of bf16x8 per lane, tile row r = the mixture's row r (so lane
+// group j of the FP32 result holds rows 4 j .. 4 j + 3; rows from D on are zero), then ONE constant line of 32 doubles: per
+// lane group j 8 doubles {c_4j..4j+3 (4 floats), 2^-12 |P_4j..4j+3| (4 floats), 2^-12 |c_4j..4j+3| (4 floats), lc (double), pad}.
+// The kernel reads a tile straight from global memory (the image is 3.3 KB per mixture and stays in L2).
+__host__ __device__ constexpr int screen2_rows() { return 16; }
+__host__ __device__ constexpr int screen2_const_off() { return screen16_tile_doubles(); }       // doubles from the tile's start
+__host__ __device__ constexpr int screen2_tile_doubles() { return screen16_tile_doubles() + 32; }
+constexpr size_t screen2_doubles(int M) { return (size_t)M * screen2_tile_doubles(); }
+
 // ------------------------------------------------------------------------------------------------
 // operands of fvconvert's frame grouping (gmmmap_group_key_kernel / gmmmap_group_key16_kernel, gmmmap.hip)
 // ------------------------------------------------------------------------------------------------

@@ -35,10 +35,12 @@ int factor_model(vcmi_gmmmap *g, HostModel &hm, const double *w, const double *m
   for (std::vector<double> *h : {&g->h_A_julia, &g->h_Sxy, &g->h_Syy, &g->h_A}) h->assign(reg * dd * M, 0.0);
   for (std::vector<double> *h : {&g->h_mux, &g->h_muy}) h->assign((size_t)D * M, 0.0);
   const bool want_screen = !px_only && D >= 4 && gmmmap_has_mfma(DP) && M <= 1024;       // (fvconvert's screen: DP <= 48; predict's: every tile-kernel dimension)
+  const bool want_screen2 = want_screen && screen16_has(DP);      // sixteen rows: only where the bf16 screen (and its second look) exists
   using V = std::vector<double>;
   hm = HostModel{D, DP, M, px_only, /*U, A*/ V(pp * M), V(reg * pp * M), /*cz, b*/ V((size_t)DP * M), V(reg * DP * M), /*lc*/ V(M),
-                 /*P, cP*/ V(want_screen ? (size_t)M * 4 * DP : 0), V(want_screen ? (size_t)M * 4 : 0)};
-  V &hU = hm.U, &hA = hm.A, &hcz = hm.cz, &hb = hm.b, &hlc = hm.lc, &hP = hm.P, &hcP = hm.cP;
+                 /*P, cP*/ V(want_screen ? (size_t)M * 4 * DP : 0), V(want_screen ? (size_t)M * 4 : 0),
+                 /*P2, cP2*/ V(want_screen2 ? (size_t)M * 16 * DP : 0), V(want_screen2 ? (size_t)M * 16 : 0)};
+  V &hU = hm.U, &hA = hm.A, &hcz = hm.cz, &hb = hm.b, &hlc = hm.lc, &hP = hm.P, &hcP = hm.cP, &hP2 = hm.P2, &hcP2 = hm.cP2;
   const int xo = (swap && !px_only) ? D : 0, yo = px_only ? 0 : (swap ? 0 : D);   // src/gmmmap.jl:74-78
   const double LOG2PI = 1.8378770664093454835606594728112;
   // The mixtures are independent (an inverse, a Cholesky factorisation and a triangular inverse each: 64 x 160^3 flop for
@@ -113,9 +115,12 @@ int factor_model(vcmi_gmmmap *g, HostModel &hm, const double *w, const double *m
           G[(size_t)r * D + c] = sacc;
         }
       la::sym_eigen_jacobi(G.data(), D, V.data());
-      int top[4] = {-1, -1, -1, -1};
-      for (int i = 0; i < 4; ++i) {
+      // (where the bf16 screen exists the sixteen strongest go to P2 for its second look; the first four are P)
+      const int nrows = want_screen2 ? std::min(16, D) : 4;
+      int top[16];
+      for (int i = 0; i < nrows; ++i) {
         double bestv = -1.0;
+        top[i] = -1;
         for (int j = 0; j < D; ++j) {
           bool used = false;
           for (int u = 0; u < i; ++u) used = used || top[u] == j;
@@ -128,10 +133,12 @@ int factor_model(vcmi_gmmmap *g, HostModel &hm, const double *w, const double *m
         double cp = 0.0;
         for (int k = 0; k < D; ++k) {
           const double v = sk * V[(size_t)k * D + top[i]];
-          hP[((size_t)m * 4 + i) * DP + k] = v;
+          if (want_screen2) hP2[((size_t)m * 16 + i) * DP + k] = v;
+          if (i < 4) hP[((size_t)m * 4 + i) * DP + k] = v;
           cp += v * mux[k];
         }
-        hcP[(size_t)m * 4 + i] = cp;
+        if (want_screen2) hcP2[(size_t)m * 16 + i] = cp;
+        if (i < 4) hcP[(size_t)m * 4 + i] = cp;
       }
     }
   }
@@ -363,6 +370,42 @@ std::vector<double> pack_screen_bf16(const HostModel &hm) {
   return p16;
 }
 
+// the sixteen strongest rows of every mixture, one tile each, for the second look of that screen (gmmmap_layout.hpp: screen2_*)
+std::vector<double> pack_screen2_bf16(const HostModel &hm) {
+  const std::vector<double> &hlc = hm.lc, &hP2 = hm.P2, &hcP2 = hm.cP2;
+  const int D = hm.D, DP = hm.DP, M = hm.M, R = screen2_rows();
+  const int KSQ = DP / 4;
+  std::vector<double> p2(screen2_doubles(M), 0.0);
+  const double kEps = 1.0 / 4096.0;                            // 2^-12, as pack_screen_bf16
+  for (int m = 0; m < M; ++m) {
+    unsigned short *fr = reinterpret_cast<unsigned short *>(&p2[(size_t)m * screen2_tile_doubles()]);
+    double *cl = &p2[(size_t)m * screen2_tile_doubles() + screen2_const_off()];
+    for (int l = 0; l < 64; ++l) {
+      const int row = frag_row(l), gq = frag_col(l);           // tile row <-> the mixture's screening row
+      unsigned short ph[10] = {0}, pl[10] = {0};
+      for (int ks = 0; ks < KSQ; ++ks) split_bf16((4 * ks + gq < DP) ? hP2[((size_t)m * R + row) * DP + 4 * ks + gq] : 0.0, ph[ks], pl[ks]);
+      for (int j = 0; j < 8; ++j) {
+        fr[(size_t)l * 8 + j] = ph[j];
+        fr[512 + (size_t)l * 8 + j] = pl[j];
+      }
+      const unsigned short tail[8] = {ph[8], ph[9], ph[8], ph[9], pl[8], pl[9], 0, 0};
+      for (int j = 0; j < 8; ++j) fr[1024 + (size_t)l * 8 + j] = tail[j];
+    }
+    for (int j = 0; j < 4; ++j) {                              // lane group j: rows 4 j .. 4 j + 3
+      float *cf = reinterpret_cast<float *>(cl + j * 8);
+      auto up = [](double v) { return std::nextafterf((float)(v * (1.0 + 0x1p-20)), INFINITY); };
+      for (int r = 0; r < 4; ++r) {
+        const double nrm = sum_of_squares(&hP2[((size_t)m * R + 4 * j + r) * DP], D), c = hcP2[(size_t)m * R + 4 * j + r];
+        cf[r] = (float)c;
+        cf[4 + r] = up(kEps * std::sqrt(nrm));
+        cf[8 + r] = up(kEps * std::fabs(c));
+      }
+      cl[j * 8 + 6] = hlc[m];
+    }
+  }
+  return p2;
+}
+
 // operand of the frame grouping (gmmmap_group_key_kernel): [-2 mu^x | |mu^x|^2] over its first dimensions, fragment order;
 // the last k-step carries |mu|^2 in its first column (rows >= M: 1e300, never the minimum)
 std::vector<double> pack_group_keys(const HostModel &hm, const std::vector<double> &hmux) {
@@ -448,7 +491,10 @@ int gmmmap_prepare(vcmi_gmmmap *g, const double *w, const double *mu, const doub
     g->screen_rpm = rpm;
     g->model_undecided4_frac = g->model.undecided_rows[rpm == 4 ? 0 : rpm == 2 ? 1 : 2];     // what the chosen screen lets through
     VCMI_TRY(upload_now(g->packedQ, pack_screen(hm, rpm)));
-    if (rpm == 4 && screen16_has(DP)) VCMI_TRY(upload_now(g->packedQ16, pack_screen_bf16(hm)));
+    if (rpm == 4 && screen16_has(DP)) {
+      VCMI_TRY(upload_now(g->packedQ16, pack_screen_bf16(hm)));
+      VCMI_TRY(upload_now(g->packedQ2, pack_screen2_bf16(hm)));
+    }
   }
   // ... and predict's (gmmmap_screen_argmax_kernel): always four rows per mixture, every tile-kernel dimension
   if (!hm.P.empty()) VCMI_TRY(upload_now(g->packedQA, pack_screen(hm, 4)));

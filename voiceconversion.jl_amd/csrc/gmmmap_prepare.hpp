@@ -15,6 +15,7 @@ struct HostModel {
   std::vector<double> cz, b;        // [M][DP]
   std::vector<double> lc;           // [M]
   std::vector<double> P, cP;        // screening rows [M][4][DP], strongest first, and their constants [M][4]; empty: no screen
+  std::vector<double> P2, cP2;      // the min(16, D) strongest rows [M][16][DP] and constants [M][16]: rows 0..3 are P's, missing rows zero; empty unless screen16_has(DP)
 };
 // Fills hm and g's host copies (h_A_julia, h_A, h_Sxy, h_Syy, h_mux, h_muy) from the joint GMM; VCMI_ERR_NOT_PD names the
 // first mixture whose Sigma^xx cannot be factored.
@@ -30,6 +31,7 @@ int choose_screen_rows(const ModelProfile &pf, int DP, int M);
 std::vector<double> pack_tiles(const HostModel &hm, int variant);    // packed (0), packedU (1), packedU2 (2): for_each_fragment's variants
 std::vector<double> pack_screen(const HostModel &hm, int rpm);       // packedQ; rpm = 4: packedQA
 std::vector<double> pack_screen_bf16(const HostModel &hm);           // packedQ16 (four rows per mixture)
+std::vector<double> pack_screen2_bf16(const HostModel &hm);          // packedQ2 (sixteen rows per mixture: the second look)
 std::vector<double> pack_group_keys(const HostModel &hm, const std::vector<double> &mux);        // gfrag
 std::vector<double> pack_group_keys_bf16(const HostModel &hm, const std::vector<double> &mux);   // gfrag16
 std::vector<double> transpose_A(const HostModel &hm);                // At

@@ -14,11 +14,18 @@
 //      boundaries) are evaluated in full -- whitening, regression, softmax -- which makes the running maximum tight for
 //      (almost) all of its frames;
 //   2. every quad of mixtures is screened against (running maximum - prune); a mixture that no frame of the workgroup lets
-//      through contributes less than e^-prune to every frame: exactly the terms the other shapes skip.  Survivors go into a
-//      bitmap in LDS (rare: one or two per workgroup on the SURVEY 8d model);
+//      through contributes less than e^-prune to every frame: exactly the terms the other shapes skip.  On the BF16 pipe a
+//      mixture that the four rows leave open for some frame of a wave gets a SECOND LOOK in that wave before it counts: the
+//      sixteen strongest rows of the same eigen-expansion (one tile per mixture, packedQ2, read straight from global memory
+//      into registers; the same four instructions against the B operands the wave already holds; no LDS, no barrier, no
+//      FP64 x).  It is the same kind of bound against the same thresholds, only sharper -- on the SURVEY 8d model the four
+//      rows let 0.6 wrong mixtures per workgroup through, the sixteen none, with hundreds of nats to spare.  What still
+//      passes goes into a bitmap in LDS: real runner-ups, and whatever a broad model lets through;
 //   3. the survivors are evaluated in full, in index order, with the "broad" loop's per-wave test in front of the regression --
 //      With two tiles per wave: by the waves that have a frame of their own which let the mixture through (a second bitmap per
-//      wave) -- for the others the bound already certifies what the exact test would find after 44 whitening MFMAs.
+//      wave) -- for the others the bound already certifies what the exact test would find after 44 whitening MFMAs.  Each
+//      survivor costs the whole workgroup two barriers, a block DMA and (BF16 pipe) the reload of x: the second look of step 2
+//      is there so that this step runs for mixtures that matter, not for those the four rows merely failed to rule out.
 // The running maximum only grows, so a mixture screened out against the maximum of step 1 is below e^-prune of the final
 // maximum as well: the result is the dense loop's to rounding (the order of the sum differs: survivors in index order after
 // the group's mixture).  Stages of QS quads are staged by LDS-DMA, double-buffered, one barrier per stage (16 mixtures).
@@ -49,11 +56,15 @@ __device__ __forceinline__ int groups_in_range(const int *__restrict__ gbase, in
   return __builtin_amdgcn_readfirstlane(first < 0 ? 0 : first);
 }
 
+// candidates per wave and stage (of 16 mixtures) up to which the second look is taken; a matter of speed only
+constexpr int kSecondLookCap = 4;
+
 template <int DP, int FT, int WAVES, bool B16 = false>
 __global__ void __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(DP <= 40 ? (FT == 2 ? 3 : 4) : 2)))
 gmmmap_screen_kernel(const double *__restrict__ packed, const double *__restrict__ packedQ, int rpm, int M, int D,
                      const double *__restrict__ X, int64_t ldx, int64_t T, double *__restrict__ Y, int64_t ldy, double prune,
-                     unsigned long long *__restrict__ nreg, const int *__restrict__ perm, const int *__restrict__ gbase) {
+                     unsigned long long *__restrict__ nreg, const int *__restrict__ perm, const int *__restrict__ gbase,
+                     const double *__restrict__ packedQ2) {
   using TL = Tiling<DP, false>;
   constexpr int KS = TL::KS, NT = TL::NT, NU = TL::NU, BLK = TL::BLK;
   constexpr int QS = screen_quads(DP), QFR = screen_frag_doubles(DP), STG = B16 ? screen16_stage_doubles(DP) : screen_stage_doubles(DP);
@@ -361,9 +372,20 @@ gmmmap_screen_kernel(const double *__restrict__ packed, const double *__restrict
   } else {
     thr[0] = runmax[0] - prune;
   }
+  // a tile beyond T: no mixture passes on its account.  B16: nor on account of a COLUMN beyond T in the call's last, partly
+  // filled tile -- its x is zero, no frame at all, and as far from the group's mean as from anyone's: half of the mixtures would
+  // pass every look for it and be whitened by the workgroup
+  if constexpr (B16) {
+    const int64_t left = T - ((int64_t)blockIdx.x * WAVES + wave_u) * (16 * FT);       // (scalar: the wave's columns that are frames)
+    const int live_cols = left < 16 * FT ? (int)left : 16 * FT;
 #pragma unroll
-  for (int f = 0; f < FT; ++f)
-    if (!(tiles_in_range >> f & 1u)) thr[f] = INFINITY;            // a tile beyond T: no mixture passes on its account
+    for (int f = 0; f < FT; ++f)
+      if (16 * f + lcol >= live_cols) thr[f] = INFINITY;
+  } else {
+#pragma unroll
+    for (int f = 0; f < FT; ++f)
+      if (!(tiles_in_range >> f & 1u)) thr[f] = INFINITY;
+  }
   // B16: the B operands of the screen from the lane's own FP64 operands (slot j of the K = 32 instructions <-> k-step j), and
   // |x| per frame for the error bound; xb itself is not needed again unless something survives
   constexpr int NMAIN = KS < 8 ? KS : 8, NTAIL = KS - NMAIN;     // k-steps in the three main instructions / in the tail one
@@ -514,6 +536,63 @@ gmmmap_screen_kernel(const double *__restrict__ packed, const double *__restrict
     }
     if (__builtin_amdgcn_ballot_w64(lanebits != 0u) != 0) {      // rare: some mixture of the stage is not ruled out for some frame
       const int per = 4 / rpm;                                   // sub-mixtures per lane group
+      if constexpr (B16) {
+        // The second look (rpm = 4: bit 4 q of lane group j <-> mixture 4 (QS s + q) + j).  Wave-uniform: the wave's candidates
+        // as one mask, each looked at with its sixteen strongest rows on all of the wave's frames; one that still passes for
+        // some frame goes into the bitmaps (lane 0), the others are ruled out for this wave exactly as the four rows would
+        // have ruled them out.  More than kSecondLookCap candidates in one stage (a broad model forced to this shape: the look
+        // would mostly say "keep"): no look, they pass as they are.
+        unsigned cand = 0;
+#pragma unroll
+        for (int q = 0; q < QS; ++q) {
+          const unsigned long long bal = __builtin_amdgcn_ballot_w64((lanebits >> (4 * q) & 1u) != 0u);
+#pragma unroll
+          for (int j = 0; j < 4; ++j) cand |= ((bal >> (16 * j)) & 0xFFFFull) != 0ull ? 1u << (4 * q + j) : 0u;
+        }
+        if (__builtin_popcount(cand) <= kSecondLookCap) {
+          lanebits = 0u;
+          while (cand) {
+            const int m = 4 * QS * s + __builtin_ctz(cand);
+            cand &= cand - 1u;
+            if (m >= M || (__builtin_amdgcn_readfirstlane(keys[m >> 5]) >> (m & 31) & 1u) != 0u) continue;
+            // (a uniform base and 32-bit lane offsets formed HERE: hoisted out of the stage loop they would be registers of the
+            // whole kernel)
+            unsigned lo = lane_off;
+            asm volatile("" : "+v"(lo));
+            const char *tb = reinterpret_cast<const char *>(packedQ2 + (size_t)m * screen2_tile_doubles());
+            const double *cl = reinterpret_cast<const double *>(tb + 8 * screen2_const_off() + ((lo >> 8) << 6));      // lane group: 8 doubles
+            const u32x4_t aph = *reinterpret_cast<const u32x4_t *>(tb + lo);
+            const u32x4_t apl = *reinterpret_cast<const u32x4_t *>(tb + 1024 + lo);
+            const u32x4_t apt = *reinterpret_cast<const u32x4_t *>(tb + 2048 + lo);
+            const f32x4_t cc = *reinterpret_cast<const f32x4_t *>(cl), np = *reinterpret_cast<const f32x4_t *>(cl + 2),
+                          nc = *reinterpret_cast<const f32x4_t *>(cl + 4);
+            const double lcq = cl[6];
+            __builtin_amdgcn_sched_barrier(0);                   // all seven requests go out before anything waits: one round trip
+            bool pass = false;
+#pragma unroll
+            for (int f = 0; f < FT; ++f) {
+              f32x4_t a = -cc;
+              a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, aph), __builtin_bit_cast(bf16x8_t, bh[f]), a, 0, 0, 0);
+              a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, aph), __builtin_bit_cast(bf16x8_t, bl[f]), a, 0, 0, 0);
+              a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, apl), __builtin_bit_cast(bf16x8_t, bh[f]), a, 0, 0, 0);
+              if constexpr (NTAIL > 0)
+                a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, apt), __builtin_bit_cast(bf16x8_t, bt[f]), a, 0, 0, 0);
+              float lb = 0.0f;                                   // the lane's rows 4 lgrp .. 4 lgrp + 3, as in screen_tile16
+#pragma unroll
+              for (int i = 0; i < 4; ++i) {
+                const float t = fmaxf(fabsf(a[i]) - fmaf(np[i], nxf[f], nc[i]), 0.0f);
+                lb = fmaf(t, t, lb);
+              }
+              pass |= fma(-0.5 * (1.0 - 0x1p-20), sum_lane_groups((double)lb), lcq) > thr[f];
+            }
+            nmfma16_wave += FT * (3 + (NTAIL > 0 ? 1 : 0));
+            if (__builtin_amdgcn_ballot_w64(pass) != 0 && lane == 0) {
+              atomicOr(&survivors[m >> 5], 1u << (m & 31));
+              if constexpr (PAIRED) atomicOr(&wsurv[wave][m >> 5], 1u << (m & 31));
+            }
+          }
+        }
+      }
       while (lanebits) {                                         // (divergent: a few lanes, a few bits)
         const int bit = __builtin_ctz(lanebits);
         lanebits &= lanebits - 1u;
