@@ -337,6 +337,34 @@ int vcmi_traj_convert_batch(vcmi_traj *t, int64_t n, const double *const *X, con
 /* device-resident batch: utterance u has X at dX + x_off[u] ((2D,T[u])) and Y at dY + y_off[u] ((D,T[u])) */
 int vcmi_traj_convert_batch_dev(vcmi_traj *t, int64_t n, const double *dX, const int64_t *x_off, const int64_t *T,
                                 double *dY, const int64_t *y_off, void *stream);
+/* Toda'07 eqs. 30-36 instead of the suboptimum sequence of src/trajectory_gmmmap.jl:81-82: n >= 0 EM iterations after
+ * the argmax solution.  0 (default) = the reference's conversion, unchanged.  E-step: gamma_{m,t} = P(m | X_t, (W y)_t) at the
+ * current y, every mixture (none is pruned); M-step: the same banded solve with Qbar_t = sum_m gamma Q_m and
+ * gbar_t = sum_m gamma Q_m E_{m,t} (statement: csrc/traj_em.hpp).  The setting belongs to the handle: vcmi_traj_convert,
+ * _batch, _batch_dev and the vcmi_vc_traj family (per chunk) honour it, also on the replicas of a device group.
+ * iters < 0: VCMI_ERR_ARG; iters > 0 on a model with some (Q_m + Q_m')/2 not positive definite (no log-determinant):
+ * VCMI_ERR_NOT_PD -- with 0 such a model converts as before.  A vcmi_trajgv over a handle with iters > 0 returns VCMI_ERR_ARG
+ * from every convert entry before anything runs (the GV ascent reads one mixture per frame): EM with GV is not provided.
+ * Device scratch while EM runs, on the handle: log pi and gamma, M T doubles each; lse, flags and indices, ~4 T words; and the
+ * precision table (M + n_mixed) (2Ds)^2 doubles, Ds the dimension the solver runs in (D, or the padded one), n_mixed the frames
+ * of a slice with 1 - max_m gamma >= 2^-53.  A batch is processed in slices of whole utterances so that the table stays under
+ * 16 GiB (kTrajEmTableCapBytes, csrc/postf.hpp): the batch starts as one slice and is cut only where the mixed-frame count of
+ * an iteration would take the table past the cap (one utterance is never cut).  That count is read back once per slice and
+ * iteration -- the loop's only host synchronisation.  The buffers are released on every return of a conversion entry, an
+ * error return included, when together they exceed 256 MiB (kVcScratchKeepBytes).  Every feature dimension the converter
+ * accepts converts with EM (2D <= 96 on MFMA tiles, above that one workgroup per frame). */
+int vcmi_traj_set_em(vcmi_traj *t, int iters);
+int vcmi_traj_get_em(const vcmi_traj *t);
+/* L(y) = log P(W y | X) of the statement above for one utterance: X (2D,T), Y (D,T).  VCMI_ERR_NOT_PD where the objective is
+ * undefined (see above).  The _dev entry takes dense device matrices and writes *dL on `stream`; it first waits for `stream`
+ * and uploads a 32-byte descriptor synchronously (the descriptor buffer is shared with the conversion entries), the kernels
+ * then run asynchronously.  Scratch: log pi and gamma, 2 M T doubles on the handle; the host entry releases it above 256 MiB,
+ * the _dev entry, which returns before its kernels end, leaves it to the next conversion or host call. */
+int vcmi_traj_cond_loglik(vcmi_traj *t, const double *X, const double *Y, int64_t T, double *L);
+int vcmi_traj_cond_loglik_dev(vcmi_traj *t, const double *dX, const double *dY, int64_t T, double *dL, void *stream);
+/* objective at each E-step of the handle's last conversion call, summed over its utterances: min(cap, iters) values
+ * (entry k = L(y^k), k = 0 .. iters-1; entries beyond the iterations of that call are NaN) */
+int vcmi_traj_em_history(const vcmi_traj *t, double *L, int cap);
 /* vc(c::TrajectoryConverter, fm (2D+1,T)) -> out (D+1,T) in chunks of length(t) frames; src/common.jl:31-63 */
 int vcmi_vc_traj(vcmi_traj *t, const double *fm, int64_t T, double *out);
 /* push_delta(src (D,T)) -> out (2D,T); src/datasets.jl:6-13.  Host matrices, host arithmetic (O(DT), no device needed). */

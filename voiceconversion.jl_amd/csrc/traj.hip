@@ -24,8 +24,17 @@
 #include "postf.hpp"
 
 #include <algorithm>
+#include <functional>
 #include <cstdlib>
 #include <type_traits>
+
+namespace vcmi {
+struct EmTimes {           // what vcmi_debug_traj_em_times reports
+  double estep_ms = 0, gbar_ms = 0, blend_ms = 0, solve_ms = 0;   // E-step; gbar; flag scan + count read + blend; pad + solve
+  int64_t mixed_frames = 0, frames = 0, slices = 0;               // summed over slices and iterations
+  size_t table_bytes = 0;                                         // the largest table
+};
+}  // namespace vcmi
 
 struct vcmi_traj {
   vcmi_gmmmap *g = nullptr;
@@ -52,6 +61,18 @@ struct vcmi_traj {
   // converters on the other devices of a device group (vcmi_set_devices), made lazily by the members' worker threads
   std::vector<vcmi_traj *> replicas;
   uint64_t replicas_epoch = 0;
+  // EM re-estimation over all mixtures (traj_em.hpp): n >= 0 E/M pairs after the arg-max solution
+  int em_iters = 0;
+  bool em_pd = false;                     // (Q_m + Q_m') / 2 positive definite for every m: c_m exists
+  vcmi::DevBuf<double> cm;                // [M] c_m - D log 2 pi
+  vcmi::DevBuf<double> em_lp, em_gamma, em_lse, em_table, em_L;   // log pi and gamma (frames, M); lse (frames); [Q_1..Q_M | Qbar of the mixed frames]; L (iteration, utterance)
+  vcmi::DevBuf<int> em_pure, em_mix;      // per frame: mixture of a pure frame or -1; the mixed frames, then their count
+  vcmi::DevBuf<int64_t> em_mh;            // table index + 1 per frame
+  int em_run_iters = 0, em_run_n = 0;     // shape of em_L in the last call
+  std::vector<double> em_hist;            // L at each E-step of the last call, summed over its utterances
+  bool em_time = false;                   // measurement hook (vcmi_debug_traj_em_times): hip events around the steps of an iteration
+  vcmi::EmTimes em_times;                 // ... accumulated since the hook last read them
+  size_t em_cap_bytes = 0;                // test hook: table cap in place of kTrajEmTableCapBytes (0: the constant)
   ~vcmi_traj() {
     for (vcmi_traj *r : replicas) delete r;
   }
@@ -976,6 +997,8 @@ traj_unpad_y_kernel(const TrajUtt *__restrict__ utts, const double *__restrict__
   }
 }
 
+#include "traj_em.hpp"
+
 // ------------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------------
@@ -1161,6 +1184,149 @@ static size_t solve_lds_bytes(int D) {
   return (W3 * (W3 + 1) + 2 * W3 + 2 * (NK * 16 + 2) + 2 * D + D) * sizeof(double);   // covers both solve kernels
 }
 
+// ---- EM re-estimation (traj_em.hpp) ----------------------------------------------------------------------------------
+// log pi_{m,t} of every frame of the call into em_lp (the weights come from X alone: once per call)
+static int traj_em_prior(vcmi_traj *t, const std::vector<TrajUtt> &utts, int64_t nframes, bool contiguous, const double *dX0,
+                         hipStream_t st) {
+  const int D2 = t->D2, M = t->M;
+  VCMI_TRY(t->em_lp.reserve((size_t)nframes * M));
+  if (contiguous) {
+    VCMI_TRY(gmmmap_logdens_device(t->g, dX0, D2, nframes, t->em_lp.p, st));
+  } else {
+    for (auto &u : utts)
+      if (u.T > 0) VCMI_TRY(gmmmap_logdens_device(t->g, u.X, D2, u.T, t->em_lp.p + (size_t)u.frame0 * M, st));
+  }
+  hipLaunchKernelGGL(traj_em_logprior_kernel, dim3((unsigned)((nframes + 255) / 256)), dim3(256), 0, st, t->em_lp.p, M, nframes);
+  VCMI_HIP(hipGetLastError());
+  return VCMI_OK;
+}
+
+// E-step of the (uploaded) utterances du[0 .. nu) at the y in their Y matrices: gamma, lse and the flags; with_g: gbar into gbuf
+// as well.  Tmax: their longest.
+static int traj_em_estep(vcmi_traj *t, const TrajUtt *du, int nu, int Tmax, int64_t nframes, bool with_g, hipStream_t st,
+                         hipEvent_t mid = nullptr) {
+  const int D2 = t->D2, M = t->M;
+  VCMI_TRY(t->em_gamma.reserve((size_t)nframes * M));
+  VCMI_TRY(t->em_lse.reserve((size_t)nframes));
+  VCMI_TRY(t->em_pure.reserve((size_t)nframes));
+  if (t->NT <= 6 && !debug_flag(kDbgTrajGScalar)) {
+    const int nthr = 64 * t->NT;
+    const dim3 grid((unsigned)((Tmax + kEmF - 1) / kEmF), (unsigned)nu);
+    const size_t tiles = ((size_t)kEmNB * 4 * t->KS * 16 + (size_t)kEmNB * 4 * t->NT * 64) * sizeof(double);
+    const size_t shp = tiles + (size_t)t->NT * kEmF * sizeof(double), shg = tiles + (size_t)M * sizeof(int);
+    VCMI_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(traj_em_post_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shp));
+    hipLaunchKernelGGL(traj_em_post_kernel, grid, dim3(nthr), shp, st, du, D2, M, t->KS, t->Afrag.p, t->Qfrag.p, t->bvec.p, t->cm.p,
+                       t->em_lp.p, t->em_gamma.p, t->em_lse.p, t->em_pure.p);
+    if (mid) VCMI_HIP(hipEventRecord(mid, st));
+    if (with_g) {
+      VCMI_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(traj_em_g_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shg));
+      hipLaunchKernelGGL(traj_em_g_kernel, grid, dim3(nthr), shg, st, du, D2, M, t->KS, t->Afrag.p, t->Qfrag.p, t->bvec.p,
+                         t->em_gamma.p, t->gbuf.p);
+    }
+  } else {
+    const size_t shv = ((size_t)4 * D2 + 256 + M) * sizeof(double);
+    VCMI_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(traj_em_valu_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shv));
+    hipLaunchKernelGGL(traj_em_valu_kernel, dim3((unsigned)Tmax, (unsigned)nu), dim3(256), shv, st, du, D2, M, t->AT.p, t->QT.p, t->bvec.p,
+                       t->cm.p, t->em_lp.p, t->em_gamma.p, t->em_lse.p, t->em_pure.p, t->gbuf.p, with_g ? 1 : 0);
+    if (mid) VCMI_HIP(hipEventRecord(mid, st));     // (one kernel does both: its time counts as E-step)
+  }
+  VCMI_HIP(hipGetLastError());
+  return VCMI_OK;
+}
+
+// em_iters E/M pairs after the arg-max solve of traj_run.  The table is sized by the mixed-frame count, one 4-byte read per
+// iteration (the only host synchronisation of the loop); the batch (sorted, uploaded at du) starts as ONE slice and is cut into
+// slices of whole utterances only where that count would take the table past kTrajEmTableCapBytes.
+template <class PadG, class Solve>
+static int traj_em_run(vcmi_traj *t, const std::vector<TrajUtt> &utts, const TrajUtt *du, int n, int64_t nframes, bool contiguous,
+                       const double *dX0, hipStream_t st, bool padded, PadG &pad_g, Solve &solve) {
+  if (!t->em_pd) return fail(VCMI_ERR_NOT_PD, "TrajectoryGMMMap: EM needs (Q_m + Q_m')/2 positive definite");
+  if (nframes > INT32_MAX) return fail(VCMI_ERR_DIM, "TrajectoryGMMMap: too many frames in one call for EM");
+  const int M = t->M, iters = t->em_iters;
+  const int Ds = padded ? t->Dpad : t->D;
+  const int64_t E = (int64_t)4 * Ds * Ds;
+  const double *Qsrc = padded ? t->Qpad.p : t->Q.p;
+  VCMI_TRY(traj_em_prior(t, utts, nframes, contiguous, dX0, st));
+  VCMI_TRY(t->em_mh.reserve((size_t)nframes));
+  VCMI_TRY(t->em_mix.reserve((size_t)nframes + 1));
+  VCMI_TRY(t->em_L.reserve((size_t)iters * n));
+  struct Events {
+    hipEvent_t e[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    ~Events() {
+      for (hipEvent_t x : e)
+        if (x) (void)hipEventDestroy(x);
+    }
+    hipEvent_t &operator[](int k) { return e[k]; }
+  } ev;
+  if (t->em_time)
+    for (int k = 0; k < 5; ++k) VCMI_HIP(hipEventCreate(&ev[k]));
+  // iterations it0 .. iters-1 of the (sorted) utterances [b0, b0 + nb).  A slice whose table would pass the cap at some
+  // iteration is cut in two there (by frames) and each half goes on from that iteration by itself: its E-step is repeated on
+  // the same y, so the results do not depend on where the cuts fall.  One utterance is never cut.
+  const size_t cap = t->em_cap_bytes ? t->em_cap_bytes : kTrajEmTableCapBytes;
+  std::function<int(int, int, int)> run_slice = [&](int b0, int nb, int it0) -> int {
+    const int Tmax = utts[(size_t)b0].T;                // (longest first)
+    int64_t fs = 0;
+    for (int u = 0; u < nb; ++u) fs += utts[(size_t)(b0 + u)].T;
+    for (int it = it0; it < iters; ++it) {
+      if (Tmax == 0) {                                  // only empty utterances: L = 0
+        hipLaunchKernelGGL(traj_em_sum_kernel, dim3((unsigned)nb), dim3(256), 0, st, du + b0, t->em_lse.p, t->em_L.p + (size_t)it * n);
+        continue;
+      }
+      if (t->em_time) VCMI_HIP(hipEventRecord(ev[0], st));
+      VCMI_TRY(traj_em_estep(t, du + b0, nb, Tmax, nframes, true, st, t->em_time ? ev[1] : nullptr));
+      if (t->em_time) VCMI_HIP(hipEventRecord(ev[2], st));
+      hipLaunchKernelGGL(traj_em_sum_kernel, dim3((unsigned)nb), dim3(256), 0, st, du + b0, t->em_lse.p, t->em_L.p + (size_t)it * n);
+      int *dcount = t->em_mix.p + nframes;
+      hipLaunchKernelGGL(traj_em_scan_kernel, dim3(1), dim3(1024), 0, st, du + b0, nb, M, t->em_pure.p, t->em_mh.p, t->em_mix.p, dcount);
+      VCMI_HIP(hipGetLastError());
+      int count = 0;
+      VCMI_HIP(hipMemcpyAsync(&count, dcount, sizeof(int), hipMemcpyDeviceToHost, st));
+      VCMI_HIP(hipStreamSynchronize(st));
+      if (count < 0 || count > fs) return fail(VCMI_ERR_HIP, "TrajectoryGMMMap: EM flag scan returned %d mixed frames of %lld", count, (long long)fs);
+      const size_t table = (size_t)(M + count) * (size_t)E;
+      if (table * sizeof(double) > cap && nb > 1) {
+        int h = 0;
+        for (int64_t f = 0; h < nb - 1 && 2 * f < fs; ++h) f += utts[(size_t)(b0 + h)].T;
+        h = std::max(h, 1);
+        VCMI_TRY(run_slice(b0, h, it));
+        return run_slice(b0 + h, nb - h, it);
+      }
+      VCMI_TRY(t->em_table.reserve(table));
+      VCMI_HIP(hipMemcpyAsync(t->em_table.p, Qsrc, sizeof(double) * (size_t)M * (size_t)E, hipMemcpyDeviceToDevice, st));
+      if (count > 0) {
+        const unsigned chunks = (unsigned)std::min<int64_t>(((E + 15) / 16 + 3) / 4, 8);
+        hipLaunchKernelGGL(traj_em_blend_kernel, dim3((unsigned)((count + 15) / 16), chunks), dim3(256), 0, st, Qsrc, M, E, t->em_gamma.p,
+                           t->em_mix.p, count, t->em_table.p + (size_t)M * (size_t)E);
+        VCMI_HIP(hipGetLastError());
+      }
+      if (t->em_time) VCMI_HIP(hipEventRecord(ev[3], st));
+      VCMI_TRY(pad_g());
+      VCMI_TRY(solve(t->em_table.p, t->em_mh.p, b0, nb));
+      if (t->em_time) {
+        VCMI_HIP(hipEventRecord(ev[4], st));
+        VCMI_HIP(hipEventSynchronize(ev[4]));
+        float ms[4] = {0.f, 0.f, 0.f, 0.f};
+        for (int k = 0; k < 4; ++k) VCMI_HIP(hipEventElapsedTime(&ms[k], ev[k], ev[k + 1]));
+        EmTimes &m = t->em_times;
+        m.estep_ms += ms[0];
+        m.gbar_ms += ms[1];
+        m.blend_ms += ms[2];
+        m.solve_ms += ms[3];
+        m.mixed_frames += count;
+        m.frames += fs;
+        m.table_bytes = std::max(m.table_bytes, table * sizeof(double));
+        m.slices += 1;
+      }
+    }
+    return VCMI_OK;
+  };
+  VCMI_TRY(run_slice(0, n, 0));
+  t->em_run_iters = iters;
+  t->em_run_n = n;
+  return VCMI_OK;
+}
+
 static int traj_run(vcmi_traj *t, std::vector<TrajUtt> &utts, int64_t nframes, bool contiguous, const double *dX0,
                     hipStream_t st, const TrajGV *gv = nullptr) {
   const int n = (int)utts.size();
@@ -1219,13 +1385,13 @@ static int traj_run(vcmi_traj *t, std::vector<TrajUtt> &utts, int64_t nframes, b
                        dim3(nthr), shg, st, du, n, D2, t->M, t->KS, t->Afrag.p, t->Qfrag.p, t->bvec.p, t->mhat.p, t->gperm.p, t->gbuf.p, split);
     VCMI_HIP(hipGetLastError());
   }
-  bool launched = false;
   // the dimension the blocked solver runs in, and its operands: the utterances' own, or the padded copies
+  const bool padded = t->Dpad && !debug_flag(kDbgTrajGeneric);
   const int Ds = t->Dpad ? t->Dpad : D;
-  const double *Qs = t->Q.p, *gs = t->gbuf.p;
+  const double *gs = t->gbuf.p;
   const TrajUtt *dus = du;
   int64_t ws_stride_s = ws_stride;
-  if (t->Dpad && !debug_flag(kDbgTrajGeneric)) {
+  if (padded) {
     const int Dp = t->Dpad;
     VCMI_TRY(t->gpad.reserve((size_t)nframes * 2 * Dp));
     VCMI_TRY(t->ypad.reserve((size_t)nframes * Dp));
@@ -1235,76 +1401,92 @@ static int traj_run(vcmi_traj *t, std::vector<TrajUtt> &utts, int64_t nframes, b
     VCMI_TRY(upload_now(t->uttpad.p, up.data(), sizeof(TrajUtt) * n));
     ws_stride_s = (int64_t)Tmax * (3 * Dp + 1) * Dp;
     VCMI_TRY(t->ws.reserve((size_t)grid * std::max(ws_stride, ws_stride_s)));
-    hipLaunchKernelGGL(traj_pad_g_kernel, dim3((unsigned)std::min<int64_t>((nframes * 2 * Dp + 255) / 256, 4096)), dim3(256), 0, st,
-                       t->gbuf.p, nframes, D, Dp, t->gpad.p);
-    VCMI_HIP(hipGetLastError());
-    Qs = t->Qpad.p;
     gs = t->gpad.p;
     dus = reinterpret_cast<const TrajUtt *>(t->uttpad.p);
   }
-  if (!debug_flag(kDbgTrajGeneric)) {
-    switch (Ds) {
-#define VCMI_TRAJ_BLK_CASE(DV)                                                                                      \
-  case DV: {                                                                                                        \
-    auto kern = traj_solve_blk_kernel<DV>;                                                                          \
-    const size_t shb = BlkCfg<DV>::lds_doubles * sizeof(double);                                                    \
-    VCMI_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,  \
-                                 (int)shb));                                                                        \
-    /* as many workgroups as the device holds at once: two per CU where LDS and registers allow (static D <= 30) */ \
-    int occ = 1;                                                                                                    \
-    if (debug_flag(kDbgTrajOneWgPerCu) ||                                                                           \
-        hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kern, blk_threads<DV>(), shb) != hipSuccess || occ < 1)        \
-      occ = 1;                                                                                                      \
-    const int grid_blk = (int)std::min<int64_t>(n, (int64_t)cus * occ);                                             \
-    VCMI_TRY(t->ws.reserve((size_t)grid_blk * std::max(ws_stride, ws_stride_s) + 256)); /* + slack: whole-KB reads */ \
-    if (blk_fused_backsub<DV>()) {                                                                                  \
-      hipLaunchKernelGGL(kern, dim3(grid_blk), dim3(blk_threads<DV>()), shb, st, dus, n, Qs, t->mhat.p, gs, t->ws.p,  \
-                         ws_stride_s, t->status.p);                                                                 \
-    } else {                                                                                                        \
-      /* eight waves: factorisation and back substitution are two kernels, per batch of grid_blk utterances */       \
-      auto kb = traj_backsub_blk_kernel<DV>;                                                                        \
-      const size_t shs = blk_backsub_lds_bytes<DV>();                                                               \
-      VCMI_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kb), hipFuncAttributeMaxDynamicSharedMemorySize,  \
-                                   (int)shs));                                                                      \
-      for (int b0 = 0; b0 < n; b0 += grid_blk) {                                                                    \
-        const int nb = std::min(grid_blk, n - b0);                                                                  \
-        hipLaunchKernelGGL(kern, dim3(nb), dim3(blk_threads<DV>()), shb, st, dus + b0, nb, Qs, t->mhat.p, gs,        \
-                           t->ws.p, ws_stride_s, t->status.p);                                                      \
-        hipLaunchKernelGGL(kb, dim3(nb), dim3(BacksubCfg<DV>::THREADS), shs, st, dus + b0, nb, t->ws.p, ws_stride_s);                    \
-      }                                                                                                             \
-    }                                                                                                               \
-    launched = true;                                                                                                \
-  } break;
-      VCMI_TRAJ_BLK_CASE(12) VCMI_TRAJ_BLK_CASE(16) VCMI_TRAJ_BLK_CASE(20) VCMI_TRAJ_BLK_CASE(24) VCMI_TRAJ_BLK_CASE(25)
-      VCMI_TRAJ_BLK_CASE(30) VCMI_TRAJ_BLK_CASE(32) VCMI_TRAJ_BLK_CASE(40) VCMI_TRAJ_BLK_CASE(46)
-#undef VCMI_TRAJ_BLK_CASE
-      default: break;
-    }
-  }
-  if (launched && t->Dpad) {
-    hipLaunchKernelGGL(traj_unpad_y_kernel, dim3(n, 8), dim3(256), 0, st, du, t->ypad.p, D, t->Dpad);
+  // gbuf -> gpad where the solver runs padded
+  auto pad_g = [&]() -> int {
+    if (!padded) return VCMI_OK;
+    const int Dp = t->Dpad;
+    hipLaunchKernelGGL(traj_pad_g_kernel, dim3((unsigned)std::min<int64_t>((nframes * 2 * Dp + 255) / 256, 4096)), dim3(256), 0, st,
+                       t->gbuf.p, nframes, D, Dp, t->gpad.p);
     VCMI_HIP(hipGetLastError());
-  }
-  if (!launched && t->big) {
-    const int64_t gstride = (int64_t)traj_big_win_doubles(D);
-    VCMI_TRY(t->gwin.reserve((size_t)grid * gstride));
-    const size_t lds_pk = traj_big_lds_bytes(D);
-    if (lds_pk <= 160 * 1024 - 256) {       // D <= 64: the window's lower triangle in LDS
-      VCMI_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(traj_solve_big_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   (int)lds_pk));
-      hipLaunchKernelGGL(traj_solve_big_kernel<true>, dim3(grid), dim3(256), lds_pk, st, du, n, D, t->Q.p, t->mhat.p, t->gbuf.p, t->ws.p,
-                         ws_stride, t->status.p, t->gwin.p, gstride);
-    } else {
-      hipLaunchKernelGGL(traj_solve_big_kernel<false>, dim3(grid), dim3(256), 0, st, du, n, D, t->Q.p, t->mhat.p, t->gbuf.p, t->ws.p,
-                         ws_stride, t->status.p, t->gwin.p, gstride);
+    return VCMI_OK;
+  };
+  // the solve of the (sorted) utterances [b0, b0 + nb) with the precision table Qs (indexed by mh[t] - 1) and the right-hand
+  // sides in gbuf / gpad
+  auto solve = [&](const double *Qs, const int64_t *mh, int b0, int nb) -> int {
+    bool launched = false;
+    const int grid_s = std::min(nb, cus);
+    if (!debug_flag(kDbgTrajGeneric)) {
+      switch (Ds) {
+#define VCMI_TRAJ_BLK_CASE(DV)                                                                                      \
+    case DV: {                                                                                                        \
+      auto kern = traj_solve_blk_kernel<DV>;                                                                          \
+      const size_t shb = BlkCfg<DV>::lds_doubles * sizeof(double);                                                    \
+      VCMI_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,  \
+                                   (int)shb));                                                                        \
+      /* as many workgroups as the device holds at once: two per CU where LDS and registers allow (static D <= 30) */ \
+      int occ = 1;                                                                                                    \
+      if (debug_flag(kDbgTrajOneWgPerCu) ||                                                                           \
+          hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kern, blk_threads<DV>(), shb) != hipSuccess || occ < 1)  \
+        occ = 1;                                                                                                      \
+      const int grid_blk = (int)std::min<int64_t>(nb, (int64_t)cus * occ);                                            \
+      VCMI_TRY(t->ws.reserve((size_t)grid_blk * std::max(ws_stride, ws_stride_s) + 256)); /* + slack: whole-KB reads */\
+      if (blk_fused_backsub<DV>()) {                                                                                  \
+        hipLaunchKernelGGL(kern, dim3(grid_blk), dim3(blk_threads<DV>()), shb, st, dus + b0, nb, Qs, mh, gs, t->ws.p, \
+                           ws_stride_s, t->status.p);                                                                 \
+      } else {                                                                                                        \
+        /* eight waves: factorisation and back substitution are two kernels, per batch of grid_blk utterances */      \
+        auto kb = traj_backsub_blk_kernel<DV>;                                                                        \
+        const size_t shs = blk_backsub_lds_bytes<DV>();                                                               \
+        VCMI_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kb), hipFuncAttributeMaxDynamicSharedMemorySize,  \
+                                     (int)shs));                                                                      \
+        for (int c0 = 0; c0 < nb; c0 += grid_blk) {                                                                   \
+          const int nc = std::min(grid_blk, nb - c0);                                                                 \
+          hipLaunchKernelGGL(kern, dim3(nc), dim3(blk_threads<DV>()), shb, st, dus + b0 + c0, nc, Qs, mh, gs,         \
+                             t->ws.p, ws_stride_s, t->status.p);                                                      \
+          hipLaunchKernelGGL(kb, dim3(nc), dim3(BacksubCfg<DV>::THREADS), shs, st, dus + b0 + c0, nc, t->ws.p, ws_stride_s);\
+        }                                                                                                             \
+      }                                                                                                               \
+      launched = true;                                                                                                \
+    } break;
+        VCMI_TRAJ_BLK_CASE(12) VCMI_TRAJ_BLK_CASE(16) VCMI_TRAJ_BLK_CASE(20) VCMI_TRAJ_BLK_CASE(24) VCMI_TRAJ_BLK_CASE(25)
+        VCMI_TRAJ_BLK_CASE(30) VCMI_TRAJ_BLK_CASE(32) VCMI_TRAJ_BLK_CASE(40) VCMI_TRAJ_BLK_CASE(46)
+#undef VCMI_TRAJ_BLK_CASE
+        default: break;
+      }
     }
-  } else if (!launched) {
-    VCMI_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(traj_solve_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                 (int)shmem));
-    hipLaunchKernelGGL(traj_solve_kernel, dim3(grid), dim3(256), shmem, st, du, n, D, t->Q.p, t->mhat.p, t->gbuf.p, t->ws.p,
-                       ws_stride, t->status.p);
-  }
-  VCMI_HIP(hipGetLastError());
+    if (launched && t->Dpad) {
+      hipLaunchKernelGGL(traj_unpad_y_kernel, dim3(nb, 8), dim3(256), 0, st, du + b0, t->ypad.p, D, t->Dpad);
+      VCMI_HIP(hipGetLastError());
+    }
+    if (!launched && t->big) {
+      const int64_t gstride = (int64_t)traj_big_win_doubles(D);
+      VCMI_TRY(t->gwin.reserve((size_t)grid * gstride));
+      const size_t lds_pk = traj_big_lds_bytes(D);
+      if (lds_pk <= 160 * 1024 - 256) {       // D <= 64: the window's lower triangle in LDS
+        VCMI_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(traj_solve_big_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                     (int)lds_pk));
+        hipLaunchKernelGGL(traj_solve_big_kernel<true>, dim3(grid_s), dim3(256), lds_pk, st, du + b0, nb, D, Qs, mh, t->gbuf.p, t->ws.p,
+                           ws_stride, t->status.p, t->gwin.p, gstride);
+      } else {
+        hipLaunchKernelGGL(traj_solve_big_kernel<false>, dim3(grid_s), dim3(256), 0, st, du + b0, nb, D, Qs, mh, t->gbuf.p, t->ws.p,
+                           ws_stride, t->status.p, t->gwin.p, gstride);
+      }
+    } else if (!launched) {
+      VCMI_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(traj_solve_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                   (int)shmem));
+      hipLaunchKernelGGL(traj_solve_kernel, dim3(grid_s), dim3(256), shmem, st, du + b0, nb, D, Qs, mh, t->gbuf.p, t->ws.p,
+                         ws_stride, t->status.p);
+    }
+    VCMI_HIP(hipGetLastError());
+    return VCMI_OK;
+  };
+  VCMI_TRY(pad_g());
+  VCMI_TRY(solve(padded ? t->Qpad.p : t->Q.p, t->mhat.p, 0, n));
+  t->em_run_iters = 0;
+  if (t->em_iters > 0) VCMI_TRY(traj_em_run(t, utts, du, n, nframes, contiguous, dX0, st, padded, pad_g, solve));
   if (gv && gv->epochs >= 0) {
     // (3) global-variance ascent on the solved trajectories, in place; workspace: V (2D,T) + r (D,T) <= the panel area
     // two-team kernel when the frame permutation of the longest utterance fits in LDS beside the two images of u
@@ -1330,6 +1512,33 @@ static int traj_run(vcmi_traj *t, std::vector<TrajUtt> &utts, int64_t nframes, b
   return VCMI_OK;
 }
 
+// the EM scratch of a call follows the rule of the vc scratch (postf.hpp): released above kVcScratchKeepBytes.  The stream is idle.
+static void traj_em_release(vcmi_traj *t) {
+  const size_t bytes = (t->em_lp.n + t->em_gamma.n + t->em_lse.n + t->em_table.n + t->em_L.n + t->em_mh.n) * sizeof(double) +
+                       (t->em_pure.n + t->em_mix.n) * sizeof(int);
+  if (bytes <= kVcScratchKeepBytes) return;
+  t->em_lp.release();
+  t->em_gamma.release();
+  t->em_lse.release();
+  t->em_table.release();
+  t->em_L.release();
+  t->em_mh.release();
+  t->em_pure.release();
+  t->em_mix.release();
+}
+
+// ... on every way out of a conversion entry, an error return between the EM loop and the status read included
+struct TrajEmRelease {
+  vcmi_traj *t;
+  ~TrajEmRelease() {
+    if (!t->em_table.p && !t->em_gamma.p) return;
+    const size_t bytes = (t->em_lp.n + t->em_gamma.n + t->em_table.n) * sizeof(double);
+    if (bytes <= kVcScratchKeepBytes) return;
+    (void)hipDeviceSynchronize();
+    traj_em_release(t);
+  }
+};
+
 static int traj_check_status(vcmi_traj *t, hipStream_t st) {
 #ifdef TRAJ_BLK_PROF
   {
@@ -1349,6 +1558,15 @@ static int traj_check_status(vcmi_traj *t, hipStream_t st) {
   int h = 0;
   VCMI_HIP(hipMemcpyAsync(&h, t->status.p, sizeof(int), hipMemcpyDeviceToHost, st));
   VCMI_HIP(hipStreamSynchronize(st));
+  // the EM objective of the call: L at each E-step, summed over the utterances in the caller's order
+  t->em_hist.assign((size_t)t->em_run_iters, 0.0);
+  if (t->em_run_iters > 0) {
+    std::vector<double> L((size_t)t->em_run_iters * t->em_run_n);
+    VCMI_HIP(hipMemcpy(L.data(), t->em_L.p, L.size() * sizeof(double), hipMemcpyDeviceToHost));
+    for (int it = 0; it < t->em_run_iters; ++it)
+      for (int u = 0; u < t->em_run_n; ++u) t->em_hist[(size_t)it] += L[(size_t)it * t->em_run_n + u];
+    traj_em_release(t);
+  }
   if (h) return fail(VCMI_ERR_NOT_PD, "trajectory normal matrix W'D^-1W is not positive definite");
   return VCMI_OK;
 }
@@ -1359,7 +1577,9 @@ static int traj_host_batch_local(vcmi_traj *t, int64_t n, const double *const *X
                                  const TrajGV *gv) {
   int64_t nframes = 0;
   for (int64_t u = 0; u < n; ++u) nframes += T[u];
+  t->em_hist.assign((size_t)t->em_iters, 0.0);
   if (nframes == 0) return VCMI_OK;
+  TrajEmRelease em_release{t};
   const int D = t->D, D2 = t->D2;
   VCMI_TRY(t->xbuf.reserve((size_t)nframes * D2));
   VCMI_TRY(t->ybuf.reserve((size_t)nframes * D));
@@ -1399,6 +1619,7 @@ static int traj_member(vcmi_traj *t, int member, vcmi_traj **out) {
   }
   vcmi_traj *&r = t->replicas[(size_t)member];
   if (!r) VCMI_TRY(vcmi_traj_create(g, t->length, &r));
+  r->em_iters = t->em_iters;      // the handle's setting, whenever it was made
   *out = r;
   return VCMI_OK;
 }
@@ -1429,7 +1650,8 @@ static int traj_host_batch(vcmi_traj *t, int64_t n, const double *const *X, cons
   std::vector<int64_t> costs((size_t)n);
   for (int64_t u = 0; u < n; ++u) costs[(size_t)u] = T[u];
   const std::vector<int> part = shard_by_cost(costs, m);
-  return group_run(m, [&](int i) -> int {
+  std::vector<std::vector<double>> hist((size_t)m);     // every member's EM objective
+  const int rc = group_run(m, [&](int i) -> int {
     std::vector<const double *> x2;
     std::vector<double *> y2;
     std::vector<int64_t> T2;
@@ -1460,8 +1682,14 @@ static int traj_host_batch(vcmi_traj *t, int64_t n, const double *const *X, cons
         gv2.pv = gr->pv.p;
       }
     }
-    return traj_host_batch_local(r, (int64_t)x2.size(), x2.data(), T2.data(), y2.data(), gv ? &gv2 : nullptr);
+    const int rcl = traj_host_batch_local(r, (int64_t)x2.size(), x2.data(), T2.data(), y2.data(), gv ? &gv2 : nullptr);
+    hist[(size_t)i] = r->em_hist;
+    return rcl;
   });
+  t->em_hist.assign((size_t)t->em_iters, 0.0);
+  for (auto &hm : hist)
+    for (size_t k = 0; k < hm.size() && k < t->em_hist.size(); ++k) t->em_hist[k] += hm[k];
+  return rc;
 }
 
 }  // namespace vcmi
@@ -1502,6 +1730,21 @@ extern "C" int vcmi_traj_create(vcmi_gmmmap *g, int64_t T, vcmi_traj **out) {
       bv[(size_t)D2 * m + r] = g->h_muy[(size_t)D2 * m + r] - ba;
     }
   }
+  // c_m = logdet((Q_m + Q_m') / 2) / 2 of the EM objective (traj_em.hpp), with its constant - D log 2 pi; a model without it
+  // (some symmetrised Q_m not positive definite) converts as before and refuses vcmi_traj_set_em(t, n > 0)
+  std::vector<double> cmv((size_t)M, 0.0);
+  t->em_pd = true;
+  for (int m = 0; m < M && t->em_pd; ++m) {
+    for (int r = 0; r < D2; ++r)
+      for (int c = 0; c < D2; ++c) S[(size_t)r * D2 + c] = 0.5 * (Q[nn * m + (size_t)r * D2 + c] + Q[nn * m + (size_t)c * D2 + r]);
+    if (!la::cholesky_from_upper(S.data(), D2, tmp.data())) {
+      t->em_pd = false;
+      break;
+    }
+    double ld = 0.0;
+    for (int r = 0; r < D2; ++r) ld += std::log(tmp[(size_t)r * D2 + r]);     // = logdet / 2
+    cmv[(size_t)m] = ld - (double)D * kEmLog2Pi;
+  }
   // Q in MFMA A-operand order for the GV ascent: fragment (row tile i, k-step ks) holds rows 16 i .. 16 i + 15, columns 4 ks .. 4 ks + 3
   // (the lane rule: fill_fragment, gmmmap_layout.hpp)
   t->NT = (D2 + 15) / 16;
@@ -1539,7 +1782,8 @@ extern "C" int vcmi_traj_create(vcmi_gmmmap *g, int64_t T, vcmi_traj **out) {
   }
   int rc = VCMI_OK;
   if ((rc = t->Q.alloc(Q.size())) || (rc = t->QT.alloc(QT.size())) || (rc = t->AT.alloc(AT.size())) ||
-      (rc = t->bvec.alloc(bv.size())) || (rc = t->Qfrag.alloc(Qf.size())) || (rc = t->Afrag.alloc(Af.size()))) {
+      (rc = t->bvec.alloc(bv.size())) || (rc = t->Qfrag.alloc(Qf.size())) || (rc = t->Afrag.alloc(Af.size())) ||
+      (rc = t->cm.alloc(cmv.size()))) {
     delete t;
     return rc;
   }
@@ -1549,6 +1793,7 @@ extern "C" int vcmi_traj_create(vcmi_gmmmap *g, int64_t T, vcmi_traj **out) {
   if (e == hipSuccess) e = upload_now_hip(t->bvec.p, bv.data(), bv.size() * 8);
   if (e == hipSuccess) e = upload_now_hip(t->Qfrag.p, Qf.data(), Qf.size() * 8);
   if (e == hipSuccess) e = upload_now_hip(t->Afrag.p, Af.data(), Af.size() * 8);
+  if (e == hipSuccess) e = upload_now_hip(t->cm.p, cmv.data(), cmv.size() * 8);
   if (e != hipSuccess) {
     delete t;
     return fail(VCMI_ERR_HIP, "TrajectoryGMMMap: upload failed: %s", hipGetErrorString(e));
@@ -1562,6 +1807,82 @@ extern "C" int vcmi_traj_destroy(vcmi_traj *t) {
   return VCMI_OK;
 }
 extern "C" int64_t vcmi_traj_length(const vcmi_traj *t) { return t ? t->length : -1; }
+
+// ---- EM re-estimation: the setting, the objective, the history (traj_em.hpp) ---------------------------------------------
+extern "C" int vcmi_traj_set_em(vcmi_traj *t, int iters) {
+  if (!t) return fail(VCMI_ERR_ARG, "vcmi_traj_set_em: NULL handle");
+  if (iters < 0) return fail(VCMI_ERR_ARG, "vcmi_traj_set_em: negative iteration count");
+  if (iters > 0 && !t->em_pd)
+    return fail(VCMI_ERR_NOT_PD, "vcmi_traj_set_em: (Q_m + Q_m')/2 of some mixture is not positive definite: the EM objective is undefined");
+  t->em_iters = iters;
+  return VCMI_OK;
+}
+extern "C" int vcmi_traj_get_em(const vcmi_traj *t) { return t ? t->em_iters : -1; }
+// Measurement hook (not part of include/vcmi.h; tools/traj_em_bench.py): with enable != 0 the EM loop of this handle records hip
+// events around its steps (and waits for them once per iteration).  out (8): ms of E-step, gbar, flag scan + count read + blend,
+// pad + solve; mixed frames; largest table in bytes; frames; slice-iterations -- accumulated since the last call, which resets them.
+extern "C" int vcmi_debug_traj_em_times(vcmi_traj *t, int enable, double *out) {
+  if (!t) return fail(VCMI_ERR_ARG, "vcmi_debug_traj_em_times: NULL handle");
+  const EmTimes &m = t->em_times;
+  const double v[8] = {m.estep_ms, m.gbar_ms, m.blend_ms, m.solve_ms, (double)m.mixed_frames, (double)m.table_bytes, (double)m.frames,
+                       (double)m.slices};
+  for (int k = 0; out && k < 8; ++k) out[k] = v[k];
+  t->em_times = EmTimes();
+  t->em_time = enable != 0;
+  return VCMI_OK;
+}
+// Test hook (not part of include/vcmi.h): the table cap of this handle's EM loop in bytes, so that the slicing can be tested
+// on small inputs; 0 restores kTrajEmTableCapBytes.  (A setting of one handle: nothing process-wide.)
+extern "C" int vcmi_debug_traj_em_cap(vcmi_traj *t, size_t bytes) {
+  if (!t) return fail(VCMI_ERR_ARG, "vcmi_debug_traj_em_cap: NULL handle");
+  t->em_cap_bytes = bytes;
+  return VCMI_OK;
+}
+
+extern "C" int vcmi_traj_em_history(const vcmi_traj *t, double *L, int cap) {
+  if (!t || (cap > 0 && !L) || cap < 0) return fail(VCMI_ERR_ARG, "vcmi_traj_em_history: bad argument");
+  for (int k = 0; k < cap; ++k) L[k] = k < (int)t->em_hist.size() ? t->em_hist[(size_t)k] : NAN;
+  return VCMI_OK;
+}
+
+extern "C" int vcmi_traj_cond_loglik_dev(vcmi_traj *t, const double *dX, const double *dY, int64_t T, double *dL, void *stream) {
+  if (!t || !dL) return fail(VCMI_ERR_ARG, "vcmi_traj_cond_loglik_dev: NULL argument");
+  if (T < 0 || T > INT32_MAX || (T > 0 && (!dX || !dY))) return fail(VCMI_ERR_ARG, "vcmi_traj_cond_loglik_dev: bad argument");
+  if (!t->em_pd) return fail(VCMI_ERR_NOT_PD, "vcmi_traj_cond_loglik: (Q_m + Q_m')/2 of some mixture is not positive definite");
+  hipStream_t st = as_stream(stream);
+  if (T == 0) {
+    VCMI_HIP(hipMemsetAsync(dL, 0, sizeof(double), st));
+    return VCMI_OK;
+  }
+  std::vector<TrajUtt> utts(1, TrajUtt{dX, const_cast<double *>(dY), 0, (int32_t)T, 0});
+  VCMI_TRY(t->uttbuf.reserve(sizeof(TrajUtt)));
+  VCMI_HIP(hipStreamSynchronize(st));       // (the descriptor buffer is shared with the conversion calls)
+  VCMI_TRY(upload_now(t->uttbuf.p, utts.data(), sizeof(TrajUtt)));
+  const TrajUtt *du = reinterpret_cast<const TrajUtt *>(t->uttbuf.p);
+  VCMI_TRY(t->gbuf.reserve((size_t)T * t->D2));
+  VCMI_TRY(traj_em_prior(t, utts, T, true, dX, st));
+  VCMI_TRY(traj_em_estep(t, du, 1, (int)T, T, false, st));
+  hipLaunchKernelGGL(traj_em_sum_kernel, dim3(1), dim3(256), 0, st, du, t->em_lse.p, dL);
+  VCMI_HIP(hipGetLastError());
+  return VCMI_OK;
+}
+
+extern "C" int vcmi_traj_cond_loglik(vcmi_traj *t, const double *X, const double *Y, int64_t T, double *L) {
+  if (!t || !L) return fail(VCMI_ERR_ARG, "vcmi_traj_cond_loglik: NULL argument");
+  if (T < 0 || T > INT32_MAX || (T > 0 && (!X || !Y))) return fail(VCMI_ERR_ARG, "vcmi_traj_cond_loglik: bad argument");
+  *L = 0.0;
+  if (T == 0) return VCMI_OK;
+  VCMI_TRY(t->xbuf.reserve((size_t)T * t->D2));
+  VCMI_TRY(t->ybuf.reserve((size_t)T * t->D + 1));
+  VCMI_TRY(upload_now(t->xbuf.p, X, sizeof(double) * T * t->D2));
+  VCMI_TRY(upload_now(t->ybuf.p, Y, sizeof(double) * T * t->D));
+  double *dL = t->ybuf.p + (size_t)T * t->D;
+  VCMI_TRY(vcmi_traj_cond_loglik_dev(t, t->xbuf.p, t->ybuf.p, T, dL, nullptr));
+  VCMI_HIP(hipStreamSynchronize(nullptr));
+  VCMI_HIP(hipMemcpy(L, dL, sizeof(double), hipMemcpyDeviceToHost));
+  traj_em_release(t);
+  return VCMI_OK;
+}
 
 extern "C" int vcmi_traj_convert(vcmi_traj *t, const double *X, int64_t T, double *Y) {
   const double *xs[1] = {X};
@@ -1591,7 +1912,9 @@ static int traj_batch_device(vcmi_traj *t, const TrajGV *gv /* may be NULL */, i
     utts[u] = TrajUtt{dX + x_off[u], dY + y_off[u], f0, (int32_t)T[u], (int32_t)u};
     f0 += T[u];
   }
+  t->em_hist.assign((size_t)t->em_iters, 0.0);
   if (f0 == 0) return VCMI_OK;   // only empty utterances: nothing was launched, there is no status to read
+  TrajEmRelease em_release{t};
   VCMI_TRY(traj_run(t, utts, f0, contiguous, dX + x_off[0], st, gv));
   return traj_check_status(t, st);
 }
@@ -1607,6 +1930,8 @@ extern "C" int vcmi_traj_convert_batch_dev(vcmi_traj *t, int64_t n, const double
 static int trajgv_args(const vcmi_trajgv *h, int64_t n, const int64_t *T, int epochs, TrajGV *gv) {
   if (!h) return fail(VCMI_ERR_ARG, "TrajectoryGVGMMMap: NULL handle");
   if (epochs < 0) return fail(VCMI_ERR_ARG, "TrajectoryGVGMMMap: negative epoch count");
+  if (h->t->em_iters > 0)    // the GV ascent groups frames by mhat[t] <= M and reads Qfrag: no blended precisions
+    return fail(VCMI_ERR_ARG, "TrajectoryGVGMMMap: the trajectory converter has EM re-estimation switched on (vcmi_traj_set_em)");
   for (int64_t u = 0; T && u < n; ++u)
     if (T[u] == 1) return fail(VCMI_ERR_DIM, "TrajectoryGVGMMMap: the variance of a one-frame trajectory is undefined");
   gv->muv = h->muv.p;
@@ -1650,6 +1975,7 @@ static int vc_traj_device(vcmi_traj *t, vcmi_trajgv *gvh, int epochs, double alp
   std::vector<TrajUtt> utts((size_t)nch);
   VCMI_TRY(check_device());
   VcScratch &sc = vc_scratch();
+  TrajEmRelease em_release{t};
   VCMI_TRY(sc.x.reserve((size_t)D2 * T));
   VCMI_TRY(sc.y.reserve((size_t)D * T));
   VCMI_TRY(sc.order.enter(st));

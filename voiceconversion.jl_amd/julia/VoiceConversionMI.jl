@@ -19,7 +19,7 @@ module VoiceConversionMI
 import LinearAlgebra
 
 export DeviceMatrix, FrameByFrameConverter, TrajectoryConverter, GMMMapParam, GMMMap, TrajectoryGMMMap, TrajectoryGVGMMMap,
-       fvconvert, vc, ncomponents, dim,
+       fvconvert, vc, ncomponents, dim, em_iters, em_iters!, cond_loglik, em_history,
        VarianceScaling, fvpostf!, fvpostf,
        align, align_mcep, push_delta, GVDataset, sp2mc, mc2sp, mc2b,
        DTW, fit!, update!, set_template!, backward,
@@ -273,6 +273,35 @@ mutable struct TrajectoryGMMMap <: TrajectoryConverter                 # src/tra
         finalizer(x -> ccall((:vcmi_traj_destroy, libvcmi), Cint, (Ptr{Cvoid},), x.h), t)
         t
     end
+end
+# TrajectoryGMMMap(g, T, n): n EM iterations (Toda et al. 2007, eqs. 30-36) after the arg-max solution of
+# src/trajectory_gmmmap.jl:81-82; 0 is the reference's conversion.  fvconvert and vc pick the setting up from the converter.
+function TrajectoryGMMMap(g::GMMMap, T::Int, n::Int)
+    t = TrajectoryGMMMap(g, T)
+    em_iters!(t, n)
+    t
+end
+em_iters(t::TrajectoryGMMMap) = Int(ccall((:vcmi_traj_get_em, libvcmi), Cint, (Ptr{Cvoid},), t.h))
+function em_iters!(t::TrajectoryGMMMap, n::Int)
+    check(ccall((:vcmi_traj_set_em, libvcmi), Cint, (Ptr{Cvoid}, Cint), t.h, n))
+    n
+end
+# L(y) = log P(W y | X) for one utterance: X (2D,T), Y (D,T)
+function cond_loglik(t::TrajectoryGMMMap, X::Matrix{Float64}, Y::Matrix{Float64})
+    (size(X, 1) == dim(t) && 2size(Y, 1) == size(X, 1) && size(X, 2) == size(Y, 2)) ||
+        throw(DimensionMismatch("Inconsistent dimentions."))
+    L = Ref{Float64}(0.0)
+    check(ccall((:vcmi_traj_cond_loglik, libvcmi), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Int64, Ref{Float64}),
+                t.h, X, Y, size(X, 2), L))
+    L[]
+end
+# the objective at each E-step of the last conversion call (as many values as that call ran iterations), summed over its
+# utterances; the library pads with NaN
+function em_history(t::TrajectoryGMMMap)
+    L = Vector{Float64}(undef, max(em_iters(t), 1024))
+    check(ccall((:vcmi_traj_em_history, libvcmi), Cint, (Ptr{Cvoid}, Ptr{Float64}, Cint), t.h, L, length(L)))
+    k = findfirst(isnan, L)
+    k === nothing ? L : L[1:k-1]
 end
 # length(t) follows the reference: fvconvert rebuilds W for a new T (src/trajectory_gmmmap.jl:70-72), so the length
 # is that of the last converted (sub-)sequence; the library tracks it.

@@ -81,11 +81,55 @@ class TrajectoryGMMMap(TrajectoryConverter):
     """TrajectoryGMMMap(g::GMMMap, T) -- src/trajectory_gmmmap.jl:3-37.  `g` is a GMMMap over static+delta
     features (dim(g) = 2D).  The constructor precomputes Dy_m = inv(Sigma^yy_m - A_m Sigma^xy_m) (:24-28)."""
 
-    def __init__(self, g, T):
+    def __init__(self, g, T, em_iters=0):
         self.gmmmap = g
         h = C.c_void_p()
         _lib.check(_lib.lib.vcmi_traj_create(g._h, int(T), C.byref(h)))
         self._h = h
+        if em_iters:
+            self.em_iters = em_iters
+
+    @property
+    def em_iters(self):
+        """EM iterations after the arg-max solution (Toda et al. 2007, eqs. 30-36: every mixture weighted by
+        P(m | X_t, Y_t)) instead of the suboptimum mixture sequence of src/trajectory_gmmmap.jl:81-82 alone.  0 (default):
+        the reference's conversion.  fvconvert, fvconvert_batch and vc pick the setting up from the converter."""
+        return int(_lib.lib.vcmi_traj_get_em(self._h))
+
+    @em_iters.setter
+    def em_iters(self, n):
+        _lib.check(_lib.lib.vcmi_traj_set_em(self._h, int(n)))
+
+    def cond_loglik(self, X, Y):
+        """L(y) = log P(W y | X) for one utterance, X (2D,T), Y (D,T): the objective the EM iterations raise.  numpy
+        matrices give a float; device tensors (dense, unit stride along the features) a one-element device tensor."""
+        if is_torch(X) and X.is_cuda:
+            import torch
+
+            xp, D2, T, ldx = dev_matrix(X, "X")
+            yp, D, Ty, ldy = dev_matrix(Y, "Y")
+            if D2 != self._dim() or 2 * D != D2 or Ty != T:
+                raise _lib.DimensionMismatch("Inconsistent dimentions.")
+            if T > 1 and (ldx != D2 or ldy != D):
+                raise ValueError("cond_loglik: X and Y must be dense")
+            out = torch.empty(1, dtype=torch.float64, device=X.device)
+            _lib.check(_lib.lib.vcmi_traj_cond_loglik_dev(self._h, xp, yp, T, out.data_ptr(), current_stream_ptr()))
+            return out
+        X, Y = jl_matrix(X, "X"), jl_matrix(Y, "Y")
+        if X.shape[0] != self._dim() or 2 * Y.shape[0] != X.shape[0] or X.shape[1] != Y.shape[1]:
+            raise _lib.DimensionMismatch("Inconsistent dimentions.")
+        L = C.c_double(0.0)
+        _lib.check(_lib.lib.vcmi_traj_cond_loglik(self._h, _lib.dptr(X), _lib.dptr(Y), X.shape[1], C.byref(L)))
+        return float(L.value)
+
+    def em_history(self):
+        """L(y^k), k = 0 .. n-1: the objective at each E-step of the LAST conversion call (n = the iterations that call ran,
+        whatever em_iters is now), summed over its utterances."""
+        cap = max(self.em_iters, 1024)
+        L = np.empty(cap)
+        _lib.check(_lib.lib.vcmi_traj_em_history(self._h, _lib.dptr(L), cap))
+        bad = np.flatnonzero(np.isnan(L))           # entries beyond that call's iterations are NaN
+        return L[:bad[0]] if len(bad) else L
 
     def __del__(self, _destroy=_lib.lib.vcmi_traj_destroy):       # bound at definition: module globals may be gone at exit
         h = getattr(self, "_h", None)
