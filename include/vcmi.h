@@ -20,6 +20,17 @@
  *     VCMI_ERR_NOT_PD -> PosDefException (raised by MvNormal in src/gmm.jl:17), others -> ErrorException;
  *   - handles are not re-entrant: one handle must not be used from two threads at once (the reference's
  *     GMMMap carries mutable scratch too, src/gmmmap.jl:59).
+ *   - stream semantics of the `_dev` entries.  Calls share device scratch that outlives them, on the handle or per host
+ *     thread ("State that outlives a call").  Consecutive calls of one thread on ANY streams, non-blocking ones
+ *     included, are ordered by the library without a host synchronisation: a call first makes its stream wait for the last
+ *     kernel of the previous call that used the same scratch (vcmi_gmmmap_convert_dev / _predict_dev per handle;
+ *     vcmi_estep_diag_dev, vcmi_gmm_em_*_estep_dev, vcmi_sp2mc_dev / vcmi_mc2sp_dev, vcmi_variance_scaling_dev,
+ *     vcmi_dtw_fit_batch_dev per thread), or it has finished when it returns because it ends with a status read on its
+ *     stream (vcmi_estep_full_dev, vcmi_traj_convert_batch_dev, vcmi_trajgv_convert_batch_dev, vcmi_vc_traj_dev,
+ *     vcmi_vc_trajgv_dev), or it touches the caller's buffers only (vcmi_gmmmap_posterior_dev, vcmi_push_delta_dev,
+ *     vcmi_mc2b_dev).  The exception is vcmi_kmeans: see there.
+ *     None of this holds for a stream that is being CAPTURED into a graph: the entries are not supported under stream
+ *     capture ("State that outlives a call").
  */
 #ifndef VCMI_H
 #define VCMI_H
@@ -296,7 +307,13 @@ int vcmi_gmm_em_diag_get(vcmi_gmm_em_diag *h, double *w, double *mu, double *var
  *                            owns a pick sends that frame (Dj doubles) to the others.
  *   vcmi_kmeans_seed_trials  local potential sum min(mind2, |x - cand_l|^2) of L <= 16 device candidates cand (Dj,L) in one
  *                            pass                                                             -> ALL-REDUCE (L doubles)
- * VCMI_ERR_ARG for non-finite frames or centers (reported by update / seed_commit), VCMI_ERR_DIM for bad shapes. */
+ * VCMI_ERR_ARG for non-finite frames or centers (reported by update / seed_commit), VCMI_ERR_DIM for bad shapes.  The update
+ * that reports a non-finite value has already written the centers from those statistics: call vcmi_kmeans_set before the
+ * handle is used again.
+ * Streams: labels, mind2 and the statistics partials live on the handle and carry NO stream order of their own.  A Lloyd
+ * iteration is a chain on one stream that ends in a synchronising read, so none is needed there; two asynchronous calls of
+ * ONE handle on different streams (vcmi_kmeans_assign_dev, _far_dev, _mind2_dev) must be ordered by the caller (an event,
+ * or the same stream). */
 typedef struct vcmi_kmeans vcmi_kmeans;
 int64_t vcmi_kmeans_stats_len(int Dj, int M);
 int vcmi_kmeans_create(int Dj, int M, const double *centers0, vcmi_kmeans **out);

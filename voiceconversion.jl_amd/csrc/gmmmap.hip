@@ -1970,6 +1970,8 @@ int gmmmap_convert_device(vcmi_gmmmap *g, const double *dX, int64_t ldx, int64_t
     // no tile-kernel instantiation (80 < padded D <= 160, or a padded dimension outside its list): MFMA log-densities
     // (logdens_tiled_kernel) + softmax / regression over the mixtures that matter, in chunks that bound the (T,M) scratch
     const int64_t chunk = std::max<int64_t>(4096, ((int64_t)1 << 24) / std::max(g->M, 1));
+    StreamOrderScope use(g->grp_order, st);       // scratch_lp is the handle's, like the grouping buffers: one order for both
+    VCMI_TRY(use.status());
     for (int64_t t0 = 0; t0 < T; t0 += chunk) {
       const int64_t n = std::min(chunk, T - t0);
       VCMI_TRY(g->scratch_lp.reserve((size_t)std::min(chunk, T) * g->M));
@@ -2039,6 +2041,8 @@ int gmmmap_predict_device(vcmi_gmmmap *g, const double *dX, int64_t ldx, int64_t
       return dispatch_mfma<3>(g, dX, ldx, T, reinterpret_cast<double *>(didx), 0, st);
     return dispatch_mfma<2>(g, dX, ldx, T, reinterpret_cast<double *>(didx), 0, st);
   }
+  StreamOrderScope use(g->grp_order, st);         // (scratch_lp: see gmmmap_convert_device)
+  VCMI_TRY(use.status());
   VCMI_TRY(g->scratch_lp.reserve((size_t)T * g->M));
   VCMI_TRY(gmmmap_logdens_device(g, dX, ldx, T, g->scratch_lp.p, st));
   hipLaunchKernelGGL(posterior_finish_kernel<1>, dim3(posterior_finish_grid(g->M, T)), dim3(256), 0, st, g->scratch_lp.p,

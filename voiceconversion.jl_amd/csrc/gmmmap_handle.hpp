@@ -59,7 +59,7 @@ struct vcmi_gmmmap {
   vcmi::DevBuf<double> gfrag16;   // the same operand split into bf16 hi + lo for gmmmap_group_key16_kernel
   // grp: key (T), perm (T), the chunk histograms (nchunks, M) and gbase (M + 1): the first sorted position of every group, gbase[M] = T
   vcmi::DevBuf<int> grp;
-  vcmi::StreamOrder grp_order;
+  vcmi::StreamOrder grp_order;   // orders every call that uses the handle's scratch: grp, grp_super and scratch_lp below
   // the grouping's super-chunk histograms: TWO tables of grp_super_stride ints, each all zero between the calls that use it
   // (launch_grouping, gmmmap.hip: call n adds into table n & 1 and clears the other one).  grp_super_used[i]: ints of table i
   // that the last call on it left non-zero; grp_super_ok: false until the tables are known to be in that state (new or grown
@@ -80,7 +80,7 @@ struct vcmi_gmmmap {
   vcmi::DevBuf<int> px_table;
   int px_table_dp = 0;
 
-  // grow-only device scratch (two-pass predict of the generic path)
+  // grow-only device scratch (two-pass predict of the generic path, fvconvert of 80 < D <= 160), under grp_order
   vcmi::DevBuf<double> scratch_lp;
 
   // constructor arguments, kept so that the converter can be re-created on the other devices of a device group
