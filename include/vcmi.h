@@ -357,7 +357,7 @@ int vcmi_traj_convert_batch_dev(vcmi_traj *t, int64_t n, const double *dX, const
 /* Toda'07 eqs. 30-36 instead of the suboptimum sequence of src/trajectory_gmmmap.jl:81-82: n >= 0 EM iterations after
  * the argmax solution.  0 (default) = the reference's conversion, unchanged.  E-step: gamma_{m,t} = P(m | X_t, (W y)_t) at the
  * current y, every mixture (none is pruned); M-step: the same banded solve with Qbar_t = sum_m gamma Q_m and
- * gbar_t = sum_m gamma Q_m E_{m,t} (statement: csrc/traj_em.hpp).  The setting belongs to the handle: vcmi_traj_convert,
+ * gbar_t = sum_m gamma Q_m E_{m,t} (statement: csrc/traj_em.hip).  The setting belongs to the handle: vcmi_traj_convert,
  * _batch, _batch_dev and the vcmi_vc_traj family (per chunk) honour it, also on the replicas of a device group.
  * iters < 0: VCMI_ERR_ARG; iters > 0 on a model with some (Q_m + Q_m')/2 not positive definite (no log-determinant):
  * VCMI_ERR_NOT_PD -- with 0 such a model converts as before.  A vcmi_trajgv over a handle with iters > 0 returns VCMI_ERR_ARG

@@ -1,4 +1,4 @@
-"""GPU: EM re-estimation of the trajectory over all mixtures (TrajectoryGMMMap(g, T, em_iters=n), csrc/traj_em.hpp) against the
+"""GPU: EM re-estimation of the trajectory over all mixtures (TrajectoryGMMMap(g, T, em_iters=n), csrc/traj_em.hip) against the
 numpy restatement tests/traj_em_restatement.py.  The inputs and what they have to satisfy are checked on the CPU by
 tests/test_traj_em_host.py; the references are computed once per case (traj_em_restatement.case_reference).
 

@@ -117,19 +117,21 @@ def test_constructW_structure(vc):
     assert W.nnz == D * T + 2 * D * (T - 1)
 
 
-def test_blocked_and_generic_solvers_agree(vc):
+@pytest.mark.parametrize("D,M,Ts", [(40, 8, (400, 57, 1)), (24, 2, (34, 5, 1)), (46, 2, (34, 5, 1))])
+def test_blocked_and_generic_solvers_agree(vc, D, M, Ts):
     """The MFMA-blocked banded Cholesky (default) against the runtime-D LDS-window kernel (the path of static dimensions
     without a blocked instantiation) and the MFMA g_t kernel against the one-workgroup-per-frame kernel: two independent
-    device implementations of src/trajectory_gmmmap.jl:85-105 on the same utterances."""
+    device implementations of src/trajectory_gmmmap.jl:85-105 on the same utterances.  D = 24 and 46 are the instantiations of
+    the blocked solver that test_vs_oracle_batch does not reach (it runs 12, 16, 20, 25, 32, 40 and, padded from 27, 30): three
+    block steps and more, fewer frames than a window, a single frame."""
     from voiceconversion_jl_amd import _lib
     from oracle import np_oracle as npo
-    D, M = 40, 8
     w, mu, sig = npo.synth_model(777, 4 * D, M, lam_lo=1e-3)
     g = vc.GMMMap(*julia_model(w, mu, sig))
-    t = vc.TrajectoryGMMMap(g, 400)
+    t = vc.TrajectoryGMMMap(g, max(Ts))
     rng = np.random.default_rng(5)
     Xs = []
-    for T in (400, 57, 1):
+    for T in Ts:
         static = npo.sample_frames(int(rng.integers(1 << 30)), w, mu, sig, T, 0, D)
         static = np.cumsum(static, axis=0) / np.sqrt(np.arange(1, T + 1))[:, None]
         Xs.append(npo.push_delta(static).T)

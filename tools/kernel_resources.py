@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Resource lines of every kernel in the device assembly that `hipcc --save-temps` (or `--offload-device-only -S`) leaves for a
-translation unit, and, given a second file, the kernels whose lines differ between the two:
+translation unit, and, given a second file, the kernels whose lines differ between the two (either side may be several files
+joined by commas, for code that moved between translation units):
 
     hipcc -O3 -std=c++17 --offload-arch=gfx950 -fno-fast-math -mllvm -amdgpu-mfma-vgpr-form --offload-device-only -S \\
         voiceconversion.jl_amd/csrc/gmmmap.hip -o gmmmap.s
@@ -14,7 +15,14 @@ import subprocess
 import sys
 
 
-def parse(path):
+def parse(paths):
+    out = {}
+    for path in paths.split(","):
+        out.update(parse_one(path))
+    return out
+
+
+def parse_one(path):
     s = open(path).read()
     out = {}
     for blk in s[s.index("amdhsa.kernels:"):].split("  - .agpr_count:")[1:]:

@@ -1,4 +1,4 @@
-"""EM re-estimation of the trajectory (TrajectoryGMMMap(g, T, em_iters=n), csrc/traj_em.hpp) beside the arg-max conversion of
+"""EM re-estimation of the trajectory (TrajectoryGMMMap(g, T, em_iters=n), csrc/traj_em.hip) beside the arg-max conversion of
 the same input, device-resident (vcmi_traj_convert_batch_dev), one GPU, one process.
 
 Inputs: cfg5 (static D = 40, M = 64, --utts x 2000 frames) with an OVERLAPPING synthetic model (every frame a blend: the table's

@@ -1,4 +1,4 @@
-// gmmmap_handle.hpp -- the opaque vcmi_gmmmap handle (shared by gmmmap.hip, gmmmap_prepare.cpp, estep_full.hip, gmm_em.hip and traj.hip).
+// gmmmap_handle.hpp -- the opaque vcmi_gmmmap handle (shared by gmmmap.hip, gmmmap_prepare.cpp, estep_full.hip, gmm_em.hip and the traj*.hip files).
 #pragma once
 #include "vcmi_common.hpp"
 #include "gmmmap_layout.hpp"

@@ -530,3 +530,30 @@ int gmm_px_create(const double *w, const double *mu, const double *sigma, int D,
 }
 
 }  // namespace vcmi
+
+// diffgmm(params) -- src/diffgmm.jl:9-25, on the joint parameters mu (2D,M), sigma (2D,2D,M) (host arithmetic: a
+// one-time parameter transform).  Feed the result to vcmi_gmmmap_create for the differential converter.
+extern "C" int vcmi_diffgmm(const double *mu, const double *sigma, int Dj, int M, double *mu_out, double *sigma_out) {
+  if (!mu || !sigma || !mu_out || !sigma_out) return vcmi::fail(VCMI_ERR_ARG, "vcmi_diffgmm: NULL argument");
+  if (Dj < 2 || (Dj & 1) || M < 1) return vcmi::fail(VCMI_ERR_DIM, "vcmi_diffgmm: joint dimension %d / mixtures %d invalid", Dj, M);
+  const int D = Dj / 2;
+  for (int m = 0; m < M; ++m) {
+    const double *S = sigma + (size_t)Dj * Dj * m;
+    double *O = sigma_out + (size_t)Dj * Dj * m;
+    for (int d = 0; d < D; ++d) {
+      const double mx = mu[d + (size_t)Dj * m], my = mu[D + d + (size_t)Dj * m];
+      mu_out[d + (size_t)Dj * m] = mx;
+      mu_out[D + d + (size_t)Dj * m] = my - mx;                                  // eq. (6)
+    }
+    for (int c = 0; c < D; ++c)
+      for (int r = 0; r < D; ++r) {
+        const double xx = S[r + (size_t)Dj * c], xy = S[r + (size_t)Dj * (D + c)], yx = S[(D + r) + (size_t)Dj * c],
+                     yy = S[(D + r) + (size_t)Dj * (D + c)];
+        O[r + (size_t)Dj * c] = xx;
+        O[r + (size_t)Dj * (D + c)] = xy - xx;                                    // eq. (7)
+        O[(D + c) + (size_t)Dj * r] = xy - xx;                                    // its transpose
+        O[(D + r) + (size_t)Dj * (D + c)] = xx + yy - xy - yx;                    // eq. (8)
+      }
+  }
+  return VCMI_OK;
+}

@@ -5,7 +5,7 @@
 //   vcmi_variance_scaling / _dev     per row sqrt(sigma2 / var) (x - mean) + mean, Julia's corrected variance, in place allowed
 //   vcmi_vc_frames_postf             vc(g::GMMMap, fm) with fvpostf! applied to the converted rows before the download
 //   vc_traj_pre_device / vc_traj_post_device   the two ends of vc(c::TrajectoryConverter, fm) around the chunk conversions
-//                                    (vc_traj_device in traj.hip: vcmi_vc_traj_postf, vcmi_vc_traj_static, vcmi_vc_trajgv, *_dev)
+//                                    (vc_traj_device in traj_vc.cpp: vcmi_vc_traj_postf, vcmi_vc_traj_static, vcmi_vc_trajgv, *_dev)
 // One kernel, vs_scale_kernel, holds fvpostf!'s scale: variance_scaling_device runs it in place or into another matrix,
 // vc_traj_post_device into rows 2..D+1 of vc's result.  The host-pointer entries stage whole matrices in the per-thread
 // VcScratch (postf.hpp), freed on return above kVcScratchKeepBytes.  Everything is HBM-bound streaming: a frame is D contiguous

@@ -1,5 +1,5 @@
 // postf.hpp -- the pre / post steps of vc on DEVICE-RESIDENT matrices: push_delta (src/datasets.jl:6-13)
-// and the VarianceScaling post-filter (src/gv.jl:10-15), shared by postf.hip (C entries) and traj.hip (vc_traj_device, the
+// and the VarianceScaling post-filter (src/gv.jl:10-15), shared by postf.hip (C entries) and traj_vc.cpp (vc_traj_device, the
 // routine behind vcmi_vc_traj_postf / vcmi_vc_traj_static / vcmi_vc_trajgv and their *_dev forms), and the whole-matrix device
 // scratch of the host-pointer entries of both files.
 #pragma once
@@ -36,7 +36,7 @@ int vc_traj_post_device(const double *dy, int D, int64_t T, const double *dstat,
 // holds a Release for the call: on every way out it waits for the device and frees the three once together they exceed
 // kVcScratchKeepBytes, so one long utterance does not keep its footprint for the life of the thread.
 static constexpr size_t kVcScratchKeepBytes = (size_t)256 << 20;
-// Cap of the precision table [Q_1..Q_M | Qbar of the mixed frames] of the trajectory converter's EM re-estimation (traj_em.hpp): a
+// Cap of the precision table [Q_1..Q_M | Qbar of the mixed frames] of the trajectory converter's EM re-estimation (traj_em.hip): a
 // batch is processed in slices of whole utterances whose worst case -- every frame mixed -- stays under it (a single longer
 // utterance is a slice of its own).  cfg5 (256 x 2000 frames, D = 40: 51 KB per mixed frame, 26 GB in all) runs in two slices.
 static constexpr size_t kTrajEmTableCapBytes = (size_t)16 << 30;

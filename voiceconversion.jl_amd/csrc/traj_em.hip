@@ -1,5 +1,6 @@
-// traj_em.hpp -- EM re-estimation of the trajectory over ALL mixtures (Toda, Black, Tokuda 2007, eqs. 30-36) in place of the
-// suboptimum mixture sequence of src/trajectory_gmmmap.jl:81-82 (their eq. 37).  Included by traj.hip (shares its statics).
+// traj_em.hip -- EM re-estimation of the trajectory over ALL mixtures (Toda, Black, Tokuda 2007, eqs. 30-36) in place of the
+// suboptimum mixture sequence of src/trajectory_gmmmap.jl:81-82 (their eq. 37).  The kernels, the loop (traj_internal.hpp:
+// traj_em_run) and the EM entries.
 //
 // Statement (restated in numpy in tests/traj_em_restatement.py).  Notation of traj.hip:9-17, every array unsymmetrised as the
 // handle holds it:  Q_m = Dy_m,  E_{m,t} = b_m + A_m X_t,  pi_{m,t} = P(m | X_t) (src/gmm.jl:24-30; w_m <= 0 excluded),
@@ -17,11 +18,17 @@
 // traj_em_g_kernel: the same tiling, gbar_t over the mixtures some frame of the workgroup gives weight.  traj_em_valu_kernel:
 // both for feature dimensions without fragments (NT > 6), one workgroup per frame like traj_g_kernel.  traj_em_scan_kernel
 // compacts the mixed frames, traj_em_blend_kernel writes their Qbar_t behind the model's M matrices in one table.
-#pragma once
+#include "traj_internal.hpp"
+#include "hostpipe.hpp"
+#include "postf.hpp"
+
+#include <algorithm>
+#include <functional>
+
+namespace vcmi {
 
 static constexpr int kEmNB = 4;              // 16-frame tiles per workgroup of the MFMA kernels
 static constexpr int kEmF = 16 * kEmNB;      // ... frames
-static constexpr double kEmLog2Pi = 1.8378770664093454835606594728112;
 
 // (W y)_t, row `row` of [static ; delta]
 __device__ __forceinline__ double em_stencil(const double *__restrict__ y, int D, int T, int t, int row) {
@@ -392,3 +399,250 @@ traj_em_blend_kernel(const double *__restrict__ Qtab, int M, int64_t E, const do
   }
 }
 
+// ---- host side ------------------------------------------------------------------------------------------------------
+// log pi_{m,t} of every frame of the call into em_lp (the weights come from X alone: once per call)
+static int traj_em_prior(vcmi_traj *t, const std::vector<TrajUtt> &utts, int64_t nframes, bool contiguous, const double *dX0,
+                         hipStream_t st) {
+  const int D2 = t->D2, M = t->M;
+  VCMI_TRY(t->em_lp.reserve((size_t)nframes * M));
+  if (contiguous) {
+    VCMI_TRY(gmmmap_logdens_device(t->g, dX0, D2, nframes, t->em_lp.p, st));
+  } else {
+    for (auto &u : utts)
+      if (u.T > 0) VCMI_TRY(gmmmap_logdens_device(t->g, u.X, D2, u.T, t->em_lp.p + (size_t)u.frame0 * M, st));
+  }
+  hipLaunchKernelGGL(traj_em_logprior_kernel, dim3((unsigned)((nframes + 255) / 256)), dim3(256), 0, st, t->em_lp.p, M, nframes);
+  VCMI_HIP(hipGetLastError());
+  return VCMI_OK;
+}
+
+// E-step of the (uploaded) utterances du[0 .. nu) at the y in their Y matrices: gamma, lse and the flags; with_g: gbar into gbuf
+// as well.  Tmax: their longest.
+static int traj_em_estep(vcmi_traj *t, const TrajUtt *du, int nu, int Tmax, int64_t nframes, bool with_g, hipStream_t st,
+                         hipEvent_t mid = nullptr) {
+  const int D2 = t->D2, M = t->M;
+  VCMI_TRY(t->em_gamma.reserve((size_t)nframes * M));
+  VCMI_TRY(t->em_lse.reserve((size_t)nframes));
+  VCMI_TRY(t->em_pure.reserve((size_t)nframes));
+  if (t->NT <= 6 && !debug_flag(kDbgTrajGScalar)) {
+    const int nthr = 64 * t->NT;
+    const dim3 grid((unsigned)((Tmax + kEmF - 1) / kEmF), (unsigned)nu);
+    const size_t tiles = ((size_t)kEmNB * 4 * t->KS * 16 + (size_t)kEmNB * 4 * t->NT * 64) * sizeof(double);
+    const size_t shp = tiles + (size_t)t->NT * kEmF * sizeof(double), shg = tiles + (size_t)M * sizeof(int);
+    VCMI_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(traj_em_post_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shp));
+    hipLaunchKernelGGL(traj_em_post_kernel, grid, dim3(nthr), shp, st, du, D2, M, t->KS, t->Afrag.p, t->Qfrag.p, t->bvec.p, t->cm.p,
+                       t->em_lp.p, t->em_gamma.p, t->em_lse.p, t->em_pure.p);
+    if (mid) VCMI_HIP(hipEventRecord(mid, st));
+    if (with_g) {
+      VCMI_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(traj_em_g_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shg));
+      hipLaunchKernelGGL(traj_em_g_kernel, grid, dim3(nthr), shg, st, du, D2, M, t->KS, t->Afrag.p, t->Qfrag.p, t->bvec.p,
+                         t->em_gamma.p, t->gbuf.p);
+    }
+  } else {
+    const size_t shv = ((size_t)4 * D2 + 256 + M) * sizeof(double);
+    VCMI_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(traj_em_valu_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shv));
+    hipLaunchKernelGGL(traj_em_valu_kernel, dim3((unsigned)Tmax, (unsigned)nu), dim3(256), shv, st, du, D2, M, t->AT.p, t->QT.p, t->bvec.p,
+                       t->cm.p, t->em_lp.p, t->em_gamma.p, t->em_lse.p, t->em_pure.p, t->gbuf.p, with_g ? 1 : 0);
+    if (mid) VCMI_HIP(hipEventRecord(mid, st));     // (one kernel does both: its time counts as E-step)
+  }
+  VCMI_HIP(hipGetLastError());
+  return VCMI_OK;
+}
+
+// em_iters E/M pairs after the arg-max solve of traj_run.  The table is sized by the mixed-frame count, one 4-byte read per
+// iteration (the only host synchronisation of the loop); the batch (sorted, uploaded at du) starts as ONE slice and is cut into
+// slices of whole utterances only where that count would take the table past kTrajEmTableCapBytes.
+int traj_em_run(vcmi_traj *t, const std::vector<TrajUtt> &utts, const TrajSolvePlan &plan, bool contiguous, const double *dX0,
+                hipStream_t st) {
+  if (!t->em_pd) return fail(VCMI_ERR_NOT_PD, "TrajectoryGMMMap: EM needs (Q_m + Q_m')/2 positive definite");
+  const int n = plan.n;
+  const int64_t nframes = plan.nframes;
+  const TrajUtt *du = plan.du;
+  if (nframes > INT32_MAX) return fail(VCMI_ERR_DIM, "TrajectoryGMMMap: too many frames in one call for EM");
+  const int M = t->M, iters = t->em_iters;
+  const int64_t E = (int64_t)4 * plan.Ds * plan.Ds;
+  const double *Qsrc = plan.padded ? t->Qpad.p : t->Q.p;
+  VCMI_TRY(traj_em_prior(t, utts, nframes, contiguous, dX0, st));
+  VCMI_TRY(t->em_mh.reserve((size_t)nframes));
+  VCMI_TRY(t->em_mix.reserve((size_t)nframes + 1));
+  VCMI_TRY(t->em_L.reserve((size_t)iters * n));
+  struct Events {
+    hipEvent_t e[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    ~Events() {
+      for (hipEvent_t x : e)
+        if (x) (void)hipEventDestroy(x);
+    }
+    hipEvent_t &operator[](int k) { return e[k]; }
+  } ev;
+  if (t->em_time)
+    for (int k = 0; k < 5; ++k) VCMI_HIP(hipEventCreate(&ev[k]));
+  // iterations it0 .. iters-1 of the (sorted) utterances [b0, b0 + nb).  A slice whose table would pass the cap at some
+  // iteration is cut in two there (by frames) and each half goes on from that iteration by itself: its E-step is repeated on
+  // the same y, so the results do not depend on where the cuts fall.  One utterance is never cut.
+  const size_t cap = t->em_cap_bytes ? t->em_cap_bytes : kTrajEmTableCapBytes;
+  std::function<int(int, int, int)> run_slice = [&](int b0, int nb, int it0) -> int {
+    const int Tmax = utts[(size_t)b0].T;                // (longest first)
+    int64_t fs = 0;
+    for (int u = 0; u < nb; ++u) fs += utts[(size_t)(b0 + u)].T;
+    for (int it = it0; it < iters; ++it) {
+      if (Tmax == 0) {                                  // only empty utterances: L = 0
+        hipLaunchKernelGGL(traj_em_sum_kernel, dim3((unsigned)nb), dim3(256), 0, st, du + b0, t->em_lse.p, t->em_L.p + (size_t)it * n);
+        continue;
+      }
+      if (t->em_time) VCMI_HIP(hipEventRecord(ev[0], st));
+      VCMI_TRY(traj_em_estep(t, du + b0, nb, Tmax, nframes, true, st, t->em_time ? ev[1] : nullptr));
+      if (t->em_time) VCMI_HIP(hipEventRecord(ev[2], st));
+      hipLaunchKernelGGL(traj_em_sum_kernel, dim3((unsigned)nb), dim3(256), 0, st, du + b0, t->em_lse.p, t->em_L.p + (size_t)it * n);
+      int *dcount = t->em_mix.p + nframes;
+      hipLaunchKernelGGL(traj_em_scan_kernel, dim3(1), dim3(1024), 0, st, du + b0, nb, M, t->em_pure.p, t->em_mh.p, t->em_mix.p, dcount);
+      VCMI_HIP(hipGetLastError());
+      int count = 0;
+      VCMI_HIP(hipMemcpyAsync(&count, dcount, sizeof(int), hipMemcpyDeviceToHost, st));
+      VCMI_HIP(hipStreamSynchronize(st));
+      if (count < 0 || count > fs) return fail(VCMI_ERR_HIP, "TrajectoryGMMMap: EM flag scan returned %d mixed frames of %lld", count, (long long)fs);
+      const size_t table = (size_t)(M + count) * (size_t)E;
+      if (table * sizeof(double) > cap && nb > 1) {
+        int h = 0;
+        for (int64_t f = 0; h < nb - 1 && 2 * f < fs; ++h) f += utts[(size_t)(b0 + h)].T;
+        h = std::max(h, 1);
+        VCMI_TRY(run_slice(b0, h, it));
+        return run_slice(b0 + h, nb - h, it);
+      }
+      VCMI_TRY(t->em_table.reserve(table));
+      VCMI_HIP(hipMemcpyAsync(t->em_table.p, Qsrc, sizeof(double) * (size_t)M * (size_t)E, hipMemcpyDeviceToDevice, st));
+      if (count > 0) {
+        const unsigned chunks = (unsigned)std::min<int64_t>(((E + 15) / 16 + 3) / 4, 8);
+        hipLaunchKernelGGL(traj_em_blend_kernel, dim3((unsigned)((count + 15) / 16), chunks), dim3(256), 0, st, Qsrc, M, E, t->em_gamma.p,
+                           t->em_mix.p, count, t->em_table.p + (size_t)M * (size_t)E);
+        VCMI_HIP(hipGetLastError());
+      }
+      if (t->em_time) VCMI_HIP(hipEventRecord(ev[3], st));
+      VCMI_TRY(traj_solve_launch(t, plan, t->em_table.p, t->em_mh.p, b0, nb, st));
+      if (t->em_time) {
+        VCMI_HIP(hipEventRecord(ev[4], st));
+        VCMI_HIP(hipEventSynchronize(ev[4]));
+        float ms[4] = {0.f, 0.f, 0.f, 0.f};
+        for (int k = 0; k < 4; ++k) VCMI_HIP(hipEventElapsedTime(&ms[k], ev[k], ev[k + 1]));
+        EmTimes &m = t->em_times;
+        m.estep_ms += ms[0];
+        m.gbar_ms += ms[1];
+        m.blend_ms += ms[2];
+        m.solve_ms += ms[3];
+        m.mixed_frames += count;
+        m.frames += fs;
+        m.table_bytes = std::max(m.table_bytes, table * sizeof(double));
+        m.slices += 1;
+      }
+    }
+    return VCMI_OK;
+  };
+  VCMI_TRY(run_slice(0, n, 0));
+  t->em_run_iters = iters;
+  t->em_run_n = n;
+  return VCMI_OK;
+}
+
+// the EM scratch of the handle in bytes: what the release rule weighs
+static size_t traj_em_scratch_bytes(const vcmi_traj *t) {
+  return (t->em_lp.n + t->em_gamma.n + t->em_lse.n + t->em_table.n + t->em_L.n + t->em_mh.n) * sizeof(double) +
+         (t->em_pure.n + t->em_mix.n) * sizeof(int);
+}
+
+void traj_em_release(vcmi_traj *t) {
+  if (traj_em_scratch_bytes(t) <= kVcScratchKeepBytes) return;
+  t->em_lp.release();
+  t->em_gamma.release();
+  t->em_lse.release();
+  t->em_table.release();
+  t->em_L.release();
+  t->em_mh.release();
+  t->em_pure.release();
+  t->em_mix.release();
+}
+
+TrajEmRelease::~TrajEmRelease() {
+  if (!t->em_table.p && !t->em_gamma.p) return;
+  if (traj_em_scratch_bytes(t) <= kVcScratchKeepBytes) return;
+  (void)hipDeviceSynchronize();
+  traj_em_release(t);
+}
+
+}  // namespace vcmi
+
+using namespace vcmi;
+
+// ---- EM re-estimation: the setting, the objective, the history -----------------------------------------------------------
+extern "C" int vcmi_traj_set_em(vcmi_traj *t, int iters) {
+  if (!t) return fail(VCMI_ERR_ARG, "vcmi_traj_set_em: NULL handle");
+  if (iters < 0) return fail(VCMI_ERR_ARG, "vcmi_traj_set_em: negative iteration count");
+  if (iters > 0 && !t->em_pd)
+    return fail(VCMI_ERR_NOT_PD, "vcmi_traj_set_em: (Q_m + Q_m')/2 of some mixture is not positive definite: the EM objective is undefined");
+  t->em_iters = iters;
+  return VCMI_OK;
+}
+extern "C" int vcmi_traj_get_em(const vcmi_traj *t) { return t ? t->em_iters : -1; }
+// Measurement hook (not part of include/vcmi.h; tools/traj_em_bench.py): with enable != 0 the EM loop of this handle records hip
+// events around its steps (and waits for them once per iteration).  out (8): ms of E-step, gbar, flag scan + count read + blend,
+// pad + solve; mixed frames; largest table in bytes; frames; slice-iterations -- accumulated since the last call, which resets them.
+extern "C" int vcmi_debug_traj_em_times(vcmi_traj *t, int enable, double *out) {
+  if (!t) return fail(VCMI_ERR_ARG, "vcmi_debug_traj_em_times: NULL handle");
+  const EmTimes &m = t->em_times;
+  const double v[8] = {m.estep_ms, m.gbar_ms, m.blend_ms, m.solve_ms, (double)m.mixed_frames, (double)m.table_bytes, (double)m.frames,
+                       (double)m.slices};
+  for (int k = 0; out && k < 8; ++k) out[k] = v[k];
+  t->em_times = EmTimes();
+  t->em_time = enable != 0;
+  return VCMI_OK;
+}
+// Test hook (not part of include/vcmi.h): the table cap of this handle's EM loop in bytes, so that the slicing can be tested
+// on small inputs; 0 restores kTrajEmTableCapBytes.  (A setting of one handle: nothing process-wide.)
+extern "C" int vcmi_debug_traj_em_cap(vcmi_traj *t, size_t bytes) {
+  if (!t) return fail(VCMI_ERR_ARG, "vcmi_debug_traj_em_cap: NULL handle");
+  t->em_cap_bytes = bytes;
+  return VCMI_OK;
+}
+
+extern "C" int vcmi_traj_em_history(const vcmi_traj *t, double *L, int cap) {
+  if (!t || (cap > 0 && !L) || cap < 0) return fail(VCMI_ERR_ARG, "vcmi_traj_em_history: bad argument");
+  for (int k = 0; k < cap; ++k) L[k] = k < (int)t->em_hist.size() ? t->em_hist[(size_t)k] : NAN;
+  return VCMI_OK;
+}
+
+extern "C" int vcmi_traj_cond_loglik_dev(vcmi_traj *t, const double *dX, const double *dY, int64_t T, double *dL, void *stream) {
+  if (!t || !dL) return fail(VCMI_ERR_ARG, "vcmi_traj_cond_loglik_dev: NULL argument");
+  if (T < 0 || T > INT32_MAX || (T > 0 && (!dX || !dY))) return fail(VCMI_ERR_ARG, "vcmi_traj_cond_loglik_dev: bad argument");
+  if (!t->em_pd) return fail(VCMI_ERR_NOT_PD, "vcmi_traj_cond_loglik: (Q_m + Q_m')/2 of some mixture is not positive definite");
+  hipStream_t st = as_stream(stream);
+  if (T == 0) {
+    VCMI_HIP(hipMemsetAsync(dL, 0, sizeof(double), st));
+    return VCMI_OK;
+  }
+  std::vector<TrajUtt> utts(1, TrajUtt{dX, const_cast<double *>(dY), 0, (int32_t)T, 0});
+  VCMI_TRY(t->uttbuf.reserve(sizeof(TrajUtt)));
+  VCMI_HIP(hipStreamSynchronize(st));       // (the descriptor buffer is shared with the conversion calls)
+  VCMI_TRY(upload_now(t->uttbuf.p, utts.data(), sizeof(TrajUtt)));
+  const TrajUtt *du = reinterpret_cast<const TrajUtt *>(t->uttbuf.p);
+  VCMI_TRY(t->gbuf.reserve((size_t)T * t->D2));
+  VCMI_TRY(traj_em_prior(t, utts, T, true, dX, st));
+  VCMI_TRY(traj_em_estep(t, du, 1, (int)T, T, false, st));
+  hipLaunchKernelGGL(traj_em_sum_kernel, dim3(1), dim3(256), 0, st, du, t->em_lse.p, dL);
+  VCMI_HIP(hipGetLastError());
+  return VCMI_OK;
+}
+
+extern "C" int vcmi_traj_cond_loglik(vcmi_traj *t, const double *X, const double *Y, int64_t T, double *L) {
+  if (!t || !L) return fail(VCMI_ERR_ARG, "vcmi_traj_cond_loglik: NULL argument");
+  if (T < 0 || T > INT32_MAX || (T > 0 && (!X || !Y))) return fail(VCMI_ERR_ARG, "vcmi_traj_cond_loglik: bad argument");
+  *L = 0.0;
+  if (T == 0) return VCMI_OK;
+  VCMI_TRY(t->xbuf.reserve((size_t)T * t->D2));
+  VCMI_TRY(t->ybuf.reserve((size_t)T * t->D + 1));
+  VCMI_TRY(upload_now(t->xbuf.p, X, sizeof(double) * T * t->D2));
+  VCMI_TRY(upload_now(t->ybuf.p, Y, sizeof(double) * T * t->D));
+  double *dL = t->ybuf.p + (size_t)T * t->D;
+  VCMI_TRY(vcmi_traj_cond_loglik_dev(t, t->xbuf.p, t->ybuf.p, T, dL, nullptr));
+  VCMI_HIP(hipStreamSynchronize(nullptr));
+  VCMI_HIP(hipMemcpy(L, dL, sizeof(double), hipMemcpyDeviceToHost));
+  traj_em_release(t);
+  return VCMI_OK;
+}

@@ -1,0 +1,572 @@
+// traj_gv.hip -- TrajectoryGVGMMMap (reference src/trajectory_gmmmap.jl:114-189): the handle, the two kernels of the
+// global-variance ascent on solved trajectories, and the host function that chooses between them (traj_internal.hpp:
+// traj_gv_launch).
+#include "traj_internal.hpp"
+#include "traj_blk_prof.hpp"
+#include "host_linalg.hpp"
+#include "hostpipe.hpp"
+
+namespace vcmi {
+
+// ------------------------------------------------------------------------------------------------
+// Global-variance ascent, fvconvert(tgv::TrajectoryGVGMMMap, X), src/trajectory_gmmmap.jl:139-189.
+// One workgroup per utterance runs all epochs:  y <- y + alpha * ( omega (r - P y) + gvgrad(y) ),  omega = 1/(2T),
+// with P y = W' D^-1 W y applied as  u_t = [y_t ; (y_{t+1} - y_{t-1})/2]  ->  v_t = Q_mhat_t u_t  ->
+// (P y)_t = vs_t + vd_{t-1}/2 - vd_{t+1}/2  (the stencil of W; W is never built) and r = W' D^-1 E from the g_t the
+// solve already has.  v = Q u runs on v_mfma_f64_16x16x4 over tiles of 16 consecutive frames: wave i owns row tile i
+// of Q; the tile's frames usually share one or two mixtures, so the product is accumulated over the DISTINCT
+// mixtures of the tile with the B operand masked to that mixture's frames (exact: the other frames add 0).
+// ------------------------------------------------------------------------------------------------
+template <typename YP>
+__device__ void gv_moments(YP y, int D, int T, int nthr, double *red, double *mean, double *var) {
+  const int tid = threadIdx.x;
+  const int NG = nthr / D;                 // frame groups per dimension
+  const int d = tid % D, g = tid / D;
+  double s = 0.0;
+  if (g < NG) {
+    // 8 loads in flight per thread (a plain loop keeps one: with one workgroup per CU the passes of this kernel are
+    // bound by memory-level parallelism, not by HBM bandwidth); the additions stay in frame order
+    int t = g;
+    for (; t + 7 * NG < T; t += 8 * NG) {
+      double v[8];
+#pragma unroll
+      for (int q = 0; q < 8; ++q) v[q] = y[(size_t)(t + q * NG) * D + d];
+#pragma unroll
+      for (int q = 0; q < 8; ++q) s += v[q];
+    }
+    for (; t < T; t += NG) s += y[(size_t)t * D + d];
+  }
+  if (g < NG) red[g * D + d] = s;
+  __syncthreads();
+  if (tid < D) {
+    double m = 0.0;
+    for (int k = 0; k < NG; ++k) m += red[k * D + tid];
+    mean[tid] = m / (double)T;
+  }
+  __syncthreads();
+  s = 0.0;
+  if (g < NG) {
+    const double m = mean[d];
+    int t = g;
+    for (; t + 7 * NG < T; t += 8 * NG) {
+      double v[8];
+#pragma unroll
+      for (int q = 0; q < 8; ++q) v[q] = y[(size_t)(t + q * NG) * D + d];
+#pragma unroll
+      for (int q = 0; q < 8; ++q) {
+        const double e = v[q] - m;
+        s = fma(e, e, s);
+      }
+    }
+    for (; t < T; t += NG) {
+      const double e = y[(size_t)t * D + d] - m;
+      s = fma(e, e, s);
+    }
+    red[g * D + d] = s;
+  }
+  __syncthreads();
+  if (tid < D) {
+    double v = 0.0;
+    for (int k = 0; k < NG; ++k) v += red[k * D + tid];
+    var[tid] = v / (double)(T - 1);        // Julia's var: corrected
+  }
+  __syncthreads();
+}
+
+typedef double gv_d4 __attribute__((ext_vector_type(4)));
+static constexpr int kGvNB = 8;   // 16-frame tiles per round of the GV product
+static constexpr int kGvMaxKS = 24;   // k-steps of the widest supported feature vector (2D <= 96)
+
+__global__ void __launch_bounds__(384)
+traj_gv_kernel(const TrajUtt *__restrict__ utts, int n, int D, int M, int KS, const double *__restrict__ Qfrag,
+               const int64_t *__restrict__ mhat_all, const double *__restrict__ g_all, double *__restrict__ ws_all,
+               int64_t ws_stride, TrajGV gv) {
+  extern __shared__ double gsm[];
+  const int D2 = 2 * D, nthr = blockDim.x, NT = nthr >> 6;
+  double *Ut = gsm;                        // [kGvNB][4*KS][16]  u of the tiles' frames, k-major
+  double *red = Ut + (size_t)kGvNB * 4 * KS * 16;  // [2][nthr]
+  double *mean = red + 2 * nthr;           // [D]
+  double *var = mean + D;                  // [D]
+  double *coef = var + D;                  // [D]
+  int *cnt = reinterpret_cast<int *>(coef + D);   // [M] frames per mixture, then the fill cursor
+  int *start = cnt + M;                           // [M] first slot of the mixture's (16-padded) segment
+  __shared__ int tidx[16 * kGvNB];
+  __shared__ int ntiles_s;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int lcol = lane & 15, lgrp = lane >> 4;
+
+  for (int u = blockIdx.x; u < n; u += gridDim.x) {
+    const TrajUtt U = utts[u];
+    const int T = U.T;
+    if (T < 2) continue;                   // var() of one frame is undefined; the host rejects such calls
+    const int64_t *mh = mhat_all + U.frame0;
+    const double *g = g_all + U.frame0 * D2;
+    gdouble *y = (gdouble *)U.Y;
+    double *V = ws_all + (size_t)blockIdx.x * ws_stride;   // [T][2D]
+    double *R = V + (size_t)T * D2;                        // [T][D]   r = W' D^-1 E
+    int *perm = reinterpret_cast<int *>(R + (size_t)T * D); // frames grouped by mixture, segments padded to 16 with -1
+    const double omega = 1.0 / (2.0 * (double)T);
+
+    // frames grouped by mixture (the selection mhat is fixed over the epochs): every 16-frame tile of the product
+    // below then has ONE mixture.  The order inside a group comes from atomics and is irrelevant: each frame's
+    // product is computed independently.
+    for (int m = tid; m < M; m += nthr) cnt[m] = 0;
+    __syncthreads();
+    for (int t = tid; t < T; t += nthr) atomicAdd(&cnt[(int)mh[t] - 1], 1);
+    __syncthreads();
+    if (tid == 0) {
+      int pos = 0;
+      for (int m = 0; m < M; ++m) {
+        start[m] = pos;
+        pos += (cnt[m] + 15) / 16 * 16;
+        cnt[m] = 0;
+      }
+      ntiles_s = pos / 16;
+    }
+    __syncthreads();
+    const int ntiles = ntiles_s;
+    for (int e = tid; e < ntiles * 16; e += nthr) perm[e] = -1;
+    __syncthreads();
+    for (int t = tid; t < T; t += nthr) {
+      const int m = (int)mh[t] - 1;
+      perm[start[m] + atomicAdd(&cnt[m], 1)] = t;
+    }
+
+    // eq. (58): y <- sqrt(mu^v / var(y)) (y - mean) + mean, src/trajectory_gmmmap.jl:152; and r.
+    // Every pass that writes y also accumulates the moments of what it writes (thread = (dimension d, frame group g),
+    // the mapping of gv_moments): sum (y - c) and sum (y - c)^2 with the shift c = mean before the pass, so that
+    // mean = c + S1/T, var = (S2 - S1^2/T)/(T-1) lose nothing to cancellation and the next epoch needs no pass of
+    // its own over y for them.
+    gv_moments(y, D, T, nthr, red, mean, var);
+    const int NGm = nthr / D, dm = tid % D, gm = tid / D;
+    auto finish_moments = [&](double s1, double s2) {
+      if (gm < NGm) {
+        red[gm * D + dm] = s1;
+        red[nthr + gm * D + dm] = s2;
+      }
+      __syncthreads();
+      if (tid < D) {
+        double a1 = 0.0, a2 = 0.0;
+        for (int k = 0; k < NGm; ++k) {
+          a1 += red[k * D + tid];
+          a2 += red[nthr + k * D + tid];
+        }
+        mean[tid] += a1 / (double)T;
+        var[tid] = (a2 - a1 * a1 / (double)T) / (double)(T - 1);       // Julia's var: corrected
+      }
+      __syncthreads();
+    };
+    {
+      double s1 = 0.0, s2 = 0.0;
+      if (gm < NGm) {
+        const double mu = mean[dm], sc = sqrt(gv.muv[dm] / var[dm]);
+#pragma unroll 8
+        for (int t = gm; t < T; t += NGm) {
+          const size_t e = (size_t)t * D + dm;
+          const int tm = t >= 1 ? t - 1 : t, tp = t + 1 < T ? t + 1 : t;
+          const double yo = y[e], g0 = g[(size_t)t * D2 + dm], g1 = g[(size_t)tm * D2 + D + dm], g2 = g[(size_t)tp * D2 + D + dm];
+          const double yn = sc * (yo - mu) + mu;
+          y[e] = yn;
+          R[e] = (g0 + (t >= 1 ? 0.5 : 0.0) * g1) - (t + 1 < T ? 0.5 : 0.0) * g2;
+          const double dv = yn - mu;
+          s1 += dv;
+          s2 = fma(dv, dv, s2);
+        }
+      }
+      __syncthreads();
+      finish_moments(s1, s2);
+    }
+
+    double afr[kGvMaxKS];
+    int mcur = -1;
+    for (int ep = 0; ep < gv.epochs; ++ep) {
+      // gvgrad coefficients, src/trajectory_gmmmap.jl:171-189: -2/T (pv' (var(y) - mu^v)), times (y - mean) below;
+      // mean and var of the current y come from the pass that wrote it
+      if (tid < D) {
+        double s = 0.0;
+        for (int j = 0; j < D; ++j) s = fma(gv.pv[j + (size_t)D * tid], var[j] - gv.muv[j], s);
+        coef[tid] = -2.0 / (double)T * s;
+      }
+      // v_t = Q_mhat_t u_t for every frame: kGvNB single-mixture tiles of 16 frames per round, so that the gathers of
+      // y, the loads of the Q fragments and the barriers are paid once per 16*kGvNB frames
+      for (int tile0 = 0; tile0 < ntiles; tile0 += kGvNB) {
+        const int nb = (ntiles - tile0 < kGvNB) ? ntiles - tile0 : kGvNB;
+        if (tid < 16 * nb) tidx[tid] = perm[tile0 * 16 + tid];
+        __syncthreads();
+        // u_t = [y_t ; (y_{t+1} - y_{t-1})/2]: two unconditional loads per element on clamped addresses with 0 / 1 / +-1/2
+        // weights (a branch or a select on the loaded value would serialise the loads), eight elements in flight
+#pragma unroll 8
+        for (int e = tid; e < nb * 4 * KS * 16; e += nthr) {
+          const int b = e / (4 * KS * 16), q = e - b * (4 * KS * 16);
+          const int k = q >> 4, t = tidx[b * 16 + (q & 15)];
+          const bool ok = t >= 0 && k < D2, st = k < D;
+          const int tc = t >= 0 ? t : 0, kd = st ? (k < D ? k : 0) : (k < D2 ? k - D : 0);
+          const int tp = tc + 1 < T ? tc + 1 : tc, tm = tc >= 1 ? tc - 1 : tc;
+          const double a = y[(size_t)(st ? tc : tp) * D + kd], c = y[(size_t)(st ? tc : tm) * D + kd];
+          const double wa = !ok ? 0.0 : (st ? 1.0 : (tc + 1 < T ? 0.5 : 0.0)), wc = (!ok || st) ? 0.0 : (tc >= 1 ? -0.5 : 0.0);
+          Ut[e] = wa * a + wc * c;
+        }
+        __syncthreads();
+        for (int b = 0; b < nb; ++b) {
+          const int m = (int)mh[tidx[b * 16]] - 1;         // the tile's mixture (slot 0 of a tile is never padding)
+          if (m != mcur) {                                 // Q fragments of this wave's row tile: all k-steps in flight at
+            mcur = m;                                      // once, kept in registers while consecutive tiles share m
+            const double *A = Qfrag + (((size_t)m * NT + wave) * KS) * 64 + lane;
+#pragma unroll
+            for (int ks = 0; ks < kGvMaxKS; ++ks) afr[ks] = (ks < KS) ? A[(size_t)ks * 64] : 0.0;
+          }
+          const double *Ub = Ut + (size_t)b * 4 * KS * 16;
+          gv_d4 acc = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+          for (int ks = 0; ks < kGvMaxKS; ++ks)
+            if (ks < KS) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(afr[ks], Ub[(4 * ks + lgrp) * 16 + lcol], acc, 0, 0, 0);
+          const int t = tidx[b * 16 + lcol];
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const int row = 16 * wave + lgrp + 4 * r;
+            if (row < D2 && t >= 0) V[(size_t)t * D2 + row] = acc[r];
+          }
+        }
+        __syncthreads();
+      }
+      // y <- y + alpha * ( omega (r - P y) + coef (y - mean) ), eq. (52), src/trajectory_gmmmap.jl:163-166
+      double s1 = 0.0, s2 = 0.0;
+      if (gm < NGm) {
+        const double mu = mean[dm], cf = coef[dm];
+#pragma unroll 8
+        for (int t = gm; t < T; t += NGm) {
+          const size_t e = (size_t)t * D + dm;
+          const int tm = t >= 1 ? t - 1 : t, tp = t + 1 < T ? t + 1 : t;
+          const double vs = V[(size_t)t * D2 + dm], vm = V[(size_t)tm * D2 + D + dm], vp = V[(size_t)tp * D2 + D + dm];
+          const double yy = y[e], rr = R[e];
+          const double py = (vs + (t >= 1 ? 0.5 : 0.0) * vm) - (t + 1 < T ? 0.5 : 0.0) * vp;
+          const double dy = omega * (rr - py) + cf * (yy - mu);
+          const double yn = fma(gv.alpha, dy, yy);
+          y[e] = yn;
+          const double dv = yn - mu;
+          s1 += dv;
+          s2 = fma(dv, dv, s2);
+        }
+      }
+      __syncthreads();
+      finish_moments(s1, s2);
+    }
+  }
+}
+
+// ------------------------------------------------------------------------------------------------
+// traj_gv2_kernel: the same ascent with the product phase run by TWO teams of waves.  With one workgroup per CU the
+// product rounds of traj_gv_kernel are a chain  gather (memory latency) -> barrier -> MFMA + store -> barrier;  here
+// waves NT..2NT-1 gather the rows of y for round r+1 into the other of two LDS images of u while waves 0..NT-1 run the
+// MFMAs of round r -- one barrier per round, and the streaming passes (scaling, update, moments) run on twice the
+// threads.  The frame permutation and the tile mixtures live in LDS (no dependent global load in the rounds), which
+// bounds the utterance length; longer utterances take traj_gv_kernel.
+// ------------------------------------------------------------------------------------------------
+static constexpr int kGv2NB = 4;     // 16-frame tiles per round
+#ifndef VCMI_GV2_GB
+#define VCMI_GV2_GB 12
+#endif
+static constexpr int kGv2GB = VCMI_GV2_GB;   // elements of u a gather thread has in flight
+static constexpr int kGv2Threads = 768;   // 12 waves: NT = ceil(2D/16) MFMA waves, the rest gather (three waves per SIMD: 168 VGPRs)
+
+__global__ void __launch_bounds__(kGv2Threads)
+traj_gv2_kernel(const TrajUtt *__restrict__ utts, int n, int D, int M, int KS, int pcap, const double *__restrict__ Qfrag,
+                const int64_t *__restrict__ mhat_all, const double *__restrict__ g_all, double *__restrict__ ws_all,
+                int64_t ws_stride, TrajGV gv) {
+  extern __shared__ double gsm[];
+  const int D2 = 2 * D, nthr = blockDim.x, NT = (D2 + 15) / 16, nmf = 64 * NT, ngth = nthr - nmf;
+  const int UTS = 4 * KS * 17, UTR = kGv2NB * UTS;
+  double *Ut = gsm;                        // [2][kGv2NB][4*KS][17]  u of the tiles' frames, k-major, row stride 17
+  double *red = Ut + 2 * (size_t)UTR;      // [2][nthr]
+  double *mean = red + 2 * nthr;           // [D]
+  double *var = mean + D;                  // [D]
+  double *coef = var + D;                  // [D]
+  int *cnt = reinterpret_cast<int *>(coef + D);   // [M] frames per mixture, then the fill cursor
+  int *start = cnt + M;                           // [M] first slot of the mixture's (16-padded) segment
+  int *perm = start + M;                          // [pcap] frames grouped by mixture, segments padded to 16 with -1
+  int *tilem = perm + pcap;                       // [pcap / 16 + 1] mixture of every tile
+  __shared__ int ntiles_s;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int lcol = lane & 15, lgrp = lane >> 4;
+  const bool gatherer = wave >= NT;
+  const int gtid = tid - nmf;
+
+  for (int u = blockIdx.x; u < n; u += gridDim.x) {
+    const TrajUtt U = utts[u];
+    const int T = U.T;
+    if (T < 2) continue;                   // var() of one frame is undefined; the host rejects such calls
+    const int64_t *mh = mhat_all + U.frame0;
+    const double *g = g_all + U.frame0 * D2;
+    gdouble *y = (gdouble *)U.Y;
+    double *V = ws_all + (size_t)blockIdx.x * ws_stride;   // [T][2D]
+    double *R = V + (size_t)T * D2;                        // [T][D]   r = W' D^-1 E
+    const double omega = 1.0 / (2.0 * (double)T);
+
+    // frames grouped by mixture (see traj_gv_kernel)
+    for (int m = tid; m < M; m += nthr) cnt[m] = 0;
+    __syncthreads();
+    for (int t = tid; t < T; t += nthr) atomicAdd(&cnt[(int)mh[t] - 1], 1);
+    __syncthreads();
+    if (tid == 0) {
+      int pos = 0;
+      for (int m = 0; m < M; ++m) {
+        start[m] = pos;
+        pos += (cnt[m] + 15) / 16 * 16;
+        cnt[m] = 0;
+      }
+      ntiles_s = pos / 16;
+    }
+    __syncthreads();
+    const int ntiles = ntiles_s;
+    for (int e = tid; e < ntiles * 16; e += nthr) perm[e] = -1;
+    __syncthreads();
+    for (int t = tid; t < T; t += nthr) {
+      const int m = (int)mh[t] - 1;
+      perm[start[m] + atomicAdd(&cnt[m], 1)] = t;
+    }
+    __syncthreads();
+    for (int i = tid; i < ntiles; i += nthr) tilem[i] = (int)mh[perm[i * 16]] - 1;
+    for (int e = tid; e < 2 * UTR; e += nthr) Ut[e] = 0.0;      // rows k >= 2D of the k-padding stay zero
+    // elements of u a gather thread fetches in a round: e = gtid + i * ngth -> (frame slot e / 2D, k = e % 2D), k fastest
+    // across threads; one division here, increments in the rounds
+    const int gsl0 = gatherer ? gtid / D2 : 0, gk0 = gatherer ? gtid % D2 : 0, dsl = ngth / D2, dk = ngth % D2;
+
+    // eq. (58) and r; every pass that writes y accumulates the moments of what it writes (see traj_gv_kernel)
+    gv_moments(y, D, T, nthr, red, mean, var);
+    const int NGm = nthr / D, dm = tid % D, gm = tid / D;
+    auto finish_moments = [&](double s1, double s2) {
+      if (gm < NGm) {
+        red[gm * D + dm] = s1;
+        red[nthr + gm * D + dm] = s2;
+      }
+      __syncthreads();
+      if (tid < D) {
+        double a1 = 0.0, a2 = 0.0;
+        for (int k = 0; k < NGm; ++k) {
+          a1 += red[k * D + tid];
+          a2 += red[nthr + k * D + tid];
+        }
+        mean[tid] += a1 / (double)T;
+        var[tid] = (a2 - a1 * a1 / (double)T) / (double)(T - 1);       // Julia's var: corrected
+      }
+      __syncthreads();
+    };
+    {
+      double s1 = 0.0, s2 = 0.0;
+      if (gm < NGm) {
+        const double mu = mean[dm], sc = sqrt(gv.muv[dm] / var[dm]);
+#pragma unroll 4
+        for (int t = gm; t < T; t += NGm) {
+          const size_t e = (size_t)t * D + dm;
+          const int tm = t >= 1 ? t - 1 : t, tp = t + 1 < T ? t + 1 : t;
+          const double yo = y[e], g0 = g[(size_t)t * D2 + dm], g1 = g[(size_t)tm * D2 + D + dm], g2 = g[(size_t)tp * D2 + D + dm];
+          const double yn = sc * (yo - mu) + mu;
+          y[e] = yn;
+          R[e] = (g0 + (t >= 1 ? 0.5 : 0.0) * g1) - (t + 1 < T ? 0.5 : 0.0) * g2;
+          const double dv = yn - mu;
+          s1 += dv;
+          s2 = fma(dv, dv, s2);
+        }
+      }
+      __syncthreads();
+      finish_moments(s1, s2);
+    }
+
+    // gather of one round into an LDS image of u: two unconditional loads per element on clamped addresses, eight
+    // elements in flight, 0 / 1 / +-1/2 weights applied on the way into LDS
+    auto gather = [&](int r, double *Ub0) {
+      const int tile0 = r * kGv2NB, total = 16 * kGv2NB * D2;
+      int sl = gsl0, k = gk0;
+      for (int e = gtid; e < total; e += kGv2GB * ngth) {
+        double ya[kGv2GB], yc[kGv2GB];
+        int tt[kGv2GB], oo[kGv2GB];
+#pragma unroll
+        for (int i = 0; i < kGv2GB; ++i) {
+          const bool in = e + i * ngth < total;
+          const int idx = tile0 * 16 + sl;
+          const int t = (in && idx < ntiles * 16) ? perm[idx] : -1;
+          tt[i] = (t < 0 ? -1 : t) | (k < D ? 0 : 1 << 30);         // frame and static / delta half
+          oo[i] = in ? ((sl >> 4) * 4 * KS + k) * 17 + (sl & 15) : -1;
+          const bool st = k < D;
+          const int tc = t >= 0 ? t : 0, kd = st ? k : k - D;
+          const int tp = tc + 1 < T ? tc + 1 : tc, tm = tc >= 1 ? tc - 1 : tc;
+          ya[i] = y[(size_t)(st ? tc : tp) * D + kd];
+          yc[i] = y[(size_t)(st ? tc : tm) * D + kd];
+          sl += dsl;
+          k += dk;
+          if (k >= D2) {
+            k -= D2;
+            ++sl;
+          }
+        }
+#pragma unroll
+        for (int i = 0; i < kGv2GB; ++i)
+          if (oo[i] >= 0) {
+            const bool ok = tt[i] >= 0, st = (tt[i] & (1 << 30)) == 0;
+            const int t = tt[i] & ~(1 << 30);
+            const double wa = !ok ? 0.0 : (st ? 1.0 : (t + 1 < T ? 0.5 : 0.0)), wc = (!ok || st) ? 0.0 : (t >= 1 ? -0.5 : 0.0);
+            Ub0[oo[i]] = wa * ya[i] + wc * yc[i];
+          }
+      }
+    };
+
+    double afr[kGvMaxKS];
+    int mcur = -1;
+    const int nrounds = (ntiles + kGv2NB - 1) / kGv2NB;
+    BLK_PROF_T0();
+    for (int ep = 0; ep < gv.epochs; ++ep) {
+      // gvgrad coefficients, src/trajectory_gmmmap.jl:171-189: -2/T (pv' (var(y) - mu^v)), times (y - mean) below
+      if (tid < D) {
+        double s = 0.0;
+        for (int j = 0; j < D; ++j) s = fma(gv.pv[j + (size_t)D * tid], var[j] - gv.muv[j], s);
+        coef[tid] = -2.0 / (double)T * s;
+      }
+      // v_t = Q_mhat_t u_t for every frame
+      if (gatherer) gather(0, Ut);
+      __syncthreads();
+      for (int r = 0; r < nrounds; ++r) {
+        if (gatherer) {
+          if (r + 1 < nrounds) gather(r + 1, Ut + (size_t)((r + 1) & 1) * UTR);
+        } else {
+          const double *Ub0 = Ut + (size_t)(r & 1) * UTR;
+          const int tile0 = r * kGv2NB, nb = (ntiles - tile0 < kGv2NB) ? ntiles - tile0 : kGv2NB;
+          for (int b = 0; b < nb; ++b) {
+            const int m = tilem[tile0 + b];
+            if (m != mcur) {                               // Q fragments of this wave's row tile, kept while tiles share m
+              mcur = m;
+              const double *A = Qfrag + (((size_t)m * NT + wave) * KS) * 64 + lane;
+#pragma unroll
+              for (int ks = 0; ks < kGvMaxKS; ++ks) afr[ks] = (ks < KS) ? A[(size_t)ks * 64] : 0.0;
+            }
+            const double *Ub = Ub0 + (size_t)b * UTS;
+            gv_d4 acc = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+            for (int ks = 0; ks < kGvMaxKS; ++ks)
+              if (ks < KS) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(afr[ks], Ub[(4 * ks + lgrp) * 17 + lcol], acc, 0, 0, 0);
+            const int t = perm[(tile0 + b) * 16 + lcol];
+#pragma unroll
+            for (int r4 = 0; r4 < 4; ++r4) {
+              const int row = 16 * wave + lgrp + 4 * r4;
+              if (row < D2 && t >= 0) V[(size_t)t * D2 + row] = acc[r4];
+            }
+          }
+        }
+        __syncthreads();
+      }
+      BLK_PROF(13);
+      // y <- y + alpha * ( omega (r - P y) + coef (y - mean) ), eq. (52), src/trajectory_gmmmap.jl:163-166
+      double s1 = 0.0, s2 = 0.0;
+      if (gm < NGm) {
+        const double mu = mean[dm], cf = coef[dm];
+#pragma unroll 4
+        for (int t = gm; t < T; t += NGm) {
+          const size_t e = (size_t)t * D + dm;
+          const int tm = t >= 1 ? t - 1 : t, tp = t + 1 < T ? t + 1 : t;
+          const double vs = V[(size_t)t * D2 + dm], vm = V[(size_t)tm * D2 + D + dm], vp = V[(size_t)tp * D2 + D + dm];
+          const double yy = y[e], rr = R[e];
+          const double py = (vs + (t >= 1 ? 0.5 : 0.0) * vm) - (t + 1 < T ? 0.5 : 0.0) * vp;
+          const double dy = omega * (rr - py) + cf * (yy - mu);
+          const double yn = fma(gv.alpha, dy, yy);
+          y[e] = yn;
+          const double dv = yn - mu;
+          s1 += dv;
+          s2 = fma(dv, dv, s2);
+        }
+      }
+      __syncthreads();
+      BLK_PROF(14);
+      finish_moments(s1, s2);
+      BLK_PROF(15);
+    }
+  }
+}
+
+// workspace: V (2D,T) + r (D,T) <= the panel area
+int traj_gv_launch(vcmi_traj *t, const TrajSolvePlan &p, const TrajGV &gv, hipStream_t st) {
+  const int D = t->D;
+  // two-team kernel when the frame permutation of the longest utterance fits in LDS beside the two images of u
+  const int pcap = ((p.Tmax + 15) / 16 + t->M) * 16;
+  const int nthr2 = kGv2Threads;
+  const size_t shmem2 = ((size_t)2 * kGv2NB * 4 * t->KS * 17 + 2 * nthr2 + 3 * (size_t)D) * sizeof(double) +
+                        (2 * (size_t)t->M + (size_t)pcap + (size_t)pcap / 16 + 2) * sizeof(int);
+  if (shmem2 <= 160 * 1024 - 256 && t->NT <= 6 && !debug_flag(kDbgGvOneTeam)) {
+    VCMI_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(traj_gv2_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                 (int)shmem2));
+    hipLaunchKernelGGL(traj_gv2_kernel, dim3(p.grid), dim3(nthr2), shmem2, st, p.du, p.n, D, t->M, t->KS, pcap, t->Qfrag.p, t->mhat.p,
+                       t->gbuf.p, t->ws.p, p.ws_stride, gv);
+  } else {
+    const int nthr = 64 * t->NT;
+    const size_t shmem = ((size_t)kGvNB * 4 * t->KS * 16 + 2 * nthr + 3 * (size_t)D) * sizeof(double) + 2 * (size_t)t->M * sizeof(int);
+    VCMI_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(traj_gv_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                 (int)shmem));
+    hipLaunchKernelGGL(traj_gv_kernel, dim3(p.grid), dim3(nthr), shmem, st, p.du, p.n, D, t->M, t->KS, t->Qfrag.p, t->mhat.p, t->gbuf.p,
+                       t->ws.p, p.ws_stride, gv);
+  }
+  VCMI_HIP(hipGetLastError());
+  return VCMI_OK;
+}
+
+#ifdef TRAJ_BLK_PROF
+void traj_gv_prof_dump(hipStream_t st) {
+  long long h[32];
+  blk_prof_fetch(h, st);
+  fprintf(stderr, "blk_prof cycles, gv kernel: product phase %lld, update %lld, moments %lld\n", h[13], h[14], h[15]);
+}
+#endif
+
+int trajgv_args(const vcmi_trajgv *h, int64_t n, const int64_t *T, int epochs, TrajGV *gv) {
+  if (!h) return fail(VCMI_ERR_ARG, "TrajectoryGVGMMMap: NULL handle");
+  if (epochs < 0) return fail(VCMI_ERR_ARG, "TrajectoryGVGMMMap: negative epoch count");
+  if (h->t->em_iters > 0)    // the GV ascent groups frames by mhat[t] <= M and reads Qfrag: no blended precisions
+    return fail(VCMI_ERR_ARG, "TrajectoryGVGMMMap: the trajectory converter has EM re-estimation switched on (vcmi_traj_set_em)");
+  for (int64_t u = 0; T && u < n; ++u)
+    if (T[u] == 1) return fail(VCMI_ERR_DIM, "TrajectoryGVGMMMap: the variance of a one-frame trajectory is undefined");
+  gv->muv = h->muv.p;
+  gv->pv = h->pv.p;
+  gv->epochs = epochs;
+  return VCMI_OK;
+}
+
+}  // namespace vcmi
+
+using namespace vcmi;
+
+// ---- TrajectoryGVGMMMap, src/trajectory_gmmmap.jl:114-189 ----------------------------------------
+extern "C" int vcmi_trajgv_create(vcmi_traj *t, const double *muv, const double *sigmavv, vcmi_trajgv **out) {
+  if (!t || !muv || !sigmavv || !out) return fail(VCMI_ERR_ARG, "vcmi_trajgv_create: NULL argument");
+  *out = nullptr;
+  const int D = t->D;
+  if (64 * t->NT > 384) return fail(VCMI_ERR_ARG, "TrajectoryGVGMMMap: feature dimension %d too large", t->D2);
+  for (int d = 0; d < D; ++d)
+    if (muv[d] < 0.0) return fail(VCMI_ERR_ARG, "TrajectoryGVGMMMap: the GV mean must be non-negative");   // the @assert of :124
+  std::vector<double> S((size_t)D * D), P((size_t)D * D);
+  for (int r = 0; r < D; ++r)
+    for (int c = 0; c < D; ++c) S[(size_t)r * D + c] = sigmavv[r + (size_t)D * c];
+  if (!la::inverse(S.data(), D, P.data())) return fail(VCMI_ERR_NOT_PD, "TrajectoryGVGMMMap: the GV covariance is singular");
+  std::vector<double> Pj((size_t)D * D);                       // back to the Julia memory image
+  for (int r = 0; r < D; ++r)
+    for (int c = 0; c < D; ++c) Pj[r + (size_t)D * c] = P[(size_t)r * D + c];
+  vcmi_trajgv *h = new (std::nothrow) vcmi_trajgv();
+  if (!h) return fail(VCMI_ERR_OOM, "out of host memory");
+  h->t = t;
+  int rc = VCMI_OK;
+  if ((rc = h->muv.alloc(D)) || (rc = h->pv.alloc((size_t)D * D))) {
+    delete h;
+    return rc;
+  }
+  hipError_t e = upload_now_hip(h->muv.p, muv, sizeof(double) * D);
+  if (e == hipSuccess) e = upload_now_hip(h->pv.p, Pj.data(), sizeof(double) * D * D);
+  if (e != hipSuccess) {
+    delete h;
+    return fail(VCMI_ERR_HIP, "TrajectoryGVGMMMap: upload failed: %s", hipGetErrorString(e));
+  }
+  h->h_muv.assign(muv, muv + D);
+  h->h_pv = Pj;
+  *out = h;
+  return VCMI_OK;
+}
+
+extern "C" int vcmi_trajgv_destroy(vcmi_trajgv *h) {
+  delete h;
+  return VCMI_OK;
+}

@@ -1,5 +1,5 @@
 // traj_solve_blk.hpp -- blocked banded Cholesky solve of the trajectory normal equations on v_mfma_f64_16x16x4.
-// Included by traj.hip inside namespace vcmi (needs TrajUtt and traj_rsqrt).
+// Included by traj_solve.hip inside namespace vcmi (needs TrajUtt and traj_rsqrt: traj_internal.hpp).
 //
 // Solves (W' Dy^-1 W) y = W' Dy^-1 E of reference src/trajectory_gmmmap.jl:103-105 for one utterance per workgroup.
 // The matrix P is block-pentadiagonal with D x D blocks (see the header of traj.hip).  Block step t works on the
@@ -39,25 +39,7 @@ struct BlkCfg {
 
 typedef double blk_d4 __attribute__((ext_vector_type(4)));
 
-#ifdef TRAJ_BLK_PROF
-__device__ long long blk_prof[32];   // cycles of workgroup 0 per phase (printed by traj_check_status)
-#define BLK_PROF_T0() long long pt_ = (long long)__builtin_readcyclecounter()
-#define BLK_PROF(k)                                                     \
-  do {                                                                  \
-    const long long n_ = (long long)__builtin_readcyclecounter();       \
-    if (blockIdx.x == 0 && threadIdx.x == 0) blk_prof[k] += n_ - pt_;   \
-    pt_ = n_;                                                           \
-  } while (0)
-// time since the last BLK_PROF mark, seen by thread `thr` (does not move the mark)
-#define BLK_PROF_AT(k, thr)                                                                                         \
-  do {                                                                                                              \
-    if (blockIdx.x == 0 && threadIdx.x == (thr)) blk_prof[k] += (long long)__builtin_readcyclecounter() - pt_;      \
-  } while (0)
-#else
-#define BLK_PROF_T0()
-#define BLK_PROF(k)
-#define BLK_PROF_AT(k, thr)
-#endif
+#include "traj_blk_prof.hpp"   // BLK_PROF marks: nothing unless TRAJ_BLK_PROF
 
 // blocks (a,a-2), (a,a-1), (a,a) of P and r_a (row D of the diagonal block) into three block buffers; every entry of the
 // DP x DP area is written (zeros outside D x D, outside the band and beyond the utterance) so recycled buffers are clean.
