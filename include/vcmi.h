@@ -121,6 +121,16 @@ int vcmi_vc_frames(vcmi_gmmmap *g, const double *fm, int64_t T, double *out);
  * family's converter input and result on this thread too: when the sum is above it, the call ends with a device-wide wait
  * (hipDeviceSynchronize) and frees all three, also after a small matrix. */
 int vcmi_vc_frames_postf(vcmi_gmmmap *g, const double *fm, int64_t T, const double *sigma2, double *out);
+/* vc over a batch of utterances, frame by frame: out[u] (D+1,T[u]) is what vcmi_vc_frames_postf(g, fm[u], T[u], sigma2, out[u])
+ * gives -- row 1 passed through bit for bit, the post-filter's mean and variance over utterance u's converted frames only --
+ * with ONE upload, ONE conversion over the packed (D+1, sum T) matrix, the per-utterance filter in place and one download (see
+ * vcmi_vc_traj_batch for the rule and the kernels).  fm, T, out: host arrays of n entries; sigma2 (D) may be NULL.  n = 0 is a
+ * no-op, T[u] = 0 is allowed (fm[u], out[u] are not read).  Refused before anything is uploaded or launched, every out[u]
+ * untouched: sigma2 with some T[u] = 1: VCMI_ERR_DIM; n < 0, T[u] < 0 or a NULL matrix with T[u] > 0: VCMI_ERR_ARG.  Runs on the
+ * calling thread's device.  Device scratch: 2 (D+1) sum T doubles in the per-thread staging matrix of vcmi_vc_frames_postf,
+ * under its 256 MiB release rule, and the work lists (4 n + sum T / 128 words). */
+int vcmi_vc_frames_batch(vcmi_gmmmap *g, int64_t n, const double *const *fm, const int64_t *T, const double *sigma2,
+                         double *const *out);
 /* predict_proba(g.px, X) -> P (M,T), src/gmm.jl:24-41 */
 int vcmi_gmmmap_posterior(vcmi_gmmmap *g, const double *X, int64_t ldx, int64_t T, double *P);
 int vcmi_gmmmap_posterior_dev(vcmi_gmmmap *g, const double *dX, int64_t ldx, int64_t T, double *dP, void *stream);
@@ -443,6 +453,45 @@ int vcmi_vc_trajgv(vcmi_trajgv *h, const double *fm, int64_t T, int is_static, i
                    const double *sigma2, double *out);
 int vcmi_vc_trajgv_dev(vcmi_trajgv *h, const double *dfm, int64_t ldf, int64_t T, int is_static, int epochs,
                        double alpha, const double *sigma2, double *dout, int64_t ldo, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * vc over a batch of utterances in one call (csrc/vc_batch.hip)
+ * ------------------------------------------------------------------------------------------- */
+/* THE RULE.  For utterances fm[0..n) of T[0..n) frames, out[u] is what vc(c_u, fm[u]) -- vcmi_vc_traj_static (is_static = 1,
+ * fm[u] (D+1,T[u])) or vcmi_vc_traj_postf (is_static = 0, fm[u] (2D+1,T[u])) -- returns for a FRESH converter c_u equal to t
+ * whose length is L = length(t) at entry:
+ *   - every utterance is cut into chunks [kL+1, min((k+1)L, T[u])] with the same L;
+ *   - static input gets its deltas over that utterance only, before chunking: only the utterance's own first and last frame
+ *     keep the copy of the static value (src/datasets.jl:6-13);
+ *   - the post-filter's mean and variance are taken over that utterance's converted frames only (src/gv.jl:10-15);
+ *   - the power row is passed through bit for bit;
+ *   - like the other batch entries, and unlike the single call, length(t) is left unchanged.
+ * The chunks of all utterances go through ONE trajectory solve (the launch of vcmi_traj_convert_batch_dev), the two ends run as
+ * segmented kernels over (utterance, tile) work lists made on the host; the filter's sums keep the order of the single call, so
+ * an utterance's result carries the bits the single call computes.  vcmi_traj_set_em is honoured per chunk.
+ * n = 0 is a no-op; T[u] = 0 is allowed and yields nothing for u.  Refused before anything is uploaded or launched, with every
+ * output untouched and length(t) as it was: sigma2 with some T[u] = 1: VCMI_ERR_DIM; a GV converter with a one-frame chunk
+ * (T[u] mod L = 1): VCMI_ERR_DIM; length(t) < 1, n < 0, T[u] < 0, a NULL matrix with T[u] > 0: VCMI_ERR_ARG; a GV converter
+ * over a handle with EM switched on: VCMI_ERR_ARG (as vcmi_vc_trajgv).
+ * The entries run on the calling thread's device (the device group of vcmi_set_devices is not used), in the per-thread
+ * scratch of the vcmi_vc_traj_static family under its rule (a host-pointer entry frees it on return above 256 MiB).  Footprint,
+ * N = sum T: converter input and result, 3 D N doubles; the host-pointer entries add the staging matrix with the inputs and
+ * the (D+1,N) results behind them -- (5D+2) N doubles in all for static input, (6D+2) N otherwise; the work lists (4 n + N / 128
+ * words, with a filter 2 D n + D N / 2048 doubles more); and the handle's per-frame workspace of vcmi_traj_convert_batch_dev
+ * over N frames.  A batch that does not fit is the caller's to slice. */
+int vcmi_vc_traj_batch(vcmi_traj *t, int64_t n, const double *const *fm, const int64_t *T, int is_static, const double *sigma2,
+                       double *const *out);
+/* ... each chunk through fvconvert(tgv, X; epochs, alpha), as vcmi_vc_trajgv */
+int vcmi_vc_trajgv_batch(vcmi_trajgv *h, int64_t n, const double *const *fm, const int64_t *T, int is_static, int epochs,
+                         double alpha, const double *sigma2, double *const *out);
+/* DEVICE-RESIDENT forms: utterance u lies dense ((D+1,T[u]) or (2D+1,T[u]), leading dimension = row count) at dfm + fm_off[u]
+ * and its (D+1,T[u]) result dense at dout + out_off[u]; the offsets (in doubles, signed) and lengths are HOST arrays, as in
+ * vcmi_traj_convert_batch_dev.  The input and output ranges must not overlap.  Asynchronous on `stream` up to the status read
+ * the trajectory entries already do (the work lists are uploaded synchronously before the first launch). */
+int vcmi_vc_traj_batch_dev(vcmi_traj *t, int64_t n, const double *dfm, const int64_t *fm_off, const int64_t *T, int is_static,
+                           const double *sigma2, double *dout, const int64_t *out_off, void *stream);
+int vcmi_vc_trajgv_batch_dev(vcmi_trajgv *h, int64_t n, const double *dfm, const int64_t *fm_off, const int64_t *T, int is_static,
+                             int epochs, double alpha, const double *sigma2, double *dout, const int64_t *out_off, void *stream);
 
 /* fvpostf(vs::VarianceScaling, src) -- src/gv.jl:10-21.  src, out (D,T), sigma2 (D); out may alias src.  D T doubles in the
  * same per-thread staging matrix, under the same rule (device-wide wait and release included). */

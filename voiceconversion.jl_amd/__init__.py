@@ -6,7 +6,7 @@ root-level shim `voiceconversion_jl_amd` (see voiceconversion_jl_amd.py)."""
 from ._lib import (DimensionMismatch, PosDefException, VCMIError, device_count, get_devices, is_pinned, pin,  # noqa: F401
                    set_device, set_devices, unpin)
 from .common import (AbstractConverter, FrameByFrameConverter, TrajectoryConverter, dim, fvconvert,  # noqa: F401
-                     ncomponents, size, vc)
+                     ncomponents, size, vc, vc_batch)
 from .gmm import GMM, predict, predict_proba  # noqa: F401
 from .gmmmap import GMMMap  # noqa: F401
 from .dtw import DTW, backward, fit_, fit_batch, set_template_, update_  # noqa: F401,E402

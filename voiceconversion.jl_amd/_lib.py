@@ -72,6 +72,7 @@ SIGNATURES = {
     "vcmi_gmmmap_convert_dev": (_int, [_vp, _vp, _i64, _i64, _vp, _i64, _vp]),
     "vcmi_vc_frames": (_int, [_vp, _dp, _i64, _dp]),
     "vcmi_vc_frames_postf": (_int, [_vp, _dp, _i64, _dp, _dp]),
+    "vcmi_vc_frames_batch": (_int, [_vp, _i64, _dpp, _ip, _dp, _dpp]),
     "vcmi_gmmmap_posterior": (_int, [_vp, _dp, _i64, _i64, _dp]),
     "vcmi_gmmmap_posterior_dev": (_int, [_vp, _vp, _i64, _i64, _vp, _vp]),
     "vcmi_gmmmap_predict": (_int, [_vp, _dp, _i64, _i64, _ip]),
@@ -136,6 +137,10 @@ SIGNATURES = {
     "vcmi_vc_traj_dev": (_int, [_vp, _vp, _i64, _i64, _int, _dp, _vp, _i64, _vp]),
     "vcmi_vc_trajgv": (_int, [_vp, _dp, _i64, _int, _int, C.c_double, _dp, _dp]),
     "vcmi_vc_trajgv_dev": (_int, [_vp, _vp, _i64, _i64, _int, _int, C.c_double, _dp, _vp, _i64, _vp]),
+    "vcmi_vc_traj_batch": (_int, [_vp, _i64, _dpp, _ip, _int, _dp, _dpp]),
+    "vcmi_vc_trajgv_batch": (_int, [_vp, _i64, _dpp, _ip, _int, _int, C.c_double, _dp, _dpp]),
+    "vcmi_vc_traj_batch_dev": (_int, [_vp, _i64, _vp, _ip, _ip, _int, _dp, _vp, _ip, _vp]),
+    "vcmi_vc_trajgv_batch_dev": (_int, [_vp, _i64, _vp, _ip, _ip, _int, _int, C.c_double, _dp, _vp, _ip, _vp]),
     "vcmi_trajgv_create": (_int, [_vp, _dp, _dp, C.POINTER(_vp)]),
     "vcmi_trajgv_destroy": (_int, [_vp]),
     "vcmi_trajgv_convert": (_int, [_vp, _dp, _i64, _int, C.c_double, _dp]),

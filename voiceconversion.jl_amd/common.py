@@ -32,6 +32,22 @@ def vc(c, fm, postfilter=None, delta=False):
     return c._vc(fm, postfilter)
 
 
+def vc_batch(c, fms, postfilter=None, delta=False, **kw):
+    """vc over a whole list of utterances in one call: vc_batch(c, fms, postfilter, delta, ...)[u] is what
+    vc(c_u, fms[u], postfilter, delta, ...) returns for a fresh converter c_u equal to `c` with len(c_u) = len(c) -- chunks of
+    len(c) frames per utterance, deltas (delta=True) and the post-filter's statistics over that utterance only, the power row
+    passed through -- with one upload, one trajectory solve over the chunks of all utterances and one download
+    (include/vcmi.h: vcmi_vc_traj_batch).  Unlike vc, the call leaves len(c) unchanged.
+    fms: a list of (rows, T_u) matrices, T_u = 0 allowed; the result is a list of Fortran (D+1, T_u) arrays.  A trajectory
+    converter also takes a list of device tensors (each with unit stride along its rows) and returns device tensors, views of
+    one buffer, on the current stream.  **kw: epochs / alpha of a TrajectoryGVGMMMap."""
+    if delta and isinstance(c, FrameByFrameConverter):
+        raise ValueError("delta=True: only a TrajectoryConverter takes delta features (bin/vc.jl:76)")
+    if isinstance(c, FrameByFrameConverter):
+        return c._vc_batch(fms, postfilter, **kw)
+    return c._vc_batch(fms, postfilter, delta, **kw)
+
+
 def fvconvert(c, x, **kw):
     """fvconvert(c, x): src/gmmmap.jl:101-118 (vector or, as a batch extension, (D,T) matrix) and
     src/trajectory_gmmmap.jl:65-110 ((2D,T) matrix)."""

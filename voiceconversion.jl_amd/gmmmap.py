@@ -117,3 +117,21 @@ class GMMMap(FrameByFrameConverter):
         out = np.empty_like(fm, order="F")
         _lib.check(_lib.lib.vcmi_vc_frames_postf(self._h, _lib.dptr(fm), fm.shape[1], s2, _lib.dptr(out)))   # NULL: vcmi_vc_frames
         return out
+
+    def _vc_batch(self, fms, postfilter=None):
+        """vc_batch for the frame-by-frame converter: one conversion over the packed matrix, the filter per utterance
+        (vcmi_vc_frames_batch)"""
+        fms = [jl_matrix(f, "fm") for f in fms]
+        n = len(fms)
+        if n == 0:
+            return []
+        for f in fms:
+            if f.shape[0] != self._D + 1:
+                raise _lib.DimensionMismatch("Inconsistent dimentions.")
+        s2 = sigma2_arg(postfilter, self._D)
+        T = np.array([f.shape[1] for f in fms], dtype=np.int64)
+        outs = [np.empty_like(f, order="F") for f in fms]
+        dpp = C.POINTER(C.c_double) * n
+        _lib.check(_lib.lib.vcmi_vc_frames_batch(self._h, n, dpp(*[_lib.dptr(f) for f in fms]), _lib.iptr(T), s2,
+                                                 dpp(*[_lib.dptr(o) for o in outs])))
+        return outs

@@ -610,6 +610,50 @@ function vc(tgv::TrajectoryGVGMMMap, fm::Matrix{Float64}, vs::Union{VarianceScal
     out
 end
 
+# ---- vc over a whole list of utterances in one call (include/vcmi.h: vcmi_vc_traj_batch) ----------------------------------
+# vc(c, fms, vs; ...)[u] is what vc(c_u, fms[u], vs; ...) returns for a fresh converter c_u equal to c with
+# length(c_u) = length(c): chunks, deltas and the post-filter's statistics per utterance, one upload, one solve over the chunks
+# of all utterances, one download.  Unlike the single call it leaves length(c) unchanged.
+function vc(g::GMMMap, fms::Vector{Matrix{Float64}}, vs::Union{VarianceScaling,Nothing}=nothing)
+    all(size(fm, 1) == dim(g) + 1 for fm in fms) || throw(DimensionMismatch("Inconsistent dimentions."))
+    σ² = σ²vector(vs, dim(g))
+    T = Int64[size(fm, 2) for fm in fms]
+    outs = [similar(fm) for fm in fms]
+    GC.@preserve fms outs σ² begin
+        check(ccall((:vcmi_vc_frames_batch, libvcmi), Cint,
+                    (Ptr{Cvoid}, Int64, Ptr{Ptr{Float64}}, Ptr{Int64}, Ptr{Float64}, Ptr{Ptr{Float64}}),
+                    g.h, length(fms), pointer.(fms), T, σ²pointer(vs, σ²), pointer.(outs)))
+    end
+    outs
+end
+function vc(t::TrajectoryGMMMap, fms::Vector{Matrix{Float64}}, vs::Union{VarianceScaling,Nothing}=nothing; delta::Bool=false)
+    D = dim(t) >> 1
+    all(size(fm, 1) == (delta ? D : 2D) + 1 for fm in fms) || throw(DimensionMismatch("Inconsistent dimentions."))
+    σ² = σ²vector(vs, D)
+    T = Int64[size(fm, 2) for fm in fms]
+    outs = [Matrix{Float64}(undef, D + 1, k) for k in T]
+    GC.@preserve fms outs σ² begin
+        check(ccall((:vcmi_vc_traj_batch, libvcmi), Cint,
+                    (Ptr{Cvoid}, Int64, Ptr{Ptr{Float64}}, Ptr{Int64}, Cint, Ptr{Float64}, Ptr{Ptr{Float64}}),
+                    t.h, length(fms), pointer.(fms), T, delta ? 1 : 0, σ²pointer(vs, σ²), pointer.(outs)))
+    end
+    outs
+end
+function vc(tgv::TrajectoryGVGMMMap, fms::Vector{Matrix{Float64}}, vs::Union{VarianceScaling,Nothing}=nothing;
+            delta::Bool=false, epochs::Int=100, α::Float64=1.0e-5)
+    D = dim(tgv) >> 1
+    all(size(fm, 1) == (delta ? D : 2D) + 1 for fm in fms) || throw(DimensionMismatch("Inconsistent dimentions."))
+    σ² = σ²vector(vs, D)
+    T = Int64[size(fm, 2) for fm in fms]
+    outs = [Matrix{Float64}(undef, D + 1, k) for k in T]
+    GC.@preserve fms outs σ² begin
+        check(ccall((:vcmi_vc_trajgv_batch, libvcmi), Cint,
+                    (Ptr{Cvoid}, Int64, Ptr{Ptr{Float64}}, Ptr{Int64}, Cint, Cint, Cdouble, Ptr{Float64}, Ptr{Ptr{Float64}}),
+                    tgv.h, length(fms), pointer.(fms), T, delta ? 1 : 0, epochs, α, σ²pointer(vs, σ²), pointer.(outs)))
+    end
+    outs
+end
+
 # A Float64 matrix that lives in HBM: device address, shape and leading dimension (what a GPU array package, or the
 # library's own `_dev` entry points, hand around).  push_delta and fvpostf! on it run where the data is, on `stream`.
 struct DeviceMatrix

@@ -77,6 +77,53 @@ def _vc_dev(c, fm, postfilter, delta, call):
     return buf.t()
 
 
+def _vc_batch(c, fms, postfilter, delta, host_call, dev_call):
+    """vc_batch of a trajectory converter.  host_call(n, fm**, T*, is_static, sigma2, out**) and
+    dev_call(n, dfm, fm_off*, T*, is_static, sigma2, dout, out_off*, stream) are the converter's two batch entries.  Device
+    tensors are addressed where they are, by their offsets from the first one (a tensor that is not dense is copied); the
+    results are views of one new (sum T, D+1) buffer."""
+    fms = list(fms)
+    n = len(fms)
+    if n == 0:
+        return []
+    D = c._dim() // 2
+    rows = (D if delta else 2 * D) + 1
+    on_dev = [is_torch(f) and f.is_cuda for f in fms]
+    if any(on_dev) and not all(on_dev):
+        raise TypeError("vc_batch: device tensors and host matrices in one list")
+    if not on_dev[0]:
+        fms = [jl_matrix(f, "fm") for f in fms]
+    for f in fms:
+        if f.shape[0] != rows:
+            raise _lib.DimensionMismatch("Inconsistent dimentions.")
+    s2 = sigma2_arg(postfilter, D)
+    T = np.array([f.shape[1] for f in fms], dtype=np.int64)
+    if not on_dev[0]:
+        outs = [np.empty((D + 1, int(t)), order="F") for t in T]
+        dpp = C.POINTER(C.c_double) * n
+        _lib.check(host_call(n, dpp(*[_lib.dptr(f) for f in fms]), _lib.iptr(T), int(bool(delta)), s2,
+                             dpp(*[_lib.dptr(o) for o in outs])))
+        return outs
+    import torch
+
+    dense = []                                   # (kept alive until the call returns: it ends with a status read)
+    for f in fms:
+        if f.shape[1] > 0:                       # (an empty tensor has no strides to speak of, and is never read)
+            _, _, t, ld = dev_matrix(f, "fm")
+            if t > 1 and ld != rows:
+                f = f.t().contiguous().t()
+        dense.append(f)
+    ptrs = [f.data_ptr() for f in dense]
+    base = next((p for p, t in zip(ptrs, T) if t > 0), 0)
+    fm_off = np.array([(p - base) // 8 if t > 0 else 0 for p, t in zip(ptrs, T)], dtype=np.int64)
+    first = np.concatenate([[0], np.cumsum(T)])
+    buf = torch.empty((int(first[-1]), D + 1), dtype=torch.float64, device=fms[0].device)
+    out_off = np.ascontiguousarray(first[:-1] * (D + 1), dtype=np.int64)
+    _lib.check(dev_call(n, base, _lib.iptr(fm_off), _lib.iptr(T), int(bool(delta)), s2, buf.data_ptr(), _lib.iptr(out_off),
+                        current_stream_ptr()))
+    return [buf[int(first[u]):int(first[u + 1])].t() for u in range(n)]
+
+
 class TrajectoryGMMMap(TrajectoryConverter):
     """TrajectoryGMMMap(g::GMMMap, T) -- src/trajectory_gmmmap.jl:3-37.  `g` is a GMMMap over static+delta
     features (dim(g) = 2D).  The constructor precomputes Dy_m = inv(Sigma^yy_m - A_m Sigma^xy_m) (:24-28)."""
@@ -189,6 +236,16 @@ class TrajectoryGMMMap(TrajectoryConverter):
         _lib.check(entry(self._h, _lib.dptr(fm), fm.shape[1], s2, _lib.dptr(out)))
         return out
 
+    def _vc_batch(self, fms, postfilter=None, delta=False):
+        """vc_batch (common.py): vcmi_vc_traj_batch on host matrices, vcmi_vc_traj_batch_dev on device tensors"""
+        def host(*args):
+            return _lib.lib.vcmi_vc_traj_batch(self._h, *args)
+
+        def dev(*args):
+            return _lib.lib.vcmi_vc_traj_batch_dev(self._h, *args)
+
+        return _vc_batch(self, fms, postfilter, delta, host, dev)
+
 
 class TrajectoryGVGMMMap(TrajectoryConverter):
     """TrajectoryGVGMMMap(tgmm, mu^v, Sigma^vv) -- src/trajectory_gmmmap.jl:114-137: trajectory conversion followed
@@ -268,3 +325,14 @@ class TrajectoryGVGMMMap(TrajectoryConverter):
             out[1:, k * L:k * L + y.shape[1]] = y
         out[0, :] = fm[0, :]
         return out
+
+    def _vc_batch(self, fms, postfilter=None, delta=False, epochs=100, alpha=1.0e-5):
+        """vc_batch (common.py): every chunk of every utterance through fvconvert(tgv, X; epochs, alpha)"""
+        def host(n, fm, T, is_static, s2, out):
+            return _lib.lib.vcmi_vc_trajgv_batch(self._h, n, fm, T, is_static, int(epochs), float(alpha), s2, out)
+
+        def dev(n, dfm, fm_off, T, is_static, s2, dout, out_off, stream):
+            return _lib.lib.vcmi_vc_trajgv_batch_dev(self._h, n, dfm, fm_off, T, is_static, int(epochs), float(alpha), s2, dout,
+                                                     out_off, stream)
+
+        return _vc_batch(self, fms, postfilter, delta, host, dev)
