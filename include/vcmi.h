@@ -433,7 +433,16 @@ int vcmi_vc_traj_dev(vcmi_traj *t, const double *dfm, int64_t ldf, int64_t T, in
  * ------------------------------------------------------------------------------------------- */
 typedef struct vcmi_trajgv vcmi_trajgv;
 /* TrajectoryGVGMMMap(tgmm, mu^v (D), Sigma^vv (D,D)) :118-129; keeps (does not own) the trajectory handle.
- * VCMI_ERR_ARG if a GV mean is negative (the @assert of :124), VCMI_ERR_NOT_PD if Sigma^vv is singular. */
+ * VCMI_ERR_ARG if a GV mean is negative (the @assert of :124), VCMI_ERR_NOT_PD if Sigma^vv is singular.
+ * Every static dimension vcmi_traj_create accepts converts with GV.  2D <= 96: one wave per 16-row tile of Q_m with the tile's
+ * k-steps in registers (traj_gv2_kernel; traj_gv_kernel where the frame permutation of the longest utterance does not fit LDS).
+ * 2D > 96: traj_gvw_kernel -- several row tiles per wave, the k range in chunks of at most 16 k-steps through a 34 KB LDS image
+ * whatever D is, Q_m read from the fragment image that vcmi_traj_create uploads for every dimension (no new buffer on the
+ * handle); utterances whose (ceil(T/16) + M) 16 permutation slots exceed 1024 keep the permutation in the workspace.  Scratch of
+ * the ascent, on the trajectory handle: per workgroup (one per utterance, at most one per compute unit) 3 D Tmax doubles (Q u and
+ * r) and 8.5 Tmax + 16 more for the permutation, inside the workspace of the solve ((3D+1) D Tmax doubles per workgroup), which
+ * is the larger of the two for every D >= 3.  D > 512 returns VCMI_ERR_ARG from the convert entries (the arg-max of the
+ * trajectory converter ends at 2D = 320). */
 int vcmi_trajgv_create(vcmi_traj *t, const double *muv, const double *sigmavv, vcmi_trajgv **out);
 int vcmi_trajgv_destroy(vcmi_trajgv *h);
 /* fvconvert(tgv, X; epochs=100, alpha=1.0e-5) :139-168: trajectory solve, eq.(58) rescaling, then `epochs` steps of

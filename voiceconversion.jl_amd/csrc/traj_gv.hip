@@ -1,6 +1,6 @@
-// traj_gv.hip -- TrajectoryGVGMMMap (reference src/trajectory_gmmmap.jl:114-189): the handle, the two kernels of the
-// global-variance ascent on solved trajectories, and the host function that chooses between them (traj_internal.hpp:
-// traj_gv_launch).
+// traj_gv.hip -- TrajectoryGVGMMMap (reference src/trajectory_gmmmap.jl:114-189): the handle, the three kernels of the
+// global-variance ascent on solved trajectories (two for 2D <= 96, traj_gvw_kernel above that), and the host function that
+// chooses between them (traj_internal.hpp: traj_gv_launch).
 #include "traj_internal.hpp"
 #include "traj_blk_prof.hpp"
 #include "host_linalg.hpp"
@@ -481,9 +481,308 @@ traj_gv2_kernel(const TrajUtt *__restrict__ utts, int n, int D, int M, int KS, i
   }
 }
 
+// ------------------------------------------------------------------------------------------------
+// traj_gvw_kernel: the same ascent for feature vectors with more than six row tiles (2D > 96), where neither "one wave per
+// row tile" nor "all k-steps of a tile in registers" holds.  Six MFMA waves and two gather waves; the streaming passes
+// (moments, eq. (58), r, update) are those of traj_gv2_kernel on the (dimension, frame group) mapping, so D <= kGvwThreads.
+//   product of a round (kGvwNB single-mixture tiles of 16 frames): work item = (row tile i, frame tile b), item i * kGvwNB + b;
+//     the items are dealt to the MFMA waves in contiguous runs (a run mostly stays on one row tile, so its Q fragments are
+//     loaded once for the frame tiles of the run), each item's 16 x 16 accumulator stays in registers over the whole k range:
+//     at most kGvwItems per wave and pass, i.e. kGvwRowsPass row tiles per pass; wider models (2D > 192) take several passes
+//     over the rows and gather u once per pass;
+//   k range in chunks of kGvwKC k-steps: the LDS image of u holds ONE chunk of the round's tiles ([kGvwNB][4 kGvwKC][17]
+//     doubles, 34 KB, two of them) whatever D is; the gather waves fill the image of step s + 1 while the MFMA waves multiply
+//     step s, one barrier per step; the Q fragments of a chunk (kGvwKC registers) come from the handle's Qfrag image
+//     ([M][NT][KS][64], built for every dimension by traj_prepare_model): one coalesced 512-byte load per k-step;
+//   the frame permutation lives in LDS up to kGvwPermLds slots and in the workspace behind V and r beyond: LDS use depends on
+//     neither D (beyond the 3 D moments) nor T.  The frames and the mixture of a round's tiles are left in LDS by the gather
+//     of the round's first step (rt / rm), so the MFMA waves never read the permutation.
+// The wide path always works in the static dimension D itself (no Dpad: the padded blocked solver ends at D = 46).
+// ------------------------------------------------------------------------------------------------
+static constexpr int kGvwNB = 4;          // 16-frame tiles per round
+static constexpr int kGvwKC = 16;         // k-steps per chunk of the u image (64 columns)
+static constexpr int kGvwThreads = 512;   // 8 waves, two per SIMD: 256 VGPRs
+static constexpr int kGvwMfmaWaves = 6;
+static constexpr int kGvwItems = 8;       // (row tile, frame tile) accumulators of an MFMA wave: 64 VGPRs
+static constexpr int kGvwRowsPass = kGvwItems * kGvwMfmaWaves / kGvwNB;   // 12 row tiles per pass over the rows
+static constexpr int kGvwGth = kGvwThreads - 64 * kGvwMfmaWaves;          // 256 gather threads
+static constexpr int kGvwGB = kGvwNB * 16 * 4 * kGvwKC / kGvwGth;         // 32 elements of u per gather thread and step ...
+static constexpr int kGvwGF = 16;                                         // ... 16 of them in flight
+static constexpr int kGvwPermLds = 1024;  // slots of the frame permutation kept in LDS (4 KB: utterances of about 1000 frames)
+static_assert(kGvwGth % 64 == 0 && kGvwGB * kGvwGth == kGvwNB * 16 * 4 * kGvwKC && 4 * kGvwKC == 64 && kGvwGB % kGvwGF == 0,
+              "gather mapping of traj_gvw_kernel");
+
+__global__ void __launch_bounds__(kGvwThreads)
+traj_gvw_kernel(const TrajUtt *__restrict__ utts, int n, int D, int M, int NT, int KS, int perm_lds, const double *__restrict__ Qfrag,
+                const int64_t *__restrict__ mhat_all, const double *__restrict__ g_all, double *__restrict__ ws_all,
+                int64_t ws_stride, TrajGV gv) {
+  extern __shared__ double gsm[];
+  const int D2 = 2 * D, nthr = blockDim.x;
+  constexpr int UTS = 4 * kGvwKC * 17, UTR = kGvwNB * UTS;
+  double *Ut = gsm;                        // [2][kGvwNB][4*kGvwKC][17]  one k chunk of u of the tiles' frames, k-major, row stride 17
+  double *red = Ut + 2 * (size_t)UTR;      // [2][nthr]
+  double *mean = red + 2 * nthr;           // [D]
+  double *var = mean + D;                  // [D]
+  double *coef = var + D;                  // [D]
+  int *cnt = reinterpret_cast<int *>(coef + D);   // [M] frames per mixture, then the fill cursor
+  int *start = cnt + M;                           // [M] first slot of the mixture's (16-padded) segment
+  int *perm_s = start + M;                        // [perm_lds] the frame permutation, when it fits
+  __shared__ int ntiles_s;
+  __shared__ int rt[2][16 * kGvwNB];       // frames of the round's tile slots (-1: padding), by round parity
+  __shared__ int rm[2][kGvwNB];            // mixture of the round's tiles (-1: no such tile)
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int lcol = lane & 15, lgrp = lane >> 4;
+  const bool gatherer = wave >= kGvwMfmaWaves;
+  const int gtid = tid - 64 * kGvwMfmaWaves;
+  const int NC = (KS + kGvwKC - 1) / kGvwKC;                   // k chunks ...
+  const int KCe = (KS + NC - 1) / NC;                          // ... of KCe <= kGvwKC k-steps each (even shares: 25 -> 13 + 12)
+  const int NP = (NT + kGvwRowsPass - 1) / kGvwRowsPass;       // passes over the row tiles ...
+  const int RP = (NT + NP - 1) / NP;                           // ... of RP row tiles each (even shares: 13 -> 7 + 6)
+  const int SPR = NP * NC;                                     // steps per round
+
+  for (int u = blockIdx.x; u < n; u += gridDim.x) {
+    const TrajUtt U = utts[u];
+    const int T = U.T;
+    if (T < 2) continue;                   // var() of one frame is undefined; the host rejects such calls
+    const int64_t *mh = mhat_all + U.frame0;
+    const double *g = g_all + U.frame0 * D2;
+    gdouble *y = (gdouble *)U.Y;
+    double *V = ws_all + (size_t)blockIdx.x * ws_stride;   // [T][2D]
+    double *R = V + (size_t)T * D2;                        // [T][D]   r = W' D^-1 E
+    // frames grouped by mixture, segments padded to 16 with -1: at most T + 15 min(M, T) slots
+    int *perm = perm_lds > 0 ? perm_s : reinterpret_cast<int *>(R + (size_t)T * D);
+    const double omega = 1.0 / (2.0 * (double)T);
+
+    // frames grouped by mixture (see traj_gv_kernel)
+    for (int m = tid; m < M; m += nthr) cnt[m] = 0;
+    __syncthreads();
+    for (int t = tid; t < T; t += nthr) atomicAdd(&cnt[(int)mh[t] - 1], 1);
+    __syncthreads();
+    if (tid == 0) {
+      int pos = 0;
+      for (int m = 0; m < M; ++m) {
+        start[m] = pos;
+        pos += (cnt[m] + 15) / 16 * 16;
+        cnt[m] = 0;
+      }
+      ntiles_s = pos / 16;
+    }
+    __syncthreads();
+    const int ntiles = ntiles_s;
+    for (int e = tid; e < ntiles * 16; e += nthr) perm[e] = -1;
+    __syncthreads();
+    for (int t = tid; t < T; t += nthr) {
+      const int m = (int)mh[t] - 1;
+      perm[start[m] + atomicAdd(&cnt[m], 1)] = t;
+    }
+    __syncthreads();
+
+    // eq. (58) and r; every pass that writes y accumulates the moments of what it writes (see traj_gv_kernel)
+    gv_moments(y, D, T, nthr, red, mean, var);
+    const int NGm = nthr / D, dm = tid % D, gm = tid / D;
+    auto finish_moments = [&](double s1, double s2) {
+      if (gm < NGm) {
+        red[gm * D + dm] = s1;
+        red[nthr + gm * D + dm] = s2;
+      }
+      __syncthreads();
+      if (tid < D) {
+        double a1 = 0.0, a2 = 0.0;
+        for (int k = 0; k < NGm; ++k) {
+          a1 += red[k * D + tid];
+          a2 += red[nthr + k * D + tid];
+        }
+        mean[tid] += a1 / (double)T;
+        var[tid] = (a2 - a1 * a1 / (double)T) / (double)(T - 1);       // Julia's var: corrected
+      }
+      __syncthreads();
+    };
+    {
+      double s1 = 0.0, s2 = 0.0;
+      if (gm < NGm) {
+        const double mu = mean[dm], sc = sqrt(gv.muv[dm] / var[dm]);
+#pragma unroll 4
+        for (int t = gm; t < T; t += NGm) {
+          const size_t e = (size_t)t * D + dm;
+          const int tm = t >= 1 ? t - 1 : t, tp = t + 1 < T ? t + 1 : t;
+          const double yo = y[e], g0 = g[(size_t)t * D2 + dm], g1 = g[(size_t)tm * D2 + D + dm], g2 = g[(size_t)tp * D2 + D + dm];
+          const double yn = sc * (yo - mu) + mu;
+          y[e] = yn;
+          R[e] = (g0 + (t >= 1 ? 0.5 : 0.0) * g1) - (t + 1 < T ? 0.5 : 0.0) * g2;
+          const double dv = yn - mu;
+          s1 += dv;
+          s2 = fma(dv, dv, s2);
+        }
+      }
+      __syncthreads();
+      finish_moments(s1, s2);
+    }
+
+    // gather of step (round r, k chunk c) into an LDS image of u: thread -> one column k of the chunk and every second slot of
+    // the round's 64 (k fastest across the threads: the reads of y run along its rows); two unconditional loads per element
+    // on clamped addresses, sixteen elements in flight, 0 / 1 / +-1/2 weights applied on the way into LDS.  Every element of the image is
+    // written (zero for padding slots, for k >= 2D and for the columns behind the chunk's KCe k-steps).  first: also leave the slots' frames and the tiles' mixtures in rt / rm.
+    auto gather = [&](int r, int c, bool first, double *Ub0) {
+      const int kk = gtid & 63, k = 4 * KCe * c + kk, sl0 = gtid >> 6;
+      const bool st = k < D, kin = k < D2 && kk < 4 * KCe;
+      const int kd = st ? k : (kin ? k - D : 0);
+      constexpr int SLW = kGvwGth / 64;      // slots between two elements of a thread
+      for (int i0 = 0; i0 < kGvwGB; i0 += kGvwGF) {
+        double ya[kGvwGF], yc[kGvwGF];
+        int tt[kGvwGF];
+#pragma unroll
+        for (int i = 0; i < kGvwGF; ++i) {
+          const int sl = sl0 + SLW * (i0 + i), idx = r * (16 * kGvwNB) + sl;
+          const int t = idx < ntiles * 16 ? perm[idx] : -1;
+          tt[i] = t;
+          const int tc = t >= 0 ? t : 0;
+          const int tp = tc + 1 < T ? tc + 1 : tc, tm = tc >= 1 ? tc - 1 : tc;
+          ya[i] = y[(size_t)(st ? tc : tp) * D + kd];
+          yc[i] = y[(size_t)(st ? tc : tm) * D + kd];
+        }
+#pragma unroll
+        for (int i = 0; i < kGvwGF; ++i) {
+          const int sl = sl0 + SLW * (i0 + i), t = tt[i];
+          const bool ok = t >= 0 && kin;
+          const double wa = !ok ? 0.0 : (st ? 1.0 : (t + 1 < T ? 0.5 : 0.0)), wc = (!ok || st) ? 0.0 : (t >= 1 ? -0.5 : 0.0);
+          Ub0[((sl >> 4) * 4 * kGvwKC + kk) * 17 + (sl & 15)] = wa * ya[i] + wc * yc[i];
+          if (first && kk == 0) {
+            rt[r & 1][sl] = t;
+            if ((sl & 15) == 0) rm[r & 1][sl >> 4] = t >= 0 ? (int)mh[t] - 1 : -1;     // (slot 0 of a tile is never padding)
+          }
+        }
+      }
+    };
+
+    const int nrounds = (ntiles + kGvwNB - 1) / kGvwNB;
+    const int nsteps = nrounds * SPR;
+    for (int ep = 0; ep < gv.epochs; ++ep) {
+      // gvgrad coefficients, src/trajectory_gmmmap.jl:171-189: -2/T (pv' (var(y) - mu^v)), times (y - mean) below
+      if (tid < D) {
+        double s = 0.0;
+        for (int j = 0; j < D; ++j) s = fma(gv.pv[j + (size_t)D * tid], var[j] - gv.muv[j], s);
+        coef[tid] = -2.0 / (double)T * s;
+      }
+      // v_t = Q_mhat_t u_t for every frame.  The two teams run loops of their own (the accumulators are live in the MFMA
+      // waves' loop only) and meet at one barrier per step: both loops execute exactly nsteps of them.
+      if (gatherer) {
+        gather(0, 0, true, Ut);
+        __syncthreads();
+        for (int s = 0; s < nsteps; ++s) {
+          if (s + 1 < nsteps) {
+            const int r1 = (s + 1) / SPR, sr1 = s + 1 - r1 * SPR;
+            gather(r1, sr1 % NC, sr1 == 0, Ut + (size_t)((s + 1) & 1) * UTR);
+          }
+          __syncthreads();
+        }
+      } else {
+        __syncthreads();
+        gv_d4 acc[kGvwItems];
+        for (int s = 0; s < nsteps; ++s) {
+          const int r = s / SPR, sr = s - r * SPR, pass = sr / NC, c = sr - pass * NC;
+          const double *Ub0 = Ut + (size_t)(s & 1) * UTR;
+          const int i0 = pass * RP;
+          const int nitems = (NT - i0 < RP ? NT - i0 : RP) * kGvwNB;
+          const int per = (nitems + kGvwMfmaWaves - 1) / kGvwMfmaWaves, q0 = wave * per;
+          double afr[kGvwKC];
+          int icur = -1, mcur = -1;        // (the fragments in afr belong to this chunk: nothing is kept across steps)
+#pragma unroll
+          for (int j = 0; j < kGvwItems; ++j) {
+            const int q = q0 + j;
+            if (c == 0) acc[j] = gv_d4{0.0, 0.0, 0.0, 0.0};
+            const int i = i0 + q / kGvwNB, b = q % kGvwNB;
+            const int m = (j < per && q < nitems) ? rm[r & 1][b] : -1;
+            if (m >= 0) {
+              if (i != icur || m != mcur) {                    // Q fragments of (mixture, row tile, this chunk)
+                icur = i;
+                mcur = m;
+                // every load unconditional, on a clamped k-step (a branch per load would serialise them); what lies beyond the
+                // chunk is not multiplied, and the k-steps a last chunk repeats meet the zero rows k >= 2D of u
+                const double *A = Qfrag + (((size_t)m * NT + i) * KS) * 64 + lane;
+#pragma unroll
+                for (int ks = 0; ks < kGvwKC; ++ks) {
+                  const int kg = KCe * c + ks;
+                  afr[ks] = A[(size_t)(kg < KS ? kg : KS - 1) * 64];
+                }
+              }
+              const double *Ub = Ub0 + (size_t)b * UTS;
+              gv_d4 a = acc[j];
+#pragma unroll
+              for (int k0 = 0; k0 < kGvwKC; k0 += 8) {         // eight operands of u in flight
+                double bfr[8];
+#pragma unroll
+                for (int ks = 0; ks < 8; ++ks) bfr[ks] = Ub[(4 * (k0 + ks) + lgrp) * 17 + lcol];
+#pragma unroll
+                for (int ks = 0; ks < 8; ++ks)
+                  if (k0 + ks < KCe) a = __builtin_amdgcn_mfma_f64_16x16x4f64(afr[k0 + ks], bfr[ks], a, 0, 0, 0);
+              }
+              acc[j] = a;
+              if (c == NC - 1) {
+                const int t = rt[r & 1][b * 16 + lcol];
+#pragma unroll
+                for (int r4 = 0; r4 < 4; ++r4) {
+                  const int row = 16 * i + lgrp + 4 * r4;
+                  if (row < D2 && t >= 0) V[(size_t)t * D2 + row] = a[r4];
+                }
+              }
+            }
+          }
+          __syncthreads();
+        }
+      }
+      // y <- y + alpha * ( omega (r - P y) + coef (y - mean) ), eq. (52), src/trajectory_gmmmap.jl:163-166
+      double s1 = 0.0, s2 = 0.0;
+      if (gm < NGm) {
+        const double mu = mean[dm], cf = coef[dm];
+#pragma unroll 4
+        for (int t = gm; t < T; t += NGm) {
+          const size_t e = (size_t)t * D + dm;
+          const int tm = t >= 1 ? t - 1 : t, tp = t + 1 < T ? t + 1 : t;
+          const double vs = V[(size_t)t * D2 + dm], vm = V[(size_t)tm * D2 + D + dm], vp = V[(size_t)tp * D2 + D + dm];
+          const double yy = y[e], rr = R[e];
+          const double py = (vs + (t >= 1 ? 0.5 : 0.0) * vm) - (t + 1 < T ? 0.5 : 0.0) * vp;
+          const double dy = omega * (rr - py) + cf * (yy - mu);
+          const double yn = fma(gv.alpha, dy, yy);
+          y[e] = yn;
+          const double dv = yn - mu;
+          s1 += dv;
+          s2 = fma(dv, dv, s2);
+        }
+      }
+      __syncthreads();
+      finish_moments(s1, s2);
+    }
+  }
+}
+
+// LDS of traj_gvw_kernel: two images of one k chunk, the reduction rows, the 3 D moments, the per-mixture counters and, when it
+// fits, the permutation
+static size_t gvw_lds_bytes(int D, int M, int perm_lds) {
+  return ((size_t)2 * kGvwNB * 4 * kGvwKC * 17 + 2 * kGvwThreads + 3 * (size_t)D) * sizeof(double) + (2 * (size_t)M + (size_t)perm_lds) * sizeof(int);
+}
+
+static int traj_gvw_launch(vcmi_traj *t, const TrajSolvePlan &p, const TrajGV &gv, hipStream_t st) {
+  const int D = t->D;
+  if (D > kGvwThreads) return fail(VCMI_ERR_ARG, "TrajectoryGVGMMMap: static dimension %d beyond %d", D, kGvwThreads);
+  // the workspace of a workgroup: V (2D,T) + r (D,T) and, behind them, room for the permutation (at most 16 T ints) -- the
+  // plan of a call with GV reserves it (traj_solve_plan); checked here because this kernel writes all three
+  const int64_t need = (int64_t)p.Tmax * 3 * D + (17 * (int64_t)p.Tmax + 1) / 2 + 16;
+  if (p.ws_stride < need) return fail(VCMI_ERR_ARG, "TrajectoryGVGMMMap: workspace stride %lld below %lld", (long long)p.ws_stride, (long long)need);
+  const int pcap = ((p.Tmax + 15) / 16 + t->M) * 16;       // slots the longest utterance can need
+  const int perm_lds = pcap <= kGvwPermLds ? pcap : 0;
+  const size_t shmem = gvw_lds_bytes(D, t->M, perm_lds);
+  if (shmem > 160 * 1024 - 256) return fail(VCMI_ERR_ARG, "TrajectoryGVGMMMap: %d mixtures at dimension %d do not fit LDS", t->M, t->D2);
+  VCMI_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(traj_gvw_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
+  hipLaunchKernelGGL(traj_gvw_kernel, dim3(p.grid), dim3(kGvwThreads), shmem, st, p.du, p.n, D, t->M, t->NT, t->KS, perm_lds, t->Qfrag.p,
+                     t->mhat.p, t->gbuf.p, t->ws.p, p.ws_stride, gv);
+  VCMI_HIP(hipGetLastError());
+  return VCMI_OK;
+}
+
 // workspace: V (2D,T) + r (D,T) <= the panel area
 int traj_gv_launch(vcmi_traj *t, const TrajSolvePlan &p, const TrajGV &gv, hipStream_t st) {
   const int D = t->D;
+  if (t->NT > 6) return traj_gvw_launch(t, p, gv, st);      // 2D > 96: several row tiles per wave, k range in chunks
   // two-team kernel when the frame permutation of the longest utterance fits in LDS beside the two images of u
   const int pcap = ((p.Tmax + 15) / 16 + t->M) * 16;
   const int nthr2 = kGv2Threads;
@@ -517,6 +816,8 @@ void traj_gv_prof_dump(hipStream_t st) {
 int trajgv_args(const vcmi_trajgv *h, int64_t n, const int64_t *T, int epochs, TrajGV *gv) {
   if (!h) return fail(VCMI_ERR_ARG, "TrajectoryGVGMMMap: NULL handle");
   if (epochs < 0) return fail(VCMI_ERR_ARG, "TrajectoryGVGMMMap: negative epoch count");
+  if (h->t->D > kGvwThreads)    // (the arg-max of the trajectory converter itself ends at 2D = 320)
+    return fail(VCMI_ERR_ARG, "TrajectoryGVGMMMap: static dimension %d beyond %d", h->t->D, kGvwThreads);
   if (h->t->em_iters > 0)    // the GV ascent groups frames by mhat[t] <= M and reads Qfrag: no blended precisions
     return fail(VCMI_ERR_ARG, "TrajectoryGVGMMMap: the trajectory converter has EM re-estimation switched on (vcmi_traj_set_em)");
   for (int64_t u = 0; T && u < n; ++u)
@@ -536,7 +837,6 @@ extern "C" int vcmi_trajgv_create(vcmi_traj *t, const double *muv, const double 
   if (!t || !muv || !sigmavv || !out) return fail(VCMI_ERR_ARG, "vcmi_trajgv_create: NULL argument");
   *out = nullptr;
   const int D = t->D;
-  if (64 * t->NT > 384) return fail(VCMI_ERR_ARG, "TrajectoryGVGMMMap: feature dimension %d too large", t->D2);
   for (int d = 0; d < D; ++d)
     if (muv[d] < 0.0) return fail(VCMI_ERR_ARG, "TrajectoryGVGMMMap: the GV mean must be non-negative");   // the @assert of :124
   std::vector<double> S((size_t)D * D), P((size_t)D * D);

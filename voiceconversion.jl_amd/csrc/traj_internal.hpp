@@ -124,8 +124,8 @@ int traj_solve_launch(vcmi_traj *t, const TrajSolvePlan &plan, const double *Qs,
 
 // ---- traj_gv.hip ----
 // The GV ascent on the solved trajectories of the plan's utterances, in place (two-team kernel where the frame permutation of
-// the longest fits LDS, else the one-team kernel).  Reads t->mhat, t->gbuf, t->Qfrag; workspace: t->ws with plan.ws_stride (a
-// plan made with_gv).  Asynchronous on st, behind the solve.
+// the longest fits LDS, else the one-team kernel; traj_gvw_kernel for more than six row tiles, 2D > 96).  Reads t->mhat, t->gbuf,
+// t->Qfrag; workspace: t->ws with plan.ws_stride (a plan made with_gv).  Asynchronous on st, behind the solve.
 int traj_gv_launch(vcmi_traj *t, const TrajSolvePlan &plan, const TrajGV &gv, hipStream_t st);
 // the checks of a call on a TrajectoryGVGMMMap (T may be NULL) and the per-call parameters of its GV ascent; no device work
 int trajgv_args(const vcmi_trajgv *h, int64_t n, const int64_t *T, int epochs, TrajGV *gv);
