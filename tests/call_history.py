@@ -17,7 +17,7 @@ import numpy as np
 
 # ---- csrc constants restated (tests/test_call_history_host.py reads them back from the sources) ----
 GROUP_CHUNK = 1024          # kGroupChunk, csrc/grouping.hpp
-SORT_MIN_FRAMES = 8192      # kSortMinFrames, csrc/gmmmap.hip: calls from here on are grouped
+SORT_MIN_FRAMES = 8192      # kSortMinFrames, csrc/gmmmap_group.hip: calls from here on are grouped
 
 
 def fresh(fn):
@@ -71,7 +71,7 @@ def same_bits(a, b):
 
 
 def grouping_geometry(T, M):
-    """launch_grouping (csrc/gmmmap.hip) restated: chunks of 1024 frames, 2^shift chunks per super-chunk (the power of two
+    """launch_grouping (csrc/gmmmap_group.hip) restated: chunks of 1024 frames, 2^shift chunks per super-chunk (the power of two
     from 32 on that reaches sqrt(nchunks)), nsuper super-chunks, and the ints one super-chunk table needs."""
     nchunks = (T + GROUP_CHUNK - 1) // GROUP_CHUNK
     shift = 5

@@ -19,8 +19,8 @@ def _constant(file, name):
 
 def test_restated_constants_are_the_library_s():
     assert _constant("grouping.hpp", "kGroupChunk") == ch.GROUP_CHUNK
-    assert _constant("gmmmap.hip", "kSortMinFrames") == ch.SORT_MIN_FRAMES
-    src = open(os.path.join(CSRC, "gmmmap.hip")).read()
+    assert _constant("gmmmap_group.hip", "kSortMinFrames") == ch.SORT_MIN_FRAMES
+    src = open(os.path.join(CSRC, "gmmmap_group.hip")).read()
     # group_super_shift: from 5 on, while 2^(2 sh) < nchunks
     assert "int sh = 5;" in src and "while (((int64_t)1 << (2 * sh)) < nchunks) ++sh;" in src
 

@@ -1,4 +1,4 @@
-"""fvconvert's frame grouping in two launches (csrc/gmmmap.hip: key kernel with chunk and super-chunk histograms, then
+"""fvconvert's frame grouping in two launches (csrc/gmmmap_group.hip: key kernel with chunk and super-chunk histograms, then
 gmmmap_group_place_kernel) and the screen kernels that take their groups from gbase (csrc/gmmmap_screen.hpp: groups_in_range),
 on the shapes where that can go wrong: the smallest grouped call, partial last chunks and tiles, two super-chunks, models whose
 frames leave most groups empty (runs of equal gbase entries, first, last and in between), many small groups per workgroup,

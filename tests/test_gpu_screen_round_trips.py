@@ -1,4 +1,4 @@
-"""The screen kernels' row access in two halves (csrc/gmmmap.hip: request_frame_rows / finish_frame_rows) and what rests on it in
+"""The screen kernels' row access in two halves (csrc/gmmmap_rows.hpp: request_frame_rows / finish_frame_rows) and what rests on it in
 csrc/gmmmap_screen.hpp: the prologue that requests every tile's rows at clamped positions before it waits for any, the reload of
 the rows behind the first survivor's block, and the per-wave survivor bitmap -- on the shapes where each can go wrong: last
 workgroups with one live frame, a dead second tile, waves that lie entirely beyond T; rows that are not whole 128-byte lines

@@ -1,7 +1,7 @@
 """tools/small_T_sweep.py -- device-resident fvconvert of utterance-sized inputs (D = 40, M = 64 and the fixture model):
 median time of one synchronised call per T, with the library's choice of launch shape (one frame tile per wave up to
-32768 frames) and with the throughput shape forced (DBG_CONVERT_WIDE_TILES).  The thresholds in csrc/gmmmap.hip
-(kSmallCallFrames, kSortMinFrames) come from this sweep, run with the two as environment knobs of a probe build.
+32768 frames) and with the throughput shape forced (DBG_CONVERT_WIDE_TILES).  The thresholds kSmallCallFrames (csrc/gmmmap.hip)
+and kSortMinFrames (csrc/gmmmap_group.hip) come from this sweep, run with the two as environment knobs of a probe build.
 
     gpurun -- python tools/small_T_sweep.py
 """

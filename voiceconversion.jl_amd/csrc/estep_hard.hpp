@@ -10,7 +10,7 @@
 //      HARD when every mixture but the best one satisfies  l^_m + eps_m < (l^_best - eps_best) - 746: then exp(l_m - max) is
 //      exactly 0 in FP64 for all of them -- also as estep_mfma_kernel evaluates it -- and the best one's responsibility is
 //      exactly 1.  key = that mixture; every other frame gets key = M ("soft");
-//   2. the stable counting sort of gmmmap.hip (grouping.hpp) by key;
+//   2. the stable counting sort of gmmmap_group.hip (grouping.hpp) by key;
 //   3. estep_hard_stats_kernel: per mixture and 256-frame piece of its hard frames: count, sum x, sum x^2 (weights are exactly 1)
 //      and sum_d (x_d - mu_d)^2 / var_d for the log-likelihood (the winner's log-density term by term, as the reference formula
 //      reads) -- one coalesced pass over the rows through perm; estep_hard_reduce_kernel adds a mixture's pieces in order;

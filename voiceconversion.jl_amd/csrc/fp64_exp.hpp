@@ -1,5 +1,5 @@
-// fp64_exp.hpp -- e^x for x <= 0 on the FP64 vector pipe, as lean as the softmax loops need it (shared by gmmmap.hip and
-// estep.hip).  The FP64 VALU shares its pipe with the FP64 MFMAs, so every instruction here is paid for in
+// fp64_exp.hpp -- e^x for x <= 0 on the FP64 vector pipe, as lean as the softmax loops need it (shared by gmmmap.hip,
+// gmmmap_fallback.hip and estep.hip).  The FP64 VALU shares its pipe with the FP64 MFMAs, so every instruction here is paid for in
 // matrix time.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -1,4 +1,5 @@
-// gmmmap_handle.hpp -- the opaque vcmi_gmmmap handle (shared by gmmmap.hip, gmmmap_prepare.cpp, estep_full.hip, gmm_em.hip and the traj*.hip files).
+// gmmmap_handle.hpp -- the opaque vcmi_gmmmap handle and the host functions around it (shared by the gmmmap*
+// files, gmm_px_prep.hip, estep_full.hip, gmm_em.hip and the traj*.hip files).
 #pragma once
 #include "vcmi_common.hpp"
 #include "gmmmap_layout.hpp"
@@ -61,7 +62,7 @@ struct vcmi_gmmmap {
   vcmi::DevBuf<int> grp;
   vcmi::StreamOrder grp_order;   // orders every call that uses the handle's scratch: grp, grp_super and scratch_lp below
   // the grouping's super-chunk histograms: TWO tables of grp_super_stride ints, each all zero between the calls that use it
-  // (launch_grouping, gmmmap.hip: call n adds into table n & 1 and clears the other one).  grp_super_used[i]: ints of table i
+  // (launch_grouping, gmmmap_group.hip: call n adds into table n & 1 and clears the other one).  grp_super_used[i]: ints of table i
   // that the last call on it left non-zero; grp_super_ok: false until the tables are known to be in that state (new or grown
   // buffer, a call whose launches did not all go out) -- the next call then zeroes both before it starts.
   vcmi::DevBuf<int> grp_super;
@@ -110,15 +111,19 @@ int gmm_px_create(const double *w, const double *mu, const double *sigma, int D,
 // Same handle prepared ON THE DEVICE from device-resident parameters (w (M), mu (D,M), sigma (D,D,M)): one workgroup
 // per mixture does the Cholesky, the triangular inverse and the MFMA operand packing.  Asynchronous on `st`;
 // *d_flag (device int, zeroed by the caller) receives m+1 for a mixture whose covariance is not positive definite.
+// (gmm_px_prep.hip)
 bool gmm_px_device_prepare_supported(int D);
 int gmm_px_prepare_device(vcmi_gmmmap **inout, const double *d_w, const double *d_mu, const double *d_sigma, int D, int M,
                           int *d_flag, hipStream_t st);
+// The device routines behind the C entry points (gmmmap.hip): device pointers, asynchronous on st.
 int gmmmap_convert_device(vcmi_gmmmap *g, const double *dX, int64_t ldx, int64_t T, double *dY, int64_t ldy, hipStream_t st);
 int gmmmap_logdens_device(vcmi_gmmmap *g, const double *dX, int64_t ldx, int64_t T, double *dLP, hipStream_t st);
 int gmmmap_posterior_device(vcmi_gmmmap *g, const double *dX, int64_t ldx, int64_t T, double *dP, hipStream_t st);
 // allow_screen: long inputs may be grouped and run the screened arg-max (exact; pays for draws from a peaked p(x))
 int gmmmap_predict_device(vcmi_gmmmap *g, const double *dX, int64_t ldx, int64_t T, int64_t *didx, hipStream_t st, bool allow_screen = true);
-// Device group support (devgroup.hpp): gmmmap_sync_replicas is called by the host thread before group_run; inside the
+// vcmi_gmmmap_convert_plan's shape: -1 no tile kernel for g, 0 dense (prune = +inf), 1 broad, 2 peaked, 3 screened
+int gmmmap_convert_plan_shape(const vcmi_gmmmap *g);
+// Device group support (devgroup.hpp, gmmmap_api.cpp): gmmmap_sync_replicas is called by the host thread before group_run; inside the
 // run member i obtains its converter (g itself on g's device, else a replica created on first use).
 void gmmmap_sync_replicas(vcmi_gmmmap *g);
 int gmmmap_member(vcmi_gmmmap *g, int member, vcmi_gmmmap **out);

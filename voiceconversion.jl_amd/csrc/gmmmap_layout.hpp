@@ -1,4 +1,4 @@
-// gmmmap_layout.hpp -- what the host packers (gmmmap_prepare.cpp) and the kernels (gmmmap.hip, gmmmap_screen.hpp) must agree
+// gmmmap_layout.hpp -- what the host packers (gmmmap_prepare.cpp) and the kernels (gmmmap.hip, gmmmap_screen.hpp, gmmmap_group.hip) must agree
 // on, written down once: the row tiling of [U_m ; A_m] and the issue order of its operand fragments, the lane rule of an
 // FP64 MFMA A-operand fragment, the stage layouts of the screens and the operands of the frame grouping.
 #pragma once
@@ -100,10 +100,16 @@ inline void fill_fragment(double *dst, int ks, Fn f) {
 // ------------------------------------------------------------------------------------------------
 // which padded dimensions have kernels
 // ------------------------------------------------------------------------------------------------
-// the tile kernel (gmmmap_mfma_kernel): DP = 16, 20, ... 80, the instantiation list of dispatch_mfma in gmmmap.hip
-inline bool gmmmap_has_mfma(int DP) { return DP >= 16 && DP <= 80 && DP % 4 == 0; }
+// The instantiation lists, written once: X(DP) for every padded dimension of the bf16 screen (.._40), of the screen kernels of
+// shape 3 (.._48) and of the tile kernel, predict's screen and the grouping keys (all of them).  The switches of gmmmap.hip and
+// gmmmap_group.hip expand them; the predicates below answer for the same sets (checked at compile time).
+#define VCMI_TILE_DIMS_40(X) X(16) X(20) X(24) X(28) X(32) X(36) X(40)
+#define VCMI_TILE_DIMS_48(X) VCMI_TILE_DIMS_40(X) X(44) X(48)
+#define VCMI_TILE_DIMS(X) VCMI_TILE_DIMS_48(X) X(52) X(56) X(60) X(64) X(68) X(72) X(76) X(80)
+// the tile kernel (gmmmap_mfma_kernel): DP = 16, 20, ... 80
+constexpr bool gmmmap_has_mfma(int DP) { return DP >= 16 && DP <= 80 && DP % 4 == 0; }
 // shape 3 (gmmmap_screen.hpp): DP = 16..48, any M up to 1024 (the survivors' bitmap)
-inline bool screen_has_kernel(int DP) { return DP >= 16 && DP <= 48 && DP % 4 == 0; }
+constexpr bool screen_has_kernel(int DP) { return DP >= 16 && DP <= 48 && DP % 4 == 0; }
 
 // ------------------------------------------------------------------------------------------------
 // stage layouts of the screens (gmmmap_screen.hpp)
@@ -146,6 +152,18 @@ __host__ __device__ constexpr int screen16_tile_doubles() { return 3 * 128; }
 __host__ __device__ constexpr int screen16_stage_doubles(int DP) { return screen_quads(DP) * (screen16_tile_doubles() + 32); }
 __host__ __device__ constexpr bool screen16_has(int DP) { return DP >= 16 && DP <= 40 && DP % 4 == 0; }
 
+// the three predicates are true exactly on their lists
+#define VCMI_DIM_IS(DPV) || DP == DPV
+constexpr bool tile_dims_agree() {
+  for (int DP = -4; DP <= 256; ++DP)
+    if (gmmmap_has_mfma(DP) != (false VCMI_TILE_DIMS(VCMI_DIM_IS)) || screen_has_kernel(DP) != (false VCMI_TILE_DIMS_48(VCMI_DIM_IS)) ||
+        screen16_has(DP) != (false VCMI_TILE_DIMS_40(VCMI_DIM_IS)))
+      return false;
+  return true;
+}
+#undef VCMI_DIM_IS
+static_assert(tile_dims_agree(), "gmmmap_has_mfma / screen_has_kernel / screen16_has and the VCMI_TILE_DIMS lists disagree");
+
 // ---- the second look of the bf16 screen: sixteen rows of ONE mixture per tile (packedQ2, pack_screen2_bf16) ----------------
 // A mixture that its four strongest rows do not rule out is looked at once more with the min(16, D) strongest rows of the same
 // eigen-expansion before it becomes a survivor: the same four instructions against the same B operands, the same margins per
@@ -161,7 +179,7 @@ __host__ __device__ constexpr int screen2_tile_doubles() { return screen16_tile_
 constexpr size_t screen2_doubles(int M) { return (size_t)M * screen2_tile_doubles(); }
 
 // ------------------------------------------------------------------------------------------------
-// operands of fvconvert's frame grouping (gmmmap_group_key_kernel / gmmmap_group_key16_kernel, gmmmap.hip)
+// operands of fvconvert's frame grouping (gmmmap_group_key_kernel / gmmmap_group_key16_kernel, gmmmap_group.hip)
 // ------------------------------------------------------------------------------------------------
 constexpr int kGroupKeyDims = 24;     // dimensions the nearest-mean key is taken over (a multiple of 4)
 constexpr int kKey16TileBytes = 2 * 1024 + 64;   // per 16 mixtures: 64 x 16 bytes of hi, 64 x 16 bytes of lo, 4 x 4 floats of |mu|^2

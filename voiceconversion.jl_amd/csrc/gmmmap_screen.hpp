@@ -1,5 +1,5 @@
 // gmmmap_screen.hpp -- fvconvert for PEAKED models on grouped frames: screen four mixtures per MFMA tile, evaluate the few that
-// survive (included by gmmmap.hip; shape 3 of vcmi_gmmmap_convert_plan).
+// survive (included by gmmmap.hip, after fp64_exp.hpp; shape 3 of vcmi_gmmmap_convert_plan).
 //
 // What the "peaked" loop of gmmmap_mfma_kernel (PRUNE = 2) spends its time on: of its ~10.5 MFMAs per (16-frame tile,
 // mixture) all but ~0.7 only PROVE that the mixture's posterior is below e^-prune -- the last 16-row whitening tile, whose
@@ -33,6 +33,7 @@
 #include <type_traits>
 #include "bf16_split.hpp"
 #include "gmmmap_layout.hpp"      // rows per mixture, stage layouts of the FP64 and the bf16 screen
+#include "gmmmap_rows.hpp"        // lane-group sums and transposes, rows of x and y as whole lines
 #include "lds_dma.hpp"
 
 namespace vcmi {
@@ -121,7 +122,7 @@ gmmmap_screen_kernel(const double *__restrict__ packed, const double *__restrict
       }
     });
   };
-  // (round 6: rows as whole 128-byte lines where they are 16-byte aligned and unpadded -- load_frame_row(s), gmmmap.hip)
+  // (round 6: rows as whole 128-byte lines where they are 16-byte aligned and unpadded -- load_frame_row(s), gmmmap_rows.hpp)
   const bool xlines = rows_as_lines(X, ldx, D, DP);
   // one tile per wave: the rows of x, requested and finished in one call (also the reload of step 3)
   auto load_x1 = [&]() {
@@ -623,7 +624,7 @@ gmmmap_screen_kernel(const double *__restrict__ packed, const double *__restrict
   for (int f = 0; f < FT; ++f) {
     const int64_t fr = frame0 + 16 * f + lcol;
     const double inv = 1.0 / den[f];
-    // rows of y as whole 128-byte lines where they can be (round 6: store_frame_row, gmmmap.hip)
+    // rows of y as whole 128-byte lines where they can be (round 6: store_frame_row, gmmmap_rows.hpp)
     double yo[KS];
 #pragma unroll
     for (int j = 0; j < KS; ++j) yo[j] = yacc[f][j] * inv;

@@ -1,11 +1,22 @@
-// grouping.hpp -- the stable counting sort of frames by an integer key (defined in gmmmap.hip; also used by estep.hip).
-// These two are the scan + scatter pair that the E-step's hard path launches behind its gate; fvconvert and predict sort
-// with one launch fewer (gmmmap_group_place_kernel, gmmmap.hip: no scan, super-chunk histograms from the key kernel).
+// grouping.hpp -- the stable counting sort of frames by an integer key (gmmmap_group.hip), as gmmmap.hip and estep.hip use it.
 #pragma once
 #include "vcmi_common.hpp"
 
+struct vcmi_gmmmap;
+
 namespace vcmi {
 constexpr int kGroupChunk = 1024;     // frames per chunk of the grouping sort (64 tiles of 16; 16 wave rows of 64)
+
+// ---- fvconvert and predict (gmmmap.hip): frames grouped by their nearest source mean, in two launches (keys with chunk and
+// super-chunk histograms, then gmmmap_group_place_kernel: no scan) ----
+// whether a call of T frames on g can be grouped at all (enough frames, a key operand, its LDS)
+bool can_group(const vcmi_gmmmap *g, int64_t T);
+// The two grouping kernels on g's scratch: *perm_out = frames in group order, *gbase_out = first sorted position of every group
+// (M + 1 ints), *key_out = group of every frame.  Enters g->grp_order on st; the caller leaves it after its last kernel.
+int launch_grouping(vcmi_gmmmap *g, const double *dX, int64_t ldx, int64_t T, hipStream_t st, int **key_out, int **perm_out,
+                    int **gbase_out);
+
+// ---- the E-step's hard path (estep.hip): the scan + scatter pair, launched behind its gate ----
 // chunkhist[c][k] (counts of key k in chunk c of kGroupChunk consecutive frames) -> its exclusive prefix over the chunks, total[k]
 // (gate, optional: a device word; 0 -> the kernel returns at once -- estep_path.hpp)
 __global__ void gmmmap_group_scan_kernel(int *__restrict__ chunkhist, int64_t nchunks, int M, int *__restrict__ total, const int64_t *__restrict__ gate);

@@ -1,6 +1,7 @@
 // vcmi_common.hpp -- status/error plumbing shared by the libvcmi translation units.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <atomic>
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
@@ -104,6 +105,20 @@ struct StreamOrderScope {
   }
   int status() const { return rc; }
 };
+
+// hipFuncAttributeMaxDynamicSharedMemorySize of `kern`, once per DEVICE (the attribute is per device, so a host that drives
+// several GPUs sets it on each of them).  `done` is the call site's own `static std::atomic<bool>[64]`, one flag per device of
+// the calling thread; a device index outside the table sets the attribute on every call.
+template <class Kern>
+inline int set_max_dynamic_lds(Kern kern, size_t bytes, std::atomic<bool> (&done)[64]) {
+  int dev = 0;
+  VCMI_HIP(hipGetDevice(&dev));
+  if (dev < 0 || dev >= 64 || !done[dev].load(std::memory_order_acquire)) {
+    VCMI_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+    if (dev >= 0 && dev < 64) done[dev].store(true, std::memory_order_release);
+  }
+  return VCMI_OK;
+}
 
 // Test hook (vcmi_debug_force, not part of include/vcmi.h): forces the fallback kernels that a given shape would not
 // select by itself, so that the parity tests cover them.  Nothing on the call path reads the environment.
