@@ -382,6 +382,24 @@ int vcmi_traj_convert_batch_dev(vcmi_traj *t, int64_t n, const double *dX, const
  * accepts converts with EM (2D <= 96 on MFMA tiles, above that one workgroup per frame). */
 int vcmi_traj_set_em(vcmi_traj *t, int iters);
 int vcmi_traj_get_em(const vcmi_traj *t);
+/* The conditional precisions of the conversion.  FULL (default): Dy_m = inv(Sigma^yy_m - A_m Sigma^xy_m), the reference's
+ * conversion, launch for launch as before.  DIAG: the conditional covariance of every mixture taken as diagonal, as MLPG is
+ * commonly run: q_m = 1 ./ diag(Sigma^yy_m - A_m Sigma^xy_m) (the reciprocals of the conditional variances, not the diagonal of
+ * Dy_m).  The normal equations then fall apart into 2 D symmetric tridiagonal systems per utterance -- one per static dimension
+ * and frame parity, strictly diagonally dominant -- which traj_diag_solve_kernel (csrc/traj_diag.hip) solves with the Thomas
+ * recurrence: O(T D) work instead of O(T D^3), one D T workspace, no LDS, the same cost per dimension for every D.
+ * The setting belongs to the handle, like vcmi_traj_set_em: vcmi_traj_convert, _batch, _batch_dev, the vcmi_vc_traj family (per
+ * chunk) and vcmi_vc_traj_batch[_dev] honour it, also on the replicas of a device group.  The diagonal model (q and the
+ * images of diag(q_m) the g_t kernels read: (M (2D)^2 + M 16 NT 4 KS + 2 D M) doubles) is built and uploaded on the first
+ * switch to DIAG, on the calling thread's device, and kept.
+ * VCMI_ERR_NOT_PD: a conditional variance that is zero, negative or not finite.  VCMI_ERR_ARG, the setting unchanged: an unknown
+ * kind; DIAG on a handle with EM iterations > 0, and vcmi_traj_set_em(t, n > 0) on a DIAG handle.  Every convert entry of a
+ * vcmi_trajgv over a DIAG handle returns VCMI_ERR_ARG before anything runs.  vcmi_traj_cond_loglik[_dev] ignores the setting:
+ * it always evaluates the full-covariance model. */
+#define VCMI_TRAJ_PRECISION_FULL 0
+#define VCMI_TRAJ_PRECISION_DIAG 1
+int vcmi_traj_set_precision(vcmi_traj *t, int kind);
+int vcmi_traj_get_precision(const vcmi_traj *t);
 /* L(y) = log P(W y | X) of the statement above for one utterance: X (2D,T), Y (D,T).  VCMI_ERR_NOT_PD where the objective is
  * undefined (see above).  The _dev entry takes dense device matrices and writes *dL on `stream`; it first waits for `stream`
  * and uploads a 32-byte descriptor synchronously (the descriptor buffer is shared with the conversion entries), the kernels
@@ -477,11 +495,12 @@ int vcmi_vc_trajgv_dev(vcmi_trajgv *h, const double *dfm, int64_t ldf, int64_t T
  *   - like the other batch entries, and unlike the single call, length(t) is left unchanged.
  * The chunks of all utterances go through ONE trajectory solve (the launch of vcmi_traj_convert_batch_dev), the two ends run as
  * segmented kernels over (utterance, tile) work lists made on the host; the filter's sums keep the order of the single call, so
- * an utterance's result carries the bits the single call computes.  vcmi_traj_set_em is honoured per chunk.
+ * an utterance's result carries the bits the single call computes.  vcmi_traj_set_em and vcmi_traj_set_precision are honoured
+ * per chunk.
  * n = 0 is a no-op; T[u] = 0 is allowed and yields nothing for u.  Refused before anything is uploaded or launched, with every
  * output untouched and length(t) as it was: sigma2 with some T[u] = 1: VCMI_ERR_DIM; a GV converter with a one-frame chunk
  * (T[u] mod L = 1): VCMI_ERR_DIM; length(t) < 1, n < 0, T[u] < 0, a NULL matrix with T[u] > 0: VCMI_ERR_ARG; a GV converter
- * over a handle with EM switched on: VCMI_ERR_ARG (as vcmi_vc_trajgv).
+ * over a handle with EM switched on or with diagonal precisions: VCMI_ERR_ARG (as vcmi_vc_trajgv).
  * The entries run on the calling thread's device (the device group of vcmi_set_devices is not used), in the per-thread
  * scratch of the vcmi_vc_traj_static family under its rule (a host-pointer entry frees it on return above 256 MiB).  Footprint,
  * N = sum T: converter input and result, 3 D N doubles; the host-pointer entries add the staging matrix with the inputs and

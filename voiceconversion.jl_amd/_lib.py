@@ -126,6 +126,8 @@ SIGNATURES = {
     "vcmi_traj_convert_batch_dev": (_int, [_vp, _i64, _vp, _ip, _ip, _vp, _ip, _vp]),
     "vcmi_traj_set_em": (_int, [_vp, _int]),
     "vcmi_traj_get_em": (_int, [_vp]),
+    "vcmi_traj_set_precision": (_int, [_vp, _int]),
+    "vcmi_traj_get_precision": (_int, [_vp]),
     "vcmi_traj_cond_loglik": (_int, [_vp, _dp, _dp, _i64, _dp]),
     "vcmi_traj_cond_loglik_dev": (_int, [_vp, _vp, _vp, _i64, _vp, _vp]),
     "vcmi_traj_em_history": (_int, [_vp, _dp, _int]),

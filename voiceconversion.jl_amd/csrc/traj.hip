@@ -15,7 +15,7 @@
 // One workgroup per utterance factorises P = L L' with a right-looking Cholesky on a sliding 3D x 3D window held
 // in LDS (the right-hand side rides along as an extra row, so z = L^-1 r falls out of the same updates), streams
 // the D-column panels of L to an HBM workspace, and back-substitutes L' y = z reading the panels in reverse.
-// Here: the g_t kernels, traj_run, the batch routines and the convert entries; solvers: traj_solve.hip, GV: traj_gv.hip, EM:
+// Here: the g_t kernels, traj_run, the batch routines and the convert entries; solvers: traj_solve.hip (diagonal precisions: traj_diag.hip), GV: traj_gv.hip, EM:
 // traj_em.hip, vc: traj_vc.cpp, the constructor's arithmetic: traj_prepare.cpp (what crosses them: traj_internal.hpp).
 #include "traj_internal.hpp"
 #include "traj_prepare.hpp"
@@ -202,11 +202,14 @@ int traj_run(vcmi_traj *t, std::vector<TrajUtt> &utts, int64_t nframes, bool con
   VCMI_TRY(t->gbuf.reserve((size_t)nframes * D2));
   // (1) mhat = predict(g.px, X), src/trajectory_gmmmap.jl:82
   const bool g_mfma = t->NT <= 6 && !debug_flag(kDbgTrajGScalar);   // g_t on MFMA tiles (one workgroup per utterance)
+  // diagonal conditional precisions: the same g_t kernels on the images of diag(q_m), then the tridiagonal solver
+  const bool diag = t->precision == VCMI_TRAJ_PRECISION_DIAG;
+  const double *QT = diag ? t->dg_QT.p : t->QT.p, *Qfrag = diag ? t->dg_Qfrag.p : t->Qfrag.p;
   auto arg_max = [&](const double *X, int64_t T, int64_t f0) -> int {     // ... and g_t where the scalar kernel runs
     VCMI_TRY(gmmmap_predict_device(t->g, X, D2, T, t->mhat.p + f0, st, /*allow_screen=*/false));
     if (!g_mfma)
       hipLaunchKernelGGL(traj_g_kernel, dim3((unsigned)T), dim3(128), 2 * D2 * sizeof(double), st, X, T, D2, t->mhat.p + f0, t->AT.p,
-                         t->QT.p, t->bvec.p, t->gbuf.p + (size_t)f0 * D2);
+                         QT, t->bvec.p, t->gbuf.p + (size_t)f0 * D2);
     return VCMI_OK;
   };
   if (contiguous) VCMI_TRY(arg_max(dX0, nframes, 0));
@@ -237,13 +240,14 @@ int traj_run(vcmi_traj *t, std::vector<TrajUtt> &utts, int64_t nframes, bool con
     int split = 1;
     while (split < 8 && (int64_t)n * 2 * split <= (int64_t)cus) split *= 2;
     hipLaunchKernelGGL(traj_g_mfma_kernel, dim3((unsigned)std::min<int64_t>((int64_t)n * split, (int64_t)4 * cus / split * split)),
-                       dim3(nthr), shg, st, du, n, D2, t->M, t->KS, t->Afrag.p, t->Qfrag.p, t->bvec.p, t->mhat.p, t->gperm.p, t->gbuf.p, split);
+                       dim3(nthr), shg, st, du, n, D2, t->M, t->KS, t->Afrag.p, Qfrag, t->bvec.p, t->mhat.p, t->gperm.p, t->gbuf.p, split);
     VCMI_HIP(hipGetLastError());
   }
   TrajSolvePlan plan;      // (its host work runs beside the g_t kernel)
   VCMI_TRY(traj_solve_plan(t, utts, nframes, Tmax, gv != nullptr, &plan));
-  VCMI_TRY(traj_solve_launch(t, plan, plan.padded ? t->Qpad.p : t->Q.p, t->mhat.p, 0, n, st));
   t->em_run_iters = 0;
+  if (diag) return traj_diag_launch(t, plan, st);     // (no EM, no GV over a diagonal handle: refused where they are set)
+  VCMI_TRY(traj_solve_launch(t, plan, plan.padded ? t->Qpad.p : t->Q.p, t->mhat.p, 0, n, st));
   if (t->em_iters > 0) VCMI_TRY(traj_em_run(t, utts, plan, contiguous, dX0, st));
   // (3) global-variance ascent on the solved trajectories, in place
   if (gv && gv->epochs >= 0) VCMI_TRY(traj_gv_launch(t, plan, *gv, st));
@@ -325,7 +329,9 @@ static int traj_member(vcmi_traj *t, int member, vcmi_traj **out) {
   }
   vcmi_traj *&r = t->replicas[(size_t)member];
   if (!r) VCMI_TRY(vcmi_traj_create(g, t->length, &r));
-  r->em_iters = t->em_iters;      // the handle's setting, whenever it was made
+  r->em_iters = t->em_iters;      // the handle's settings, whenever they were made
+  if (t->precision == VCMI_TRAJ_PRECISION_DIAG) VCMI_TRY(traj_diag_ensure(r));     // (on the member's device: its worker thread)
+  r->precision = t->precision;
   *out = r;
   return VCMI_OK;
 }

@@ -575,6 +575,8 @@ using namespace vcmi;
 extern "C" int vcmi_traj_set_em(vcmi_traj *t, int iters) {
   if (!t) return fail(VCMI_ERR_ARG, "vcmi_traj_set_em: NULL handle");
   if (iters < 0) return fail(VCMI_ERR_ARG, "vcmi_traj_set_em: negative iteration count");
+  if (iters > 0 && t->precision == VCMI_TRAJ_PRECISION_DIAG)    // the M-step blends full precision matrices
+    return fail(VCMI_ERR_ARG, "vcmi_traj_set_em: the converter has diagonal conditional precisions (vcmi_traj_set_precision)");
   if (iters > 0 && !t->em_pd)
     return fail(VCMI_ERR_NOT_PD, "vcmi_traj_set_em: (Q_m + Q_m')/2 of some mixture is not positive definite: the EM objective is undefined");
   t->em_iters = iters;

@@ -820,6 +820,8 @@ int trajgv_args(const vcmi_trajgv *h, int64_t n, const int64_t *T, int epochs, T
     return fail(VCMI_ERR_ARG, "TrajectoryGVGMMMap: static dimension %d beyond %d", h->t->D, kGvwThreads);
   if (h->t->em_iters > 0)    // the GV ascent groups frames by mhat[t] <= M and reads Qfrag: no blended precisions
     return fail(VCMI_ERR_ARG, "TrajectoryGVGMMMap: the trajectory converter has EM re-estimation switched on (vcmi_traj_set_em)");
+  if (h->t->precision == VCMI_TRAJ_PRECISION_DIAG)    // ... and it multiplies by the full Q_m
+    return fail(VCMI_ERR_ARG, "TrajectoryGVGMMMap: the trajectory converter has diagonal conditional precisions (vcmi_traj_set_precision)");
   for (int64_t u = 0; T && u < n; ++u)
     if (T[u] == 1) return fail(VCMI_ERR_DIM, "TrajectoryGVGMMMap: the variance of a one-frame trajectory is undefined");
   gv->muv = h->muv.p;

@@ -1,4 +1,4 @@
-// traj_internal.hpp -- what crosses traj.hip, traj_solve.hip, traj_gv.hip, traj_em.hip and traj_vc.cpp: the two handles, the
+// traj_internal.hpp -- what crosses traj.hip, traj_solve.hip, traj_diag.hip, traj_gv.hip, traj_em.hip and traj_vc.cpp: the two handles, the
 // per-call descriptors and HOST functions (no relocatable device code: a kernel is launched by the file that defines it).
 #pragma once
 #include "vcmi_common.hpp"
@@ -49,6 +49,10 @@ struct vcmi_traj {
   bool em_time = false;                   // measurement hook (vcmi_debug_traj_em_times): hip events around the steps of an iteration
   vcmi::EmTimes em_times;                 // ... accumulated since the hook last read them
   size_t em_cap_bytes = 0;                // test hook: table cap in place of kTrajEmTableCapBytes (0: the constant)
+  // diagonal conditional precisions (vcmi_traj_set_precision, traj_diag.hip): made on the first switch to DIAG, then kept
+  int precision = VCMI_TRAJ_PRECISION_FULL;
+  bool diag_ready = false;
+  vcmi::DevBuf<double> dg_q, dg_QT, dg_Qfrag;   // q [M][2D]; diag(q_m) in the layouts of QT and Qfrag
   ~vcmi_traj() {
     for (vcmi_traj *r : replicas) delete r;
   }
@@ -115,12 +119,22 @@ bool traj_solve_is_big(int D);
 // the g_t launch, so this host work overlaps that kernel); with_gv: the workspace
 // also holds the GV ascent's V, r and perm.  Host work only, nothing goes to a stream: reserves ws (the one reserve of the solve
 // path), gpad / ypad / gwin where the solver needs them, and uploads the padded descriptors (synchronous).  A reserve that
-// grows a buffer frees the old one, which waits for the device.
+// grows a buffer frees the old one, which waits for the device.  A handle in diagonal mode gets n, Tmax, nframes, du and a
+// workspace of nframes * D doubles: no padded copies, no window, no occupancy query.
 int traj_solve_plan(vcmi_traj *t, const std::vector<TrajUtt> &utts, int64_t nframes, int Tmax, bool with_gv, TrajSolvePlan *plan);
 // Solve of the (sorted) utterances [b0, b0 + nb) with the precision table Qs (indexed by mh[t] - 1: t->Q / t->Qpad with t->mhat,
 // or the EM loop's table; in plan.Ds) and the right-hand sides in t->gbuf: gbuf -> gpad where padded, the solver the plan chose,
 // ypad -> the utterances' Y after a padded solve.  Asynchronous on st, in launch order; t->status must have been zeroed on st.
 int traj_solve_launch(vcmi_traj *t, const TrajSolvePlan &plan, const double *Qs, const int64_t *mh, int b0, int nb, hipStream_t st);
+
+// ---- traj_diag.hip ----
+// The diagonal model of the handle on the current device (traj_prepare_diag + upload), once; VCMI_ERR_NOT_PD from the host
+// arithmetic.  Synchronous.
+int traj_diag_ensure(vcmi_traj *t);
+// Solve of the plan's utterances with diagonal conditional precisions: right-hand sides in t->gbuf (made with the diagonal
+// images), t->dg_q, t->mhat; workspace t->ws, nframes * D doubles indexed by frame0 (a plan made in diagonal mode).  Asynchronous
+// on st; never writes t->status.
+int traj_diag_launch(vcmi_traj *t, const TrajSolvePlan &plan, hipStream_t st);
 
 // ---- traj_gv.hip ----
 // The GV ascent on the solved trajectories of the plan's utterances, in place (two-team kernel where the frame permutation of

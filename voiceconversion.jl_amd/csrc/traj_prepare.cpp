@@ -11,12 +11,55 @@ namespace vcmi {
 
 static constexpr double kEmLog2Pi = 1.8378770664093454835606594728112;
 
+// W [M][D2][D2] row-major -> F [M][NT][KS][64]: tile (i, ks) of every matrix in MFMA A-operand order, zero outside the matrix
+static void pack_fragments(const std::vector<double> &W, int D2, int M, std::vector<double> &F) {
+  const int NT = (D2 + 15) / 16, KS = (D2 + 3) / 4;
+  const size_t nn = (size_t)D2 * D2;
+  F.assign((size_t)M * NT * KS * 64, 0.0);
+  for (int m = 0; m < M; ++m)
+    for (int i = 0; i < NT; ++i)
+      for (int ks = 0; ks < KS; ++ks)
+        fill_fragment(&F[(((size_t)m * NT + i) * KS + ks) * 64], ks, [&](int row, int k) {
+          return (16 * i + row < D2 && k < D2) ? W[nn * m + (size_t)(16 * i + row) * D2 + k] : 0.0;
+        });
+}
+// Q [M][D2][D2] row-major -> its transposes
+static void transpose_blocks(const std::vector<double> &Q, int D2, int M, std::vector<double> &QT) {
+  const size_t nn = (size_t)D2 * D2;
+  QT.assign(nn * M, 0.0);
+  for (int m = 0; m < M; ++m)
+    for (int r = 0; r < D2; ++r)
+      for (int k = 0; k < D2; ++k) QT[nn * m + (size_t)k * D2 + r] = Q[nn * m + (size_t)r * D2 + k];
+}
+
+int traj_prepare_diag(const std::vector<double> &h_A, const std::vector<double> &h_Sxy, const std::vector<double> &h_Syy, int D2,
+                      int M, TrajDiagModel &dm) {
+  const size_t nn = (size_t)D2 * D2;
+  dm.q.assign((size_t)D2 * M, 0.0);
+  dm.Q.assign(nn * M, 0.0);
+  std::vector<double> tmp(nn);
+  for (int m = 0; m < M; ++m) {
+    la::matmul(&h_A[nn * m], &h_Sxy[nn * m], D2, tmp.data());     // the product traj_prepare_model inverts, diagonal kept
+    for (int r = 0; r < D2; ++r) {
+      const double c = h_Syy[nn * m + (size_t)r * D2 + r] - tmp[(size_t)r * D2 + r];
+      const double q = 1.0 / c;
+      if (!(q > 0.0) || !std::isfinite(q))     // c zero, negative, NaN, or beyond either end of the range
+        return fail(VCMI_ERR_NOT_PD, "TrajectoryGMMMap: conditional variance %d of mixture %d is not positive", r + 1, m + 1);
+      dm.q[(size_t)D2 * m + r] = q;
+      dm.Q[nn * m + (size_t)r * D2 + r] = q;
+    }
+  }
+  transpose_blocks(dm.Q, D2, M, dm.QT);
+  pack_fragments(dm.Q, D2, M, dm.Qfrag);
+  return VCMI_OK;
+}
+
 int traj_prepare_model(const std::vector<double> &h_A, const std::vector<double> &h_Sxy, const std::vector<double> &h_Syy,
                        const std::vector<double> &h_mux, const std::vector<double> &h_muy, int D2, int M, TrajModel &tm) {
   const int D = D2 / 2;
   const size_t nn = (size_t)D2 * D2;
   std::vector<double> &Q = tm.Q, &QT = tm.QT, &AT = tm.AT, &bv = tm.b;
-  for (auto *v : {&Q, &QT, &AT}) v->assign(nn * M, 0.0);
+  Q.assign(nn * M, 0.0);
   bv.assign((size_t)D2 * M, 0.0);
   std::vector<double> tmp(nn), S(nn);
   for (int m = 0; m < M; ++m) {
@@ -27,14 +70,12 @@ int traj_prepare_model(const std::vector<double> &h_A, const std::vector<double>
       return fail(VCMI_ERR_NOT_PD, "TrajectoryGMMMap: conditional covariance of mixture %d is singular", m + 1);
     for (int r = 0; r < D2; ++r) {
       double ba = 0.0;
-      for (int k = 0; k < D2; ++k) {
-        QT[nn * m + (size_t)k * D2 + r] = Q[nn * m + (size_t)r * D2 + k];
-        AT[nn * m + (size_t)k * D2 + r] = h_A[nn * m + (size_t)r * D2 + k];
-        ba += h_A[nn * m + (size_t)r * D2 + k] * h_mux[(size_t)D2 * m + k];
-      }
+      for (int k = 0; k < D2; ++k) ba += h_A[nn * m + (size_t)r * D2 + k] * h_mux[(size_t)D2 * m + k];
       bv[(size_t)D2 * m + r] = h_muy[(size_t)D2 * m + r] - ba;
     }
   }
+  transpose_blocks(Q, D2, M, QT);
+  transpose_blocks(h_A, D2, M, AT);
   // c_m = logdet((Q_m + Q_m') / 2) / 2 of the EM objective (traj_em.hip), with its constant - D log 2 pi; a model without it
   // (some symmetrised Q_m not positive definite) converts as before and refuses vcmi_traj_set_em(t, n > 0)
   tm.cm.assign((size_t)M, 0.0);
@@ -53,18 +94,8 @@ int traj_prepare_model(const std::vector<double> &h_A, const std::vector<double>
   // Q and A in MFMA A-operand order: fragment (row tile i, k-step ks) holds rows 16 i .. 16 i + 15, columns 4 ks .. 4 ks + 3
   tm.NT = (D2 + 15) / 16;
   tm.KS = (D2 + 3) / 4;
-  tm.Qfrag.assign((size_t)M * tm.NT * tm.KS * 64, 0.0);
-  tm.Afrag.assign(tm.Qfrag.size(), 0.0);
-  for (int m = 0; m < M; ++m)
-    for (int i = 0; i < tm.NT; ++i)
-      for (int ks = 0; ks < tm.KS; ++ks) {
-        auto frag = [&](const double *W, std::vector<double> &F) {     // tile (i, ks) of the row-major (D2,D2) matrix W, zero outside it
-          fill_fragment(&F[(((size_t)m * tm.NT + i) * tm.KS + ks) * 64], ks,
-                        [&](int row, int k) { return (16 * i + row < D2 && k < D2) ? W[(size_t)(16 * i + row) * D2 + k] : 0.0; });
-        };
-        frag(&Q[nn * m], tm.Qfrag);
-        frag(&h_A[nn * m], tm.Afrag);
-      }
+  pack_fragments(Q, D2, M, tm.Qfrag);
+  pack_fragments(h_A, D2, M, tm.Afrag);
   // Static dimensions without an instantiation of the blocked solver run in the next larger one
   tm.Dpad = traj_blk_padded_dim(D);
   tm.Qpad.clear();

@@ -37,4 +37,17 @@ struct TrajModel {
 int traj_prepare_model(const std::vector<double> &h_A, const std::vector<double> &h_Sxy, const std::vector<double> &h_Syy,
                        const std::vector<double> &h_mux, const std::vector<double> &h_muy, int D2, int M, TrajModel &tm);
 
+// The second model of a converter (VCMI_TRAJ_PRECISION_DIAG): the conditional covariance C_m = Syy_m - A_m Sxy_m taken as
+// diagonal, q_m = 1 ./ diag(C_m) -- the reciprocals of the conditional variances, NOT the diagonal of Q_m = inv(C_m).  The g_t
+// kernels run unchanged on the images of diag(q_m), packed by the routines that pack Q_m; the tridiagonal solver
+// (traj_diag.hip) reads q itself.
+struct TrajDiagModel {
+  std::vector<double> q;             // [M][2D]
+  std::vector<double> Q, QT;         // [M][2D][2D] diag(q_m), row-major and transposed (the same bytes)
+  std::vector<double> Qfrag;         // diag(q_m) in MFMA A-operand order [M][NT][KS][64]
+};
+// VCMI_ERR_NOT_PD: some conditional variance is zero, negative or not finite.
+int traj_prepare_diag(const std::vector<double> &h_A, const std::vector<double> &h_Sxy, const std::vector<double> &h_Syy, int D2,
+                      int M, TrajDiagModel &dm);
+
 }  // namespace vcmi

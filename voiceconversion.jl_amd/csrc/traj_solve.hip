@@ -467,6 +467,12 @@ int traj_solve_plan(vcmi_traj *t, const std::vector<TrajUtt> &utts, int64_t nfra
   p.n = n;
   p.Tmax = Tmax;
   p.nframes = nframes;
+  if (t->precision == VCMI_TRAJ_PRECISION_DIAG) {   // traj_diag.hip: one double per frame and dimension, indexed by frame0; nothing else
+    p.Ds = D;
+    p.du = p.dus = reinterpret_cast<const TrajUtt *>(t->uttbuf.p);
+    p.gs = t->gbuf.p;
+    return t->ws.reserve((size_t)nframes * D);
+  }
   int dev = 0;
   (void)hipGetDevice(&dev);
   (void)hipDeviceGetAttribute(&p.cus, hipDeviceAttributeMultiprocessorCount, dev);

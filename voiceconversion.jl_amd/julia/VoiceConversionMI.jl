@@ -19,7 +19,7 @@ module VoiceConversionMI
 import LinearAlgebra
 
 export DeviceMatrix, FrameByFrameConverter, TrajectoryConverter, GMMMapParam, GMMMap, TrajectoryGMMMap, TrajectoryGVGMMMap,
-       fvconvert, vc, ncomponents, dim, em_iters, em_iters!, cond_loglik, em_history,
+       fvconvert, vc, ncomponents, dim, em_iters, em_iters!, traj_precision, traj_precision!, cond_loglik, em_history,
        VarianceScaling, fvpostf!, fvpostf,
        align, align_mcep, push_delta, GVDataset, sp2mc, mc2sp, mc2b,
        DTW, fit!, update!, set_template!, backward,
@@ -286,7 +286,17 @@ function em_iters!(t::TrajectoryGMMMap, n::Int)
     check(ccall((:vcmi_traj_set_em, libvcmi), Cint, (Ptr{Cvoid}, Cint), t.h, n))
     n
 end
-# L(y) = log P(W y | X) for one utterance: X (2D,T), Y (D,T)
+# The conditional precisions of the conversion: :full (the reference's Dy_m) or :diag (the conditional covariances taken as
+# diagonal: tridiagonal systems per static dimension and frame parity, csrc/traj_diag.hip).  A setting of the converter, like
+# em_iters; not together with em_iters > 0 or under a TrajectoryGVGMMMap.
+const TRAJ_PRECISIONS = (:full, :diag)                                # VCMI_TRAJ_PRECISION_FULL, VCMI_TRAJ_PRECISION_DIAG
+traj_precision(t::TrajectoryGMMMap) = TRAJ_PRECISIONS[Int(ccall((:vcmi_traj_get_precision, libvcmi), Cint, (Ptr{Cvoid},), t.h)) + 1]
+function traj_precision!(t::TrajectoryGMMMap, kind::Symbol)
+    k = findfirst(isequal(kind), TRAJ_PRECISIONS)
+    check(ccall((:vcmi_traj_set_precision, libvcmi), Cint, (Ptr{Cvoid}, Cint), t.h, k === nothing ? -1 : k - 1))
+    kind
+end
+# L(y) = log P(W y | X) for one utterance: X (2D,T), Y (D,T); always of the full-covariance model
 function cond_loglik(t::TrajectoryGMMMap, X::Matrix{Float64}, Y::Matrix{Float64})
     (size(X, 1) == dim(t) && 2size(Y, 1) == size(X, 1) && size(X, 2) == size(Y, 2)) ||
         throw(DimensionMismatch("Inconsistent dimentions."))

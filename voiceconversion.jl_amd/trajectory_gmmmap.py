@@ -128,13 +128,33 @@ class TrajectoryGMMMap(TrajectoryConverter):
     """TrajectoryGMMMap(g::GMMMap, T) -- src/trajectory_gmmmap.jl:3-37.  `g` is a GMMMap over static+delta
     features (dim(g) = 2D).  The constructor precomputes Dy_m = inv(Sigma^yy_m - A_m Sigma^xy_m) (:24-28)."""
 
-    def __init__(self, g, T, em_iters=0):
+    _PRECISIONS = ("full", "diag")          # VCMI_TRAJ_PRECISION_FULL, VCMI_TRAJ_PRECISION_DIAG
+
+    def __init__(self, g, T, em_iters=0, precision="full"):
         self.gmmmap = g
         h = C.c_void_p()
         _lib.check(_lib.lib.vcmi_traj_create(g._h, int(T), C.byref(h)))
         self._h = h
         if em_iters:
             self.em_iters = em_iters
+        if precision != "full":
+            self.precision = precision
+
+    @property
+    def precision(self):
+        """The conditional precisions of the conversion.  "full" (default): Dy_m = inv(Sigma^yy_m - A_m Sigma^xy_m), the
+        reference's conversion.  "diag": the conditional covariance of every mixture taken as diagonal, as MLPG is commonly
+        run -- the normal equations fall apart into tridiagonal systems per static dimension and frame parity, solved in
+        O(T D) (csrc/traj_diag.hip).  fvconvert, fvconvert_batch, vc and vc_batch pick the setting up from the converter.
+        Not together with em_iters > 0 or under a TrajectoryGVGMMMap (VCMIError); cond_loglik always evaluates the
+        full-covariance model."""
+        return self._PRECISIONS[int(_lib.lib.vcmi_traj_get_precision(self._h))]
+
+    @precision.setter
+    def precision(self, kind):
+        # (a name the library does not know goes to it as a kind it does not know: the refusal is the library's)
+        k = self._PRECISIONS.index(kind) if kind in self._PRECISIONS else -1
+        _lib.check(_lib.lib.vcmi_traj_set_precision(self._h, k))
 
     @property
     def em_iters(self):
