@@ -284,9 +284,9 @@ def test_column_segments_and_persistent_workgroups(vc, D):
 @pytest.mark.gpu
 def test_segmented_jobs_at_benchmark_size_repeatedly(vc):
     """The jobs of the fused kernel hand boundary pairs and last cost columns to each other through agent-scope (sc1) stores
-    and loads, ordered by hand, instead of acquire / release fences (csrc/dtw.hip, dtw_wait_flag): a race there would be a
-    rare event, so the benchmark batch (1000 pairs of ~500 x 500 frames: 5465 jobs drawn by 512 persistent workgroups on all
-    eight XCDs) runs several times, segmented and whole-length, and every path must come out the same each time; a sample
+    and loads, ordered by hand, instead of acquire / release fences (csrc/dtw_fused.hip, dtw_wait_flag): a race there would be a
+    rare event, so the benchmark batch (1000 pairs of ~500 x 500 frames, every strip cut into column segments by
+    csrc/dtw_plan.cpp, the jobs drawn by persistent workgroups on all eight XCDs) runs several times, segmented and whole-length, and every path must come out the same each time; a sample
     is checked against the oracle."""
     from oracle import c_oracle as co
     from voiceconversion_jl_amd import _lib

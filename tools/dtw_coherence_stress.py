@@ -1,4 +1,4 @@
-"""One-off stress of the fence-free job synchronisation of the fused DTW kernel (csrc/dtw.hip, dtw_wait_flag): the benchmark
+"""One-off stress of the fence-free job synchronisation of the fused DTW kernel (csrc/dtw_fused.hip, dtw_wait_flag): the benchmark
 batch (1000 pairs of ~500 x 500 frames -> 3279 segment jobs on all eight XCDs) over and over, every result compared with
 the whole-length, grid-order run of the same inputs.  usage: python tools/dtw_coherence_stress.py [reps] [D ...]"""
 import os

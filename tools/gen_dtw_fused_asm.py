@@ -27,7 +27,7 @@ Per column t (one iteration):
       table every 16 columns (global_store_dwordx2: rows r0, r1 adjacent).
   outbox: lane 63 publishes (C0, C1) of column t for the next wave, then the tag t+1.
 
-Operands: see dtw_fused_kernel in dtw.hip.  Fixed registers (all clobbered):
+Operands: see dtw_fused_job in dtw_fused.hip.  Fixed registers (all clobbered):
   v[0:159]   template rows (row 0 at 0, row 1 at 2*DMAX)
   v[160:163] O0, O1 accumulators      v[164:171] four FP64 temporaries
   v[172:175] C0, C1 (current costs)   v[176:179] P0, P1 (neighbour costs of the previous column)
