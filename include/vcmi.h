@@ -291,6 +291,47 @@ int vcmi_gmm_em_diag_estep_dev(vcmi_gmm_em_diag *h, const double *dX, int64_t N,
 int vcmi_gmm_em_diag_mstep(vcmi_gmm_em_diag *h, const double *dstats, void *stream, double *loglik);
 int vcmi_gmm_em_diag_get(vcmi_gmm_em_diag *h, double *w, double *mu, double *var);
 
+/* CROSS-DIAGONAL ("block_diag") joint model -- Toda, Black and Tokuda (2007): each of the four blocks Sigma^xx, Sigma^xy,
+ * Sigma^yx, Sigma^yy is diagonal.  Dj is even, D = Dj / 2; pair d is the joint rows (d, d + D), a 2 x 2 block per pair.
+ * covars (Dj + D, M), column-major: rows [0, Dj) the variances (as the diagonal model's var), rows [Dj, Dj + D) the
+ * cross-covariances c_dm = cov(z_d, z_{d+D}).  With det = vx vy - c^2, dx = z_d - mu_d, dy = z_{d+D} - mu_{d+D}:
+ *   l_nm = log w_m - (Dj log 2 pi + sum_d log det_dm + sum_d (vy dx^2 - 2 c dx dy + vx dy^2) / det_dm) / 2,
+ * evaluated in the centred, factorised form dx^2 / vx + (dy - (c / vx) dx)^2 vx / det (no cancellation to repair, also at
+ * pair correlations close to +-1).  Statistics: one DEVICE buffer [S0 (M) | S1 (Dj,M) | S2 (Dj,M) | Sxy (D,M) | loglik] of
+ * vcmi_estep_bdiag_stats_len(Dj,M) = M (1 + 2 Dj + D) + 1 doubles, each (.,M) part mixture by mixture;
+ * Sxy_dm = sum_n gamma_nm z_d z_{d+D}, the rest as vcmi_estep_diag_dev -- one contiguous buffer, one all-reduce(sum).
+ * Every even Dj in [2, 256] and every M in [1, 256]; anything else: VCMI_ERR_DIM (the message names the limit).  N == 0 gives
+ * zeroed statistics.  A pair is valid when vx > 0, vy > 0 and vx vy - c^2 > 0 (a NaN fails): otherwise VCMI_ERR_NOT_PD, the
+ * message names the first (d, m) in memory order, d the pair index.  Every sum has a fixed order and nothing depends on
+ * earlier calls: identical inputs give identical bits.
+ * Accuracy, per mixture m: each of S0[m], S1[:,m], S2[:,m], Sxy[:,m] within 1e-9 of the exact statistics, relative to that
+ * mixture's own largest value; loglik within 1e-9 relative -- variances at min_covar and pair correlations close to +-1
+ * included. */
+int64_t vcmi_estep_bdiag_stats_len(int Dj, int M);
+int vcmi_estep_bdiag_dev(const double *dX, int64_t N, int Dj, int M, const double *w, const double *mu,
+                         const double *covars, double *dstats, void *stream);
+
+/* The EM loop for the cross-diagonal model.  The handle owns [w (M) | mu (Dj,M) | covars (Dj + D, M)] on the device; one
+ * iteration is
+ *   vcmi_gmm_em_bdiag_estep_dev (vcmi_estep_bdiag_dev's statistics under the handle's parameters, asynchronous on `stream`:
+ *      no parameter crosses the host, the call waits for nothing; bit-identical to vcmi_estep_bdiag_dev called with the
+ *      values vcmi_gmm_em_bdiag_get returns; N == 0 gives zeroed statistics)
+ *   -> the caller sums the statistics buffers of all ranks (one all-reduce of vcmi_estep_bdiag_stats_len(Dj,M) doubles)
+ *   -> vcmi_gmm_em_bdiag_mstep (eps = 2^-52:  w = S0 / (sum S0 + 10 eps) + eps,  inv = 1 / (S0 + 10 eps),  mu = S1 inv,
+ *      var = S2 inv - 2 mu S1 inv + mu mu + min_covar,  c = Sxy inv - mu_d mu_{d+D} (min_covar on variances only); the sum
+ *      over M in a fixed order, no floating-point atomics: the same statistics give the same bits).  It synchronises the
+ *      stream and returns the log-likelihood the statistics carry.
+ * VCMI_ERR_NOT_PD: a pair that is not valid -- from create for the initial parameters, from mstep for updated ones.  After a
+ * failed mstep the handle keeps the parameters the statistics were computed under (vcmi_gmm_em_bdiag_get shows them), every
+ * later mstep fails the same way and vcmi_gmm_em_bdiag_estep_dev returns VCMI_ERR_NOT_PD without launching. */
+typedef struct vcmi_gmm_em_bdiag vcmi_gmm_em_bdiag;
+int vcmi_gmm_em_bdiag_create(int Dj, int M, const double *w, const double *mu, const double *covars, double min_covar,
+                             vcmi_gmm_em_bdiag **out);
+int vcmi_gmm_em_bdiag_destroy(vcmi_gmm_em_bdiag *h);
+int vcmi_gmm_em_bdiag_estep_dev(vcmi_gmm_em_bdiag *h, const double *dX, int64_t N, double *dstats, void *stream);
+int vcmi_gmm_em_bdiag_mstep(vcmi_gmm_em_bdiag *h, const double *dstats, void *stream, double *loglik);
+int vcmi_gmm_em_bdiag_get(vcmi_gmm_em_bdiag *h, double *w, double *mu, double *covars);
+
 /* k-means -- sklearn 0.17 cluster.KMeans, what GMM(init_params="wmc") runs over all of X before the first E-step
  * (bin/train_gmm.jl:84-89).  Centers (Dj,M) column-major, 1 <= Dj <= 256, 1 <= M <= 1024; every distance is the direct
  * difference sum_d (x_d - c_d)^2 (sequential in d, FP64, no contraction); exact ties go to the smaller center index.

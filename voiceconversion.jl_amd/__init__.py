@@ -14,10 +14,12 @@ from .align import align, align_batch  # noqa: F401,E402
 from .estep import (ESTEP_AUTO, ESTEP_HARD, ESTEP_SOFT, estep_diag, estep_diag_allreduce, estep_diag_dev, estep_get_path,  # noqa: F401,E402
                     estep_set_path, mstep_diag, stats_len, unpack_stats,
                     estep_full, estep_full_allreduce, estep_full_dev, fit_full, full_stats_len, mstep_full,
-                    unpack_full_stats)
+                    unpack_full_stats,
+                    bdiag_stats_len, estep_bdiag_dev, mstep_bdiag, unpack_bdiag_stats)
 from .trajectory_gmmmap import TrajectoryGVGMMMap, TrajectoryGMMMap, constructW, push_delta  # noqa: F401,E402
 from . import dist  # noqa: F401,E402
-from .train import DiagEMState, EMState, expand_diag, train_gmm  # noqa: F401,E402
+from .train import (BlockDiagEMState, DiagEMState, EMState, data_block_covariance, expand_block_diag, expand_diag,  # noqa: F401,E402
+                    train_gmm)
 from .kmeans import KMeansState, kmeans  # noqa: F401,E402
 from .gv import VarianceScaling, diffgmm, fvpostf, fvpostf_  # noqa: F401,E402
 from .datasets import GVDataset, ParallelDataset, align_mcep, mc2e  # noqa: F401,E402

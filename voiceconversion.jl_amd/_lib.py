@@ -104,6 +104,13 @@ SIGNATURES = {
     "vcmi_gmm_em_diag_estep_dev": (_int, [_vp, _vp, _i64, _vp, _vp]),
     "vcmi_gmm_em_diag_mstep": (_int, [_vp, _vp, _vp, _dp]),
     "vcmi_gmm_em_diag_get": (_int, [_vp, _dp, _dp, _dp]),
+    "vcmi_estep_bdiag_stats_len": (_i64, [_int, _int]),
+    "vcmi_estep_bdiag_dev": (_int, [_vp, _i64, _int, _int, _dp, _dp, _dp, _vp, _vp]),
+    "vcmi_gmm_em_bdiag_create": (_int, [_int, _int, _dp, _dp, _dp, C.c_double, C.POINTER(_vp)]),
+    "vcmi_gmm_em_bdiag_destroy": (_int, [_vp]),
+    "vcmi_gmm_em_bdiag_estep_dev": (_int, [_vp, _vp, _i64, _vp, _vp]),
+    "vcmi_gmm_em_bdiag_mstep": (_int, [_vp, _vp, _vp, _dp]),
+    "vcmi_gmm_em_bdiag_get": (_int, [_vp, _dp, _dp, _dp]),
     "vcmi_kmeans_stats_len": (_i64, [_int, _int]),
     "vcmi_kmeans_create": (_int, [_int, _int, _dp, C.POINTER(_vp)]),
     "vcmi_kmeans_destroy": (_int, [_vp]),

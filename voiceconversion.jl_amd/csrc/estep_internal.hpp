@@ -1,6 +1,7 @@
-// estep_internal.hpp -- what crosses estep.hip (diagonal E-step), estep_full.hip (full-covariance E-step) and gmm_em.hip
-// (device-resident EM states).  Host functions only: the library is built without relocatable device code, so a kernel is
-// launched by a host function of the file that defines it.
+// estep_internal.hpp -- what crosses estep.hip (diagonal E-step), estep_full.hip (full-covariance E-step), estep_bdiag.hip
+// (cross-diagonal E-step) and gmm_em.hip (device-resident EM states).  Host functions, and two inline helpers that host and
+// device code share: the library is built without relocatable device code, so a kernel is launched by a host function of
+// the file that defines it.
 #pragma once
 #include "vcmi_common.hpp"
 
@@ -37,6 +38,30 @@ int estep_check_dims(int64_t N, int Dj, int M);
 int64_t first_bad_variance(const double *var, int Dj, int M);
 // vcmi_debug_estep_mfma / vcmi_debug_estep_full_mfma on their counter
 int mfma_count_hook(DevBuf<unsigned long long> &count, int enable, int64_t *issued);
+
+// ---- estep_bdiag.hip ----
+// The cross-diagonal ("block_diag") model: joint row d couples with row d + D only, D = Dj / 2; per mixture the covariances
+// are [var (Dj) | c (D)].  Every even Dj in [2, 256] and M in [1, 256]: estep_bdiag_gamma_kernel holds a 64-frame tile of
+// Dj rows in LDS, em_mstep_bdiag_kernel is one thread per pair.
+constexpr int kBdiagMaxDj = 256, kBdiagMaxM = 256;
+// vx vy - c^2 to a few ulps also where it cancels (Kahan's 2 x 2 determinant: the rounding of c c is added back)
+__host__ __device__ inline double bdiag_det(double vx, double vy, double c) {
+  const double cc = c * c;
+  return fma(vx, vy, -cc) - fma(c, c, -cc);
+}
+// the pair's 2 x 2 block is positive definite (a NaN anywhere: not)
+__host__ __device__ inline bool bdiag_pair_valid(double vx, double vy, double c) {
+  return vx > 0.0 && vy > 0.0 && bdiag_det(vx, vy, c) > 0.0;
+}
+// VCMI_ERR_DIM unless Dj is even, 2 <= Dj <= kBdiagMaxDj and 1 <= M <= kBdiagMaxM; the message names the limit
+int estep_bdiag_check_dims(const char *who, int Dj, int M);
+// index d + D m of the first pair of covars (Dj + D, M) that is not valid, -1: none
+int64_t first_bad_pair(const double *covars, int Dj, int M);
+// The E-step of N device-resident frames from a DEVICE parameter block [w (M) | mu (Dj,M) | covars (Dj + D, M)] that the
+// caller keeps alive and orders on `st`; asynchronous, no parameter crosses the host.  *dflag (an int the caller has set to
+// INT_MAX) receives the smallest 1 + d + D m of an invalid pair; N == 0 zeroes the statistics and launches nothing.
+int estep_bdiag_device_block(const double *dX, int64_t N, int Dj, int M, const double *dparams, int *dflag, double *dstats,
+                             hipStream_t st);
 
 // ---- estep_full.hip ----
 // statistics of N device-resident frames under the prepared p(x) handle -> dstats (zeroed here); asynchronous on st

@@ -1,9 +1,10 @@
-// gmm_em.hip -- EM states resident on the device, MI355X (gfx950): vcmi_gmm_em_* (full covariance) and vcmi_gmm_em_diag_*.
+// gmm_em.hip -- EM states resident on the device, MI355X (gfx950): vcmi_gmm_em_* (full covariance), vcmi_gmm_em_diag_* and
+// vcmi_gmm_em_bdiag_* (cross-diagonal).
 //
 // bin/train_gmm.jl:84-103 (sklearn.mixture.GMM(covariance_type="full", min_covar).fit): parameters, statistics and
 // whitening blocks stay in HBM; one iteration is
 //   estep (local statistics) -> [caller all-reduces the statistics buffer over RCCL] -> mstep (+ whitening prep).
-// The E-steps are those of estep_full.hip and estep.hip (estep_internal.hpp); the M-step kernels are here.
+// The E-steps are those of estep_full.hip, estep.hip and estep_bdiag.hip (estep_internal.hpp); the M-step kernels are here.
 #include "estep_internal.hpp"
 #include "gmmmap_handle.hpp"
 #include "hostpipe.hpp"
@@ -82,6 +83,51 @@ em_mstep_diag_kernel(const double *__restrict__ stats, int Dj, int M, double min
     raw[M + e] = mean;
     raw[M + (size_t)M * Dj + e] = v;
     if (!(v > 0.0)) atomicMin(ctl + 1, (int)(1 + e));
+  }
+}
+
+// The cross-diagonal twin (estep.py:mstep_bdiag, operation for operation):
+//   stats = [S0 (M) | S1 (Dj,M) | S2 (Dj,M) | Sxy (D,M) | loglik]  ->  raw = [w (M) | mu (Dj,M) | covars (Dj + D, M)], the block
+//   estep_bdiag_prep_kernel reads; covars[:, m] = [var (Dj) | c (D)], c = Sxy inv - mu_d mu_{d+D} (min_covar on variances only).
+// One workgroup per mixture, thread d owns PAIR d (D <= 128): both means, both variances and the cross-covariance; the total
+// over M, the roundings of the variance and the control block as em_mstep_diag_kernel.  A pair that is not positive definite
+// (bdiag_pair_valid; a NaN included) is reported through ctl[1] as the smallest 1 + d + D m.
+__global__ void __launch_bounds__(256)
+em_mstep_bdiag_kernel(const double *__restrict__ stats, int Dj, int M, double min_covar, double *__restrict__ raw, int *__restrict__ ctl) {
+#pragma clang fp contract(off)
+  __shared__ double red[256];
+  const int tid = threadIdx.x, m = blockIdx.x, D = Dj / 2;
+  if (m == 0 && tid == 0) *reinterpret_cast<double *>(ctl + 2) = stats[(size_t)M * (1 + 2 * (size_t)Dj + D)];
+  if (ctl[0]) return;
+  const double eps = 2.220446049250313e-16;
+  double t = 0.0;
+  for (int k = tid; k < M; k += 256) t += stats[k];
+  red[tid] = t;
+  __syncthreads();
+  for (int o = 128; o >= 1; o >>= 1) {
+    if (tid < o) red[tid] += red[tid + o];
+    __syncthreads();
+  }
+  const double tot = red[0], s0 = stats[m];
+  const double inv = 1.0 / (s0 + 10 * eps);
+  if (tid == 0) raw[m] = s0 / (tot + 10 * eps) + eps;
+  if (tid < D) {
+    const double *S1 = stats + M + (size_t)m * Dj, *S2 = stats + M + (size_t)M * Dj + (size_t)m * Dj;
+    const double sxy = stats[M + 2 * (size_t)M * Dj + (size_t)m * D + tid];
+    double mean[2], v[2];
+    for (int h = 0; h < 2; ++h) {
+      const double s1 = S1[tid + h * D], s2 = S2[tid + h * D];
+      mean[h] = s1 * inv;
+      v[h] = s2 * inv - ((2.0 * mean[h]) * s1) * inv + mean[h] * mean[h] + min_covar;
+    }
+    const double c = sxy * inv - mean[0] * mean[1];
+    double *mu = raw + M + (size_t)m * Dj, *cv = raw + M + (size_t)M * Dj + (size_t)m * (Dj + D);
+    mu[tid] = mean[0];
+    mu[tid + D] = mean[1];
+    cv[tid] = v[0];
+    cv[tid + D] = v[1];
+    cv[tid + Dj] = c;
+    if (!bdiag_pair_valid(v[0], v[1], c)) atomicMin(ctl + 1, 1 + tid + D * m);
   }
 }
 
@@ -303,5 +349,110 @@ extern "C" int vcmi_gmm_em_diag_get(vcmi_gmm_em_diag *h, double *w, double *mu, 
   VCMI_HIP(hipMemcpy(w, h->params(), sizeof(double) * h->M, hipMemcpyDeviceToHost));
   VCMI_HIP(hipMemcpy(mu, h->params() + h->M, sizeof(double) * md, hipMemcpyDeviceToHost));
   VCMI_HIP(hipMemcpy(var, h->params() + h->M + md, sizeof(double) * md, hipMemcpyDeviceToHost));
+  return VCMI_OK;
+}
+
+// ---- device-resident cross-diagonal EM state -----------------------------------------------------
+// As vcmi_gmm_em_diag: two parameter blocks [w | mu (Dj,M) | covars (Dj + D, M)], the M-step kernel writes the one the E-step
+// does not read, and a failed M-step leaves the parameters its statistics were computed under.
+struct vcmi_gmm_em_bdiag {
+  int Dj = 0, M = 0, device = 0, cur = 0;
+  double min_covar = 0.0;
+  bool failed = false;           // an M-step reported a pair: the state takes no further E-step
+  int bad = 0;                   // ... 1 + d + D m of that pair
+  vcmi::DevBuf<double> raw;      // 2 x M (1 + 2 Dj + D)
+  vcmi::DevBuf<int> ctl;         // [latch | smallest bad index (INT_MAX: none) | loglik (a double) | the E-step preparation's report]
+  size_t nraw() const { return (size_t)M * (1 + 2 * (size_t)Dj + Dj / 2); }
+  double *params() { return raw.p + (size_t)cur * nraw(); }
+  int not_pd() const {
+    const int D = Dj / 2;
+    return vcmi::fail(VCMI_ERR_NOT_PD, "M-step: pair (%d,%d) is not positive definite", (bad - 1) % D + 1, (bad - 1) / D + 1);
+  }
+};
+
+extern "C" int vcmi_gmm_em_bdiag_create(int Dj, int M, const double *w, const double *mu, const double *covars, double min_covar,
+                                        vcmi_gmm_em_bdiag **out) {
+  if (!w || !mu || !covars || !out) return fail(VCMI_ERR_ARG, "vcmi_gmm_em_bdiag_create: NULL argument");
+  *out = nullptr;
+  VCMI_TRY(estep_bdiag_check_dims("vcmi_gmm_em_bdiag_create", Dj, M));
+  if (!(min_covar >= 0.0)) return fail(VCMI_ERR_ARG, "vcmi_gmm_em_bdiag_create: min_covar must be >= 0");
+  const int D = Dj / 2;
+  const int64_t bad = first_bad_pair(covars, Dj, M);
+  if (bad >= 0)
+    return fail(VCMI_ERR_NOT_PD, "vcmi_gmm_em_bdiag_create: pair (%d,%d) is not positive definite", (int)(bad % D) + 1, (int)(bad / D) + 1);
+  VCMI_TRY(check_device());
+  vcmi_gmm_em_bdiag *h = new (std::nothrow) vcmi_gmm_em_bdiag();
+  if (!h) return fail(VCMI_ERR_OOM, "out of host memory");
+  h->Dj = Dj;
+  h->M = M;
+  h->min_covar = min_covar;
+  (void)hipGetDevice(&h->device);
+  int rc = h->raw.alloc(2 * h->nraw());
+  if (rc == VCMI_OK) rc = h->ctl.alloc(6);
+  if (rc != VCMI_OK) {
+    delete h;
+    return rc;
+  }
+  const int ctl0[6] = {0, INT32_MAX, 0, 0, INT32_MAX, 0};
+  const size_t md = (size_t)M * Dj;
+  hipError_t e = upload_now_hip(h->raw.p, w, sizeof(double) * M);
+  if (e == hipSuccess) e = upload_now_hip(h->raw.p + M, mu, sizeof(double) * md);
+  if (e == hipSuccess) e = upload_now_hip(h->raw.p + M + md, covars, sizeof(double) * M * (Dj + D));
+  if (e == hipSuccess) e = upload_now_hip(h->ctl.p, ctl0, sizeof(ctl0));
+  if (e != hipSuccess) {
+    delete h;
+    return fail(VCMI_ERR_HIP, "vcmi_gmm_em_bdiag_create: %s", hipGetErrorString(e));
+  }
+  *out = h;
+  return VCMI_OK;
+}
+
+extern "C" int vcmi_gmm_em_bdiag_destroy(vcmi_gmm_em_bdiag *h) {
+  delete h;
+  return VCMI_OK;
+}
+
+extern "C" int vcmi_gmm_em_bdiag_estep_dev(vcmi_gmm_em_bdiag *h, const double *dX, int64_t N, double *dstats, void *stream) {
+  if (!h || !dstats) return fail(VCMI_ERR_ARG, "vcmi_gmm_em_bdiag_estep_dev: NULL argument");
+  if (N < 0 || (N > 0 && !dX)) return fail(VCMI_ERR_ARG, "vcmi_gmm_em_bdiag_estep_dev: bad frame block");
+  if (h->failed) return h->not_pd();
+  // (the pairs of the block are positive definite: vcmi_gmm_em_bdiag_create and every M-step since have checked them)
+  return estep_bdiag_device_block(dX, N, h->Dj, h->M, h->params(), h->ctl.p + 4, dstats, as_stream(stream));
+}
+
+extern "C" int vcmi_gmm_em_bdiag_mstep(vcmi_gmm_em_bdiag *h, const double *dstats, void *stream, double *loglik) {
+  if (!h || !dstats) return fail(VCMI_ERR_ARG, "vcmi_gmm_em_bdiag_mstep: NULL argument");
+  hipStream_t st = as_stream(stream);
+  double *next = h->raw.p + (size_t)(1 - h->cur) * h->nraw();
+  hipLaunchKernelGGL(em_mstep_bdiag_kernel, dim3(h->M), dim3(256), 0, st, dstats, h->Dj, h->M, h->min_covar, next, h->ctl.p);
+  VCMI_HIP(hipGetLastError());
+  struct {
+    int latch, bad;
+    double ll;
+  } r = {0, 0, 0.0};
+  static_assert(sizeof(r) == 16, "the control block starts with two ints and a double");
+  VCMI_HIP(hipMemcpyAsync(&r, h->ctl.p, sizeof(r), hipMemcpyDeviceToHost, st));
+  VCMI_HIP(hipStreamSynchronize(st));
+  if (loglik) *loglik = r.ll;
+  if (r.bad != INT32_MAX) {
+    if (!h->failed) {      // latch it on the device too: a later M-step kernel returns before it writes
+      const int one = 1;
+      VCMI_HIP(hipMemcpy(h->ctl.p, &one, sizeof(int), hipMemcpyHostToDevice));
+    }
+    h->failed = true;
+    h->bad = r.bad;
+    return h->not_pd();
+  }
+  h->cur = 1 - h->cur;
+  return VCMI_OK;
+}
+
+extern "C" int vcmi_gmm_em_bdiag_get(vcmi_gmm_em_bdiag *h, double *w, double *mu, double *covars) {
+  if (!h || !w || !mu || !covars) return fail(VCMI_ERR_ARG, "vcmi_gmm_em_bdiag_get: NULL argument");
+  VCMI_HIP(hipDeviceSynchronize());
+  const size_t md = (size_t)h->M * h->Dj;
+  VCMI_HIP(hipMemcpy(w, h->params(), sizeof(double) * h->M, hipMemcpyDeviceToHost));
+  VCMI_HIP(hipMemcpy(mu, h->params() + h->M, sizeof(double) * md, hipMemcpyDeviceToHost));
+  VCMI_HIP(hipMemcpy(covars, h->params() + h->M + md, sizeof(double) * h->M * (h->Dj + h->Dj / 2), hipMemcpyDeviceToHost));
   return VCMI_OK;
 }

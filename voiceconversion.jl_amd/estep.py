@@ -118,6 +118,48 @@ def mstep_diag(S0, S1, S2, min_covar=1e-7):
     return w, mu, var
 
 
+# ------------------------------------------------------------------------------- cross-diagonal ("block_diag")
+def bdiag_stats_len(Dj, M):
+    return int(_lib.lib.vcmi_estep_bdiag_stats_len(int(Dj), int(M)))
+
+
+def _params_bdiag(w, mu, covars):
+    w = jl_vector(w)
+    mu = jl_matrix(mu, "mu")
+    covars = jl_matrix(covars, "covars")
+    Dj, M = mu.shape
+    if Dj % 2:
+        raise _lib.DimensionMismatch(f"block_diag: the joint dimension must be even, got {Dj}")
+    if covars.shape != (Dj + Dj // 2, M) or w.shape != (M,):
+        raise _lib.DimensionMismatch(f"w {w.shape}, mu {mu.shape}, block_diag covars {covars.shape} are inconsistent")
+    return w, mu, covars, Dj, M
+
+
+def unpack_bdiag_stats(stats, Dj, M):
+    """[S0 | S1 | S2 | Sxy | loglik] -> (S0 (M,), S1 (Dj,M), S2 (Dj,M), Sxy (Dj/2,M), loglik); numpy or torch buffers."""
+    D, a = Dj // 2, M + 2 * M * Dj
+    S0, S1, S2, _ = unpack_stats(stats, Dj, M)
+    return S0, S1, S2, stats[a:a + M * D].reshape(M, D).T, stats[a + M * D]
+
+
+def estep_bdiag_dev(X, w, mu, covars, out=None):
+    """Device-resident E-step of the cross-diagonal model (include/vcmi.h): X is a dense (Dj,N) torch tensor, covars
+    (Dj + Dj/2, M) = [variances; cross-covariances of the pairs (d, d + Dj/2)].  Returns the packed statistics as a device
+    tensor of bdiag_stats_len(Dj,M) doubles."""
+    return _estep_dev(_lib.lib.vcmi_estep_bdiag_dev, bdiag_stats_len, _params_bdiag(w, mu, covars), X, out)
+
+
+def mstep_bdiag(S0, S1, S2, Sxy, min_covar=1e-7):
+    """M-step of the cross-diagonal model from its E-step statistics: mstep_diag's weights, means and variances, and
+    c = Sxy / S0 - mu_d mu_{d+D} (min_covar on variances only).  Returns w, mu (Dj,M), covars (Dj + Dj/2, M); float64, the
+    operations and their order are those of em_mstep_bdiag_kernel."""
+    w, mu, var = mstep_diag(S0, S1, S2, min_covar)
+    D = mu.shape[0] // 2
+    inv = 1.0 / (np.asarray(S0) + 10 * np.finfo(np.float64).eps)
+    c = Sxy * inv[None, :] - mu[:D] * mu[D:]
+    return w, mu, np.vstack([var, c])
+
+
 # ----------------------------------------------------------------------------------------- full covariance
 def full_stats_len(Dj, M):
     return int(_lib.lib.vcmi_estep_full_stats_len(int(Dj), int(M)))

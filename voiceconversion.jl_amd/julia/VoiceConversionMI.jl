@@ -24,7 +24,7 @@ export DeviceMatrix, FrameByFrameConverter, TrajectoryConverter, GMMMapParam, GM
        align, align_mcep, push_delta, GVDataset, sp2mc, mc2sp, mc2b,
        DTW, fit!, update!, set_template!, backward,
        predict_proba, predict_proba!, predict, predict!, diffgmm,
-       estep_diag, estep_full, estep_set_path, estep_get_path, ESTEP_AUTO, ESTEP_HARD, ESTEP_SOFT, GMMEM, GMMEMDiag, estep!, mstep!, params, KMeansState, kmeans_stats_len, kmeans_assign!, kmeans_update!, kmeans_far!,
+       estep_diag, estep_full, estep_set_path, estep_get_path, ESTEP_AUTO, ESTEP_HARD, ESTEP_SOFT, GMMEM, GMMEMDiag, GMMEMBlockDiag, bdiag_stats_len, estep!, mstep!, params, KMeansState, kmeans_stats_len, kmeans_assign!, kmeans_update!, kmeans_far!,
        kmeans_relocate!, kmeans_seed_commit!, kmeans_seed_pick, kmeans_seed_trials!, kmeans_mind2!, kmeans_restore_best!, kmeans_centers,
        kmeans!, set_devices, device_count, set_prune!, convert_plan, pin!, unpin!, ispinned
 
@@ -853,6 +853,46 @@ function params(em::GMMEMDiag)
     w = Vector{Float64}(undef, em.M); μ = Matrix{Float64}(undef, em.Dj, em.M); σ² = Matrix{Float64}(undef, em.Dj, em.M)
     check(ccall((:vcmi_gmm_em_diag_get, libvcmi), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}), em.h, w, μ, σ²))
     w, μ, σ²
+end
+
+# The cross-diagonal twin (covariance_type="block_diag"): Dj even, D = Dj ÷ 2, Σ is (Dj + D, M) = [variances; cross-covariances
+# of the pairs (d, d + D)]; `dstats` holds vcmi_estep_bdiag_stats_len(Dj,M) doubles.
+mutable struct GMMEMBlockDiag
+    h::Ptr{Cvoid}
+    Dj::Int
+    M::Int
+    function GMMEMBlockDiag(w::Vector{Float64}, μ::Matrix{Float64}, Σ::Matrix{Float64}; min_covar::Float64=1.0e-7)
+        Dj, M = size(μ)
+        iseven(Dj) || throw(DimensionMismatch("the joint dimension must be even"))
+        size(Σ) == (Dj + Dj ÷ 2, M) || throw(DimensionMismatch("Σ must be (Dj + Dj/2, M)"))
+        length(w) == M || throw(DimensionMismatch("w must have M entries"))
+        h = Ref{Ptr{Cvoid}}(C_NULL)
+        check(ccall((:vcmi_gmm_em_bdiag_create, libvcmi), Cint,
+                    (Cint, Cint, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Cdouble, Ref{Ptr{Cvoid}}),
+                    Dj, M, w, μ, Σ, min_covar, h))
+        em = new(h[], Dj, M)
+        finalizer(e -> ccall((:vcmi_gmm_em_bdiag_destroy, libvcmi), Cint, (Ptr{Cvoid},), e.h), em)
+        em
+    end
+end
+
+bdiag_stats_len(Dj::Integer, M::Integer) = ccall((:vcmi_estep_bdiag_stats_len, libvcmi), Int64, (Cint, Cint), Dj, M)
+
+estep!(em::GMMEMBlockDiag, dX::Ptr{Float64}, N::Integer, dstats::Ptr{Float64}; stream::Ptr{Cvoid}=C_NULL) =
+    check(ccall((:vcmi_gmm_em_bdiag_estep_dev, libvcmi), Cint, (Ptr{Cvoid}, Ptr{Float64}, Int64, Ptr{Float64}, Ptr{Cvoid}),
+                em.h, dX, N, dstats, stream))
+
+function mstep!(em::GMMEMBlockDiag, dstats::Ptr{Float64}; stream::Ptr{Cvoid}=C_NULL)
+    ll = Ref{Float64}(0.0)
+    check(ccall((:vcmi_gmm_em_bdiag_mstep, libvcmi), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Cvoid}, Ref{Float64}),
+                em.h, dstats, stream, ll))
+    ll[]
+end
+
+function params(em::GMMEMBlockDiag)
+    w = Vector{Float64}(undef, em.M); μ = Matrix{Float64}(undef, em.Dj, em.M); Σ = Matrix{Float64}(undef, em.Dj + em.Dj ÷ 2, em.M)
+    check(ccall((:vcmi_gmm_em_bdiag_get, libvcmi), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}), em.h, w, μ, Σ))
+    w, μ, Σ
 end
 
 # ------------------------------------------------------------------------------------- device k-means

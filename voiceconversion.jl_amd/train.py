@@ -18,6 +18,14 @@ covariance_type="diag" runs the same loop on a diagonal model (DiagEMState, vcmi
 M(1+2Dj)+1 doubles of the diagonal E-step, the initial variances the diagonal of the data covariance + min_covar (what the
 old sklearn GMM takes for "diag") -- for init="kmeans" from the M=1 DIAGONAL E-step statistics (N, sum x, sum x^2), not
 the Dj^2 pass.  expand_diag turns its variances into the (Dj,Dj,M) tensor that refine= of the full fit takes.
+
+covariance_type="block_diag" is the cross-diagonal joint model GMM voice conversion is usually trained with (Toda, Black and
+Tokuda 2007): Dj is even, D = Dj/2, dimension d couples with dimension d + D only.  BlockDiagEMState (vcmi_gmm_em_bdiag_*)
+keeps covars (Dj + D, M) = [variances; cross-covariances c_dm]; the statistics are the M(1 + 2Dj + D) + 1 doubles of the
+block-diagonal E-step, the initial covariances the variances and pair covariances of the data + min_covar on the variances --
+for init="kmeans" from the M=1 block-diagonal E-step statistics (data_block_covariance).  expand_block_diag gives the
+(Dj,Dj,M) tensor that GMMMap and refine= of the full fit take; TrajectoryGMMMap(precision="diag") converts with such a model
+exactly.
 """
 import ctypes as C
 
@@ -25,7 +33,8 @@ import numpy as np
 
 from . import _lib
 from ._arrays import current_stream_ptr, jl_matrix, jl_vector
-from .estep import _dense_frames, estep_diag_dev, estep_full_dev, full_stats_len, stats_len, unpack_full_stats, unpack_stats
+from .estep import (_dense_frames, bdiag_stats_len, estep_bdiag_dev, estep_diag_dev, estep_full_dev, full_stats_len, stats_len,
+                    unpack_bdiag_stats, unpack_full_stats, unpack_stats)
 from .kmeans import kmeans
 
 
@@ -107,6 +116,39 @@ class DiagEMState(_EMState):
         self._create(w, mu, var, "var", min_covar)
 
 
+class BlockDiagEMState(_EMState):
+    """Device-resident (w, mu, covars) of a cross-diagonal GMM (vcmi_gmm_em_bdiag_*): mu (Dj,M), covars (Dj + Dj/2, M) =
+    [variances; cross-covariances of the pairs (d, d + Dj/2)]."""
+    _entries = (_lib.lib.vcmi_gmm_em_bdiag_create, _lib.lib.vcmi_gmm_em_bdiag_destroy, _lib.lib.vcmi_gmm_em_bdiag_estep_dev,
+                _lib.lib.vcmi_gmm_em_bdiag_mstep, _lib.lib.vcmi_gmm_em_bdiag_get)
+    _stats_len = staticmethod(bdiag_stats_len)
+
+    @staticmethod
+    def _third_shape(Dj, M):
+        return (Dj + Dj // 2, M)
+
+    def __init__(self, w, mu, covars, min_covar=1e-7):
+        if np.ndim(mu) == 2 and np.shape(mu)[0] % 2:
+            raise _lib.DimensionMismatch(f"block_diag: the joint dimension must be even, got {np.shape(mu)[0]}")
+        self._create(w, mu, covars, "block_diag covars", min_covar)
+
+
+def expand_block_diag(covars):
+    """covars (Dj + D, M) of a cross-diagonal model -> the (Dj,Dj,M) covariance tensor: the variances on the diagonals, c at
+    (d, d + D) and (d + D, d).  What GMMMap and train_gmm(X, refine=(w, mu, expand_block_diag(covars))) take."""
+    v = np.asarray(covars, dtype=np.float64)
+    if v.ndim != 2 or v.shape[0] % 3:
+        raise _lib.DimensionMismatch(f"expand_block_diag: covars must be (Dj + Dj/2, M), got {v.shape}")
+    D, M = v.shape[0] // 3, v.shape[1]
+    Dj = 2 * D
+    out = np.zeros((Dj, Dj, M), order="F")
+    i, d = np.arange(Dj), np.arange(D)
+    out[i, i, :] = v[:Dj]
+    out[d, d + D, :] = v[Dj:]
+    out[d + D, d, :] = v[Dj:]
+    return out
+
+
 def expand_diag(covars):
     """Variances (Dj,M) -> the (Dj,Dj,M) covariance tensor with them on the diagonals:
     train_gmm(X, refine=(w, mu, expand_diag(var))) warm-starts the full-covariance fit from a diagonal one."""
@@ -168,6 +210,21 @@ def data_variance(X, group=None):
     return (S2[:, 0] - s1 * s1 / n) / (n - 1.0)
 
 
+def data_block_covariance(X, group=None):
+    """The (Dj + D,) variances and pair covariances cov(z_d, z_{d+D}) (ddof=1) over every frame of every rank, from the M=1
+    block-diagonal E-step statistics (N, sum z, sum z^2, sum z_d z_{d+D})."""
+    import torch.distributed as dist
+
+    Dj = X.shape[0]
+    D = Dj // 2
+    st = estep_bdiag_dev(X, np.ones(1), np.zeros((Dj, 1)), np.vstack([np.ones((Dj, 1)), np.zeros((D, 1))]))
+    if dist.is_available() and dist.is_initialized():
+        dist.all_reduce(st, group=group)
+    S0, S1, S2, Sxy, _ = unpack_bdiag_stats(st.cpu().numpy(), Dj, 1)
+    n, s1 = S0[0], S1[:, 0]
+    return np.concatenate([S2[:, 0] - s1 * s1 / n, Sxy[:, 0] - s1[:D] * s1[D:] / n]) / (n - 1.0)
+
+
 def train_gmm(X, n_components=16, n_iter=200, n_init=2, min_covar=1e-7, tol=1e-3, refine=None, seed=0, group=None,
               init_sample=50000, init="subsample", covariance_type="full"):
     """train_gmm.jl's `gmm[:fit]`: X is this rank's (Dj,N) device-resident shard of the joint features.
@@ -182,12 +239,16 @@ def train_gmm(X, n_components=16, n_iter=200, n_init=2, min_covar=1e-7, tol=1e-3
     covariance_type="diag" fits a diagonal model by the same rules (module docstring): refine=(w, mu, var (Dj,M)), the
     variances start from the diagonal of the data covariance + min_covar, "covars" is (Dj,M) and the result carries
     "covariance_type": "diag".
+    covariance_type="block_diag" fits the cross-diagonal model (module docstring; Dj even): refine=(w, mu, covars (Dj + Dj/2, M)),
+    "covars" is (Dj + Dj/2, M) = [variances; pair cross-covariances] and the result carries "covariance_type": "block_diag".
     """
-    if covariance_type not in ("full", "diag"):
-        raise ValueError(f"train_gmm: covariance_type must be 'full' or 'diag', got {covariance_type!r}")
+    if covariance_type not in ("full", "diag", "block_diag"):
+        raise ValueError(f"train_gmm: covariance_type must be 'full', 'diag' or 'block_diag', got {covariance_type!r}")
     diag = covariance_type == "diag"
     Dj, N = X.shape
     M = int(n_components)
+    if covariance_type == "block_diag":
+        return _train_gmm_block_diag(X, M, n_iter, n_init, min_covar, tol, refine, seed, group, init_sample, init)
     if diag and refine is not None and np.shape(refine[2]) != (Dj, M):
         raise _lib.DimensionMismatch(f"train_gmm: covariance_type='diag' refines from variances ({Dj},{M}), got {np.shape(refine[2])}")
 
@@ -259,4 +320,71 @@ def train_gmm(X, n_components=16, n_iter=200, n_init=2, min_covar=1e-7, tol=1e-3
     return out
 
 
-__all__ = ["EMState", "DiagEMState", "train_gmm", "expand_diag", "kmeans_init", "data_covariance", "data_variance", "unpack_full_stats"]
+def _train_gmm_block_diag(X, M, n_iter, n_init, min_covar, tol, refine, seed, group, init_sample, init):
+    """train_gmm for covariance_type="block_diag": the rules of the other two types on BlockDiagEMState."""
+    import torch
+    import torch.distributed as dist
+
+    Dj, N = X.shape
+    if Dj % 2:
+        raise _lib.DimensionMismatch(f"train_gmm: covariance_type='block_diag' needs an even joint dimension, got {Dj}")
+    D = Dj // 2
+    if refine is not None and np.shape(refine[2]) != (Dj + D, M):
+        raise _lib.DimensionMismatch(f"train_gmm: covariance_type='block_diag' refines from covars ({Dj + D},{M}), got {np.shape(refine[2])}")
+    if init not in ("subsample", "kmeans"):
+        raise ValueError(f"train_gmm: init must be 'subsample' or 'kmeans', got {init!r}")
+    distributed = dist.is_available() and dist.is_initialized()
+    rank = dist.get_rank(group) if distributed else 0
+    ntot = torch.tensor([float(N)], dtype=torch.float64, device=X.device)
+    if distributed:
+        dist.all_reduce(ntot, group=group)
+    ntot = float(ntot.item())
+    rng = np.random.default_rng(seed)
+    floor = np.concatenate([np.full(Dj, float(min_covar)), np.zeros(D)])        # min_covar on variances only
+    cv_all = data_block_covariance(X, group) + floor if init == "kmeans" and refine is None else None
+    best = None
+    for _ in range(1 if refine is not None else max(1, int(n_init))):
+        if refine is not None:
+            w0, mu0, cv0 = refine
+        elif init == "kmeans":
+            # every rank runs the same collective k-means and gets the same centers: nothing to broadcast
+            mu0 = kmeans(X, M, seed=int(rng.integers(2**31 - 1)), group=group)["centers"]
+            cv0 = np.repeat(cv_all[:, None], M, axis=1)
+            w0 = np.full(M, 1.0 / M)
+        else:
+            # rank 0 draws the initial model from its shard and every rank receives the same one
+            pk = torch.empty(M * (1 + 2 * Dj + D), dtype=torch.float64, device=X.device)
+            if rank == 0:
+                idx = rng.choice(N, size=min(N, int(init_sample)), replace=False)
+                Xs = X[:, torch.from_numpy(np.sort(idx)).to(X.device)].t().contiguous().cpu().numpy()
+                mu0 = kmeans_init(Xs, M, rng).T
+                Xc = Xs - Xs.mean(axis=0)
+                pair = (Xc[:, :D] * Xc[:, D:]).sum(axis=0) / (len(Xs) - 1.0)
+                cv0 = np.repeat((np.concatenate([np.var(Xs, axis=0, ddof=1), pair]) + floor)[:, None], M, axis=1)
+                w0 = np.full(M, 1.0 / M)
+                pk.copy_(torch.from_numpy(np.concatenate([w0, mu0.T.ravel(), cv0.T.ravel()])))
+            if distributed:
+                dist.broadcast(pk, src=0, group=group)
+            h = pk.cpu().numpy()
+            w0 = h[:M].copy()
+            mu0 = h[M:M + M * Dj].reshape(M, Dj).T
+            cv0 = h[M + M * Dj:].reshape(M, Dj + D).T
+        em = BlockDiagEMState(w0, mu0, cv0, min_covar)
+        stats = torch.empty(bdiag_stats_len(Dj, M), dtype=torch.float64, device=X.device)
+        hist, converged = [], False
+        for _ in range(int(n_iter)):
+            em.estep(X, out=stats)
+            if distributed:
+                dist.all_reduce(stats, group=group)
+            hist.append(em.mstep(stats) / ntot)
+            if len(hist) > 1 and abs(hist[-1] - hist[-2]) < tol:
+                converged = True
+                break
+        if best is None or hist[-1] > best[0]:
+            best = (hist[-1], em.get(), hist, converged)
+    (w, mu, covars), hist, converged = best[1], best[2], best[3]
+    return {"weights": w, "means": mu, "covars": covars, "n_components": M, "loglik": hist, "converged": converged,
+            "covariance_type": "block_diag"}
+
+
+__all__ = ["EMState", "DiagEMState", "BlockDiagEMState", "train_gmm", "expand_diag", "expand_block_diag", "data_block_covariance", "kmeans_init", "data_covariance", "data_variance", "unpack_full_stats"]
