@@ -4,12 +4,38 @@
 // bin/train_gmm.jl:84-103 (sklearn.mixture.GMM(covariance_type="full", min_covar).fit): parameters, statistics and
 // whitening blocks stay in HBM; one iteration is
 //   estep (local statistics) -> [caller all-reduces the statistics buffer over RCCL] -> mstep (+ whitening prep).
-// The E-steps are those of estep_full.hip, estep.hip and estep_bdiag.hip (estep_internal.hpp); the M-step kernels are here.
+// The E-steps are those of estep_full.hip, estep.hip and estep_bdiag.hip (estep_internal.hpp); the M-step kernels are here,
+// and open with one helper (mstep_weight).
+// Two kinds of state.  vcmi_gmm_em (full covariance) has one parameter block, a p(x) handle and a flag that the whitening
+// preparation reads.  vcmi_gmm_em_diag and vcmi_gmm_em_bdiag are two opaque names of ONE two-block state (Em2State): create,
+// the M-step's host side (launch, the 16-byte read of {latch, report, loglik}, the latch, the swap of the blocks), get and the
+// guard in front of the E-step are written once (em2_*), and a type supplies an Em2Kind -- its dimension check, host validity
+// scan, third-parameter length, control words, M-step kernel, E-step call and the unit its report names.
 #include "estep_internal.hpp"
 #include "gmmmap_handle.hpp"
 #include "hostpipe.hpp"
 
 namespace vcmi {
+
+// The opening of the three M-step kernels, called by every thread of the 256-thread workgroup of mixture m: the total of S0
+// over M in a fixed order (256 strided partial sums in `red`, an 8-level tree -- no floating-point atomics), then
+// *inv = 1 / (S0[m] + 10 eps) and the return value, the weight S0[m] / (total + 10 eps) + eps.  Sums and quotients only:
+// nothing here that a compiler could contract, inside or outside an `fp contract(off)` scope.
+__device__ inline double mstep_weight(const double *__restrict__ stats, int M, int m, double *red, double *inv) {
+  const int tid = threadIdx.x;
+  const double eps = 2.220446049250313e-16;
+  double t = 0.0;
+  for (int k = tid; k < M; k += 256) t += stats[k];
+  red[tid] = t;
+  __syncthreads();
+  for (int o = 128; o >= 1; o >>= 1) {
+    if (tid < o) red[tid] += red[tid + o];
+    __syncthreads();
+  }
+  const double tot = red[0], s0 = stats[m];
+  *inv = 1.0 / (s0 + 10 * eps);
+  return s0 / (tot + 10 * eps) + eps;
+}
 
 __global__ void __launch_bounds__(256)
 em_mstep_full_kernel(const double *__restrict__ stats, int Dj, int M, double min_covar, double *__restrict__ w,
@@ -21,17 +47,8 @@ em_mstep_full_kernel(const double *__restrict__ stats, int Dj, int M, double min
   // for every mixture.  Keep the parameters, so that the preparation that follows reports the same mixture again (and not
   // the last one of a model that is NaN throughout) and vcmi_gmm_em_get still shows the model that failed.
   if (*flag) return;
-  const double eps = 2.220446049250313e-16;
-  double t = 0.0;
-  for (int k = tid; k < M; k += 256) t += stats[k];
-  red[tid] = t;
-  __syncthreads();
-  for (int o = 128; o >= 1; o >>= 1) {
-    if (tid < o) red[tid] += red[tid + o];
-    __syncthreads();
-  }
-  const double tot = red[0], s0 = stats[m];
-  const double inv = 1.0 / (s0 + 10 * eps);
+  double inv;
+  const double wm = mstep_weight(stats, M, m, red, &inv);
   const double *S1 = stats + M + (size_t)m * Dj;
   const double *S2 = stats + M + (size_t)M * Dj + (size_t)m * Dj * Dj;
   for (int d = tid; d < Dj; d += 256) {
@@ -39,7 +56,7 @@ em_mstep_full_kernel(const double *__restrict__ stats, int Dj, int M, double min
     mus[d] = v;
     mu[(size_t)m * Dj + d] = v;
   }
-  if (tid == 0) w[m] = s0 / (tot + 10 * eps) + eps;
+  if (tid == 0) w[m] = wm;
   __syncthreads();
   for (int e = tid; e < Dj * Dj; e += 256) {
     const int c = e / Dj, r = e - c * Dj;
@@ -63,18 +80,9 @@ em_mstep_diag_kernel(const double *__restrict__ stats, int Dj, int M, double min
   const int tid = threadIdx.x, m = blockIdx.x;
   if (m == 0 && tid == 0) *reinterpret_cast<double *>(ctl + 2) = stats[(size_t)M * (1 + 2 * (size_t)Dj)];
   if (ctl[0]) return;
-  const double eps = 2.220446049250313e-16;
-  double t = 0.0;
-  for (int k = tid; k < M; k += 256) t += stats[k];
-  red[tid] = t;
-  __syncthreads();
-  for (int o = 128; o >= 1; o >>= 1) {
-    if (tid < o) red[tid] += red[tid + o];
-    __syncthreads();
-  }
-  const double tot = red[0], s0 = stats[m];
-  const double inv = 1.0 / (s0 + 10 * eps);
-  if (tid == 0) raw[m] = s0 / (tot + 10 * eps) + eps;
+  double inv;
+  const double wm = mstep_weight(stats, M, m, red, &inv);
+  if (tid == 0) raw[m] = wm;
   if (tid < Dj) {
     const size_t e = (size_t)m * Dj + tid;
     const double s1 = stats[M + e], s2 = stats[M + (size_t)M * Dj + e];
@@ -99,18 +107,9 @@ em_mstep_bdiag_kernel(const double *__restrict__ stats, int Dj, int M, double mi
   const int tid = threadIdx.x, m = blockIdx.x, D = Dj / 2;
   if (m == 0 && tid == 0) *reinterpret_cast<double *>(ctl + 2) = stats[(size_t)M * (1 + 2 * (size_t)Dj + D)];
   if (ctl[0]) return;
-  const double eps = 2.220446049250313e-16;
-  double t = 0.0;
-  for (int k = tid; k < M; k += 256) t += stats[k];
-  red[tid] = t;
-  __syncthreads();
-  for (int o = 128; o >= 1; o >>= 1) {
-    if (tid < o) red[tid] += red[tid + o];
-    __syncthreads();
-  }
-  const double tot = red[0], s0 = stats[m];
-  const double inv = 1.0 / (s0 + 10 * eps);
-  if (tid == 0) raw[m] = s0 / (tot + 10 * eps) + eps;
+  double inv;
+  const double wm = mstep_weight(stats, M, m, red, &inv);
+  if (tid == 0) raw[m] = wm;
   if (tid < D) {
     const double *S1 = stats + M + (size_t)m * Dj, *S2 = stats + M + (size_t)M * Dj + (size_t)m * Dj;
     const double sxy = stats[M + 2 * (size_t)M * Dj + (size_t)m * D + tid];
@@ -171,23 +170,164 @@ static int em_prepare(vcmi_gmm_em *h, hipStream_t st) {
 }
 }  // namespace vcmi
 
-// The diagonal EM state.  `raw` holds TWO parameter blocks [w | mu (Dj,M) | var (Dj,M)]: the E-step reads block `cur`, the M-step
-// kernel writes the other one, and vcmi_gmm_em_diag_mstep -- which synchronises anyway -- makes that one current only when no
-// variance was reported.  So a failed M-step leaves the parameters its statistics were computed under, whichever workgroup
-// found the variance and whichever had already written.
-struct vcmi_gmm_em_diag {
+// ---- the two-block state: diagonal and cross-diagonal -----------------------------------------------
+// `raw` holds TWO parameter blocks [w | mu (Dj,M) | third], third = var (Dj,M) or covars (Dj + D, M): the E-step reads block
+// `cur`, the M-step kernel writes the other one, and em2_mstep -- which synchronises anyway -- makes that one current only when
+// nothing was reported.  So a failed M-step leaves the parameters its statistics were computed under, whichever workgroup
+// found the variance or pair and whichever had already written.
+namespace vcmi {
+
+// What a covariance type supplies.  A report counts in `units` per mixture (dimensions or pairs): index u + units m.
+struct Em2Kind {
+  int (*check_dims)(const char *who, int Dj, int M);
+  int64_t (*first_bad)(const double *third, int Dj, int M);   // the host validity scan: index of the first bad unit, -1: none
+  int (*third_len)(int Dj);                                   // doubles of the third parameter per mixture
+  int (*units)(int Dj);
+  int (*not_valid)(const char *who, int u, int m);            // VCMI_ERR_NOT_PD naming unit (u, m), 1-based
+  int nctl;   // control words: [latch | smallest bad 1 + index (INT_MAX: none) | loglik (a double)], then the E-step's own
+  void (*mstep_kernel)(const double *stats, int Dj, int M, double min_covar, double *raw, int *ctl);
+  int (*estep)(const double *dX, int64_t N, int Dj, int M, const double *dparams, int *ctl, double *dstats, hipStream_t st);
+};
+
+struct Em2State {
+  const Em2Kind *kind = nullptr;
   int Dj = 0, M = 0, device = 0, cur = 0;
   double min_covar = 0.0;
-  bool failed = false;           // an M-step reported a variance: the state takes no further E-step
-  int bad = 0;                   // ... 1 + d + Dj m of that variance
-  vcmi::DevBuf<double> raw;      // 2 x M (1 + 2 Dj)
-  vcmi::DevBuf<int> ctl;         // [latch | smallest bad index (INT_MAX: none) | loglik (a double)]
-  size_t nraw() const { return (size_t)M * (1 + 2 * (size_t)Dj); }
+  bool failed = false;           // an M-step reported a unit: the state takes no further E-step
+  int bad = 0;                   // ... 1 + u + units m of that unit
+  DevBuf<double> raw;            // 2 x nraw()
+  DevBuf<int> ctl;               // kind->nctl words
+  size_t nthird() const { return (size_t)M * kind->third_len(Dj); }
+  size_t nraw() const { return (size_t)M * (1 + (size_t)Dj) + nthird(); }
   double *params() { return raw.p + (size_t)cur * nraw(); }
+  double *next() { return raw.p + (size_t)(1 - cur) * nraw(); }
   int not_pd() const {
-    return vcmi::fail(VCMI_ERR_NOT_PD, "M-step: variance (%d,%d) is not positive", (bad - 1) % Dj + 1, (bad - 1) / Dj + 1);
+    const int U = kind->units(Dj);
+    return kind->not_valid("M-step", (bad - 1) % U + 1, (bad - 1) / U + 1);
   }
 };
+
+// H: the opaque handle type of the entry, an Em2State and nothing more
+template <class H>
+static int em2_create(const Em2Kind &k, const char *who, int Dj, int M, const double *w, const double *mu, const double *third,
+                      double min_covar, H **out) {
+  if (!w || !mu || !third || !out) return fail(VCMI_ERR_ARG, "%s: NULL argument", who);
+  *out = nullptr;
+  VCMI_TRY(k.check_dims(who, Dj, M));
+  if (!(min_covar >= 0.0)) return fail(VCMI_ERR_ARG, "%s: min_covar must be >= 0", who);
+  const int64_t bad = k.first_bad(third, Dj, M);
+  if (bad >= 0) return k.not_valid(who, (int)(bad % k.units(Dj)) + 1, (int)(bad / k.units(Dj)) + 1);
+  VCMI_TRY(check_device());
+  H *h = new (std::nothrow) H();
+  if (!h) return fail(VCMI_ERR_OOM, "out of host memory");
+  h->kind = &k;
+  h->Dj = Dj;
+  h->M = M;
+  h->min_covar = min_covar;
+  (void)hipGetDevice(&h->device);
+  int rc = h->raw.alloc(2 * h->nraw());
+  if (rc == VCMI_OK) rc = h->ctl.alloc(k.nctl);
+  if (rc != VCMI_OK) {
+    delete h;
+    return rc;
+  }
+  const int ctl0[6] = {0, INT32_MAX, 0, 0, INT32_MAX, 0};      // (word 4: the report of the cross-diagonal E-step's preparation)
+  const size_t md = (size_t)M * Dj;
+  hipError_t e = upload_now_hip(h->raw.p, w, sizeof(double) * M);
+  if (e == hipSuccess) e = upload_now_hip(h->raw.p + M, mu, sizeof(double) * md);
+  if (e == hipSuccess) e = upload_now_hip(h->raw.p + M + md, third, sizeof(double) * h->nthird());
+  if (e == hipSuccess) e = upload_now_hip(h->ctl.p, ctl0, sizeof(int) * k.nctl);
+  if (e != hipSuccess) {
+    delete h;
+    return fail(VCMI_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
+  }
+  *out = h;
+  return VCMI_OK;
+}
+
+static int em2_estep(Em2State *h, const char *who, const double *dX, int64_t N, double *dstats, void *stream) {
+  if (!h || !dstats) return fail(VCMI_ERR_ARG, "%s: NULL argument", who);
+  if (N < 0 || (N > 0 && !dX)) return fail(VCMI_ERR_ARG, "%s: bad frame block", who);
+  if (h->failed) return h->not_pd();
+  // (every unit of the block is valid: create and every M-step since have checked them)
+  return h->kind->estep(dX, N, h->Dj, h->M, h->params(), h->ctl.p, dstats, as_stream(stream));
+}
+
+static int em2_mstep(Em2State *h, const char *who, const double *dstats, void *stream, double *loglik) {
+  if (!h || !dstats) return fail(VCMI_ERR_ARG, "%s: NULL argument", who);
+  hipStream_t st = as_stream(stream);
+  hipLaunchKernelGGL(h->kind->mstep_kernel, dim3(h->M), dim3(256), 0, st, dstats, h->Dj, h->M, h->min_covar, h->next(), h->ctl.p);
+  VCMI_HIP(hipGetLastError());
+  struct {
+    int latch, bad;
+    double ll;
+  } r = {0, 0, 0.0};
+  static_assert(sizeof(r) == 16, "the control block starts with two ints and a double");
+  VCMI_HIP(hipMemcpyAsync(&r, h->ctl.p, sizeof(r), hipMemcpyDeviceToHost, st));
+  VCMI_HIP(hipStreamSynchronize(st));
+  if (loglik) *loglik = r.ll;
+  if (r.bad != INT32_MAX) {
+    if (!h->failed) {      // latch it on the device too: a later M-step kernel returns before it writes
+      const int one = 1;
+      VCMI_HIP(hipMemcpy(h->ctl.p, &one, sizeof(int), hipMemcpyHostToDevice));
+    }
+    h->failed = true;
+    h->bad = r.bad;
+    return h->not_pd();
+  }
+  h->cur = 1 - h->cur;
+  return VCMI_OK;
+}
+
+static int em2_get(Em2State *h, const char *who, double *w, double *mu, double *third) {
+  if (!h || !w || !mu || !third) return fail(VCMI_ERR_ARG, "%s: NULL argument", who);
+  VCMI_HIP(hipDeviceSynchronize());
+  const size_t md = (size_t)h->M * h->Dj;
+  VCMI_HIP(hipMemcpy(w, h->params(), sizeof(double) * h->M, hipMemcpyDeviceToHost));
+  VCMI_HIP(hipMemcpy(mu, h->params() + h->M, sizeof(double) * md, hipMemcpyDeviceToHost));
+  VCMI_HIP(hipMemcpy(third, h->params() + h->M + md, sizeof(double) * h->nthird(), hipMemcpyDeviceToHost));
+  return VCMI_OK;
+}
+
+static int em_diag_check_dims(const char *who, int Dj, int M) {
+  if (Dj < 1 || M < 1) return fail(VCMI_ERR_DIM, "%s: Dj=%d M=%d invalid", who, Dj, M);
+  if (Dj > 256)   // em_mstep_diag_kernel: one thread of a 256-thread workgroup per dimension
+    return fail(VCMI_ERR_DIM, "%s: joint dimension %d exceeds the device EM limit (256)", who, Dj);
+  if ((int64_t)M * Dj >= INT32_MAX) return fail(VCMI_ERR_DIM, "%s: Dj=%d M=%d too large", who, Dj, M);
+  return VCMI_OK;
+}
+
+// the diagonal state: units are dimensions, four control words
+static const Em2Kind kEmDiag = {
+    em_diag_check_dims,
+    first_bad_variance,
+    [](int Dj) { return Dj; },
+    [](int Dj) { return Dj; },
+    [](const char *who, int d, int m) { return fail(VCMI_ERR_NOT_PD, "%s: variance (%d,%d) is not positive", who, d, m); },
+    4,
+    em_mstep_diag_kernel,
+    [](const double *dX, int64_t N, int Dj, int M, const double *dparams, int *, double *dstats, hipStream_t st) {
+      return estep_device_block(dX, N, Dj, M, dparams, dstats, st);
+    }};
+
+// the cross-diagonal state: units are pairs, two more control words for the E-step preparation's report (ctl + 4, INT_MAX: none)
+static const Em2Kind kEmBdiag = {
+    estep_bdiag_check_dims,
+    first_bad_pair,
+    [](int Dj) { return Dj + Dj / 2; },
+    [](int Dj) { return Dj / 2; },
+    [](const char *who, int d, int m) { return fail(VCMI_ERR_NOT_PD, "%s: pair (%d,%d) is not positive definite", who, d, m); },
+    6,
+    em_mstep_bdiag_kernel,
+    [](const double *dX, int64_t N, int Dj, int M, const double *dparams, int *ctl, double *dstats, hipStream_t st) {
+      return estep_bdiag_device_block(dX, N, Dj, M, dparams, ctl + 4, dstats, st);
+    }};
+
+}  // namespace vcmi
+
+// two distinct opaque types, one state
+struct vcmi_gmm_em_diag : vcmi::Em2State {};
+struct vcmi_gmm_em_bdiag : vcmi::Em2State {};
 
 using namespace vcmi;
 
@@ -266,40 +406,7 @@ extern "C" int vcmi_gmm_em_get(vcmi_gmm_em *h, double *w, double *mu, double *si
 // ---- device-resident diagonal EM state -----------------------------------------------------------
 extern "C" int vcmi_gmm_em_diag_create(int Dj, int M, const double *w, const double *mu, const double *var, double min_covar,
                                        vcmi_gmm_em_diag **out) {
-  if (!w || !mu || !var || !out) return fail(VCMI_ERR_ARG, "vcmi_gmm_em_diag_create: NULL argument");
-  *out = nullptr;
-  if (Dj < 1 || M < 1) return fail(VCMI_ERR_DIM, "vcmi_gmm_em_diag_create: Dj=%d M=%d invalid", Dj, M);
-  if (Dj > 256)   // em_mstep_diag_kernel: one thread of a 256-thread workgroup per dimension
-    return fail(VCMI_ERR_DIM, "vcmi_gmm_em_diag_create: joint dimension %d exceeds the device EM limit (256)", Dj);
-  if ((int64_t)M * Dj >= INT32_MAX) return fail(VCMI_ERR_DIM, "vcmi_gmm_em_diag_create: Dj=%d M=%d too large", Dj, M);
-  if (!(min_covar >= 0.0)) return fail(VCMI_ERR_ARG, "vcmi_gmm_em_diag_create: min_covar must be >= 0");
-  const int64_t bad = first_bad_variance(var, Dj, M);
-  if (bad >= 0)
-    return fail(VCMI_ERR_NOT_PD, "vcmi_gmm_em_diag_create: variance (%d,%d) is not positive", (int)(bad % Dj) + 1, (int)(bad / Dj) + 1);
-  VCMI_TRY(check_device());
-  vcmi_gmm_em_diag *h = new (std::nothrow) vcmi_gmm_em_diag();
-  if (!h) return fail(VCMI_ERR_OOM, "out of host memory");
-  h->Dj = Dj;
-  h->M = M;
-  h->min_covar = min_covar;
-  (void)hipGetDevice(&h->device);
-  int rc = h->raw.alloc(2 * h->nraw());
-  if (rc == VCMI_OK) rc = h->ctl.alloc(4);
-  if (rc != VCMI_OK) {
-    delete h;
-    return rc;
-  }
-  const int ctl0[4] = {0, INT32_MAX, 0, 0};
-  hipError_t e = upload_now_hip(h->raw.p, w, sizeof(double) * M);
-  if (e == hipSuccess) e = upload_now_hip(h->raw.p + M, mu, sizeof(double) * M * Dj);
-  if (e == hipSuccess) e = upload_now_hip(h->raw.p + M + (size_t)M * Dj, var, sizeof(double) * M * Dj);
-  if (e == hipSuccess) e = upload_now_hip(h->ctl.p, ctl0, sizeof(ctl0));
-  if (e != hipSuccess) {
-    delete h;
-    return fail(VCMI_ERR_HIP, "vcmi_gmm_em_diag_create: %s", hipGetErrorString(e));
-  }
-  *out = h;
-  return VCMI_OK;
+  return em2_create(kEmDiag, "vcmi_gmm_em_diag_create", Dj, M, w, mu, var, min_covar, out);
 }
 
 extern "C" int vcmi_gmm_em_diag_destroy(vcmi_gmm_em_diag *h) {
@@ -308,103 +415,21 @@ extern "C" int vcmi_gmm_em_diag_destroy(vcmi_gmm_em_diag *h) {
 }
 
 extern "C" int vcmi_gmm_em_diag_estep_dev(vcmi_gmm_em_diag *h, const double *dX, int64_t N, double *dstats, void *stream) {
-  if (!h || !dstats) return fail(VCMI_ERR_ARG, "vcmi_gmm_em_diag_estep_dev: NULL argument");
-  if (N < 0 || (N > 0 && !dX)) return fail(VCMI_ERR_ARG, "vcmi_gmm_em_diag_estep_dev: bad frame block");
-  if (h->failed) return h->not_pd();
-  // (the variances of the block are positive: vcmi_gmm_em_diag_create and every M-step since have checked them)
-  return estep_device_block(dX, N, h->Dj, h->M, h->params(), dstats, as_stream(stream));
+  return em2_estep(h, "vcmi_gmm_em_diag_estep_dev", dX, N, dstats, stream);
 }
 
 extern "C" int vcmi_gmm_em_diag_mstep(vcmi_gmm_em_diag *h, const double *dstats, void *stream, double *loglik) {
-  if (!h || !dstats) return fail(VCMI_ERR_ARG, "vcmi_gmm_em_diag_mstep: NULL argument");
-  hipStream_t st = as_stream(stream);
-  double *next = h->raw.p + (size_t)(1 - h->cur) * h->nraw();
-  hipLaunchKernelGGL(em_mstep_diag_kernel, dim3(h->M), dim3(256), 0, st, dstats, h->Dj, h->M, h->min_covar, next, h->ctl.p);
-  VCMI_HIP(hipGetLastError());
-  struct {
-    int latch, bad;
-    double ll;
-  } r = {0, 0, 0.0};
-  static_assert(sizeof(r) == 16, "the control block is two ints and a double");
-  VCMI_HIP(hipMemcpyAsync(&r, h->ctl.p, sizeof(r), hipMemcpyDeviceToHost, st));
-  VCMI_HIP(hipStreamSynchronize(st));
-  if (loglik) *loglik = r.ll;
-  if (r.bad != INT32_MAX) {
-    if (!h->failed) {      // latch it on the device too: a later M-step kernel returns before it writes
-      const int one = 1;
-      VCMI_HIP(hipMemcpy(h->ctl.p, &one, sizeof(int), hipMemcpyHostToDevice));
-    }
-    h->failed = true;
-    h->bad = r.bad;
-    return h->not_pd();
-  }
-  h->cur = 1 - h->cur;
-  return VCMI_OK;
+  return em2_mstep(h, "vcmi_gmm_em_diag_mstep", dstats, stream, loglik);
 }
 
 extern "C" int vcmi_gmm_em_diag_get(vcmi_gmm_em_diag *h, double *w, double *mu, double *var) {
-  if (!h || !w || !mu || !var) return fail(VCMI_ERR_ARG, "vcmi_gmm_em_diag_get: NULL argument");
-  VCMI_HIP(hipDeviceSynchronize());
-  const size_t md = (size_t)h->M * h->Dj;
-  VCMI_HIP(hipMemcpy(w, h->params(), sizeof(double) * h->M, hipMemcpyDeviceToHost));
-  VCMI_HIP(hipMemcpy(mu, h->params() + h->M, sizeof(double) * md, hipMemcpyDeviceToHost));
-  VCMI_HIP(hipMemcpy(var, h->params() + h->M + md, sizeof(double) * md, hipMemcpyDeviceToHost));
-  return VCMI_OK;
+  return em2_get(h, "vcmi_gmm_em_diag_get", w, mu, var);
 }
 
 // ---- device-resident cross-diagonal EM state -----------------------------------------------------
-// As vcmi_gmm_em_diag: two parameter blocks [w | mu (Dj,M) | covars (Dj + D, M)], the M-step kernel writes the one the E-step
-// does not read, and a failed M-step leaves the parameters its statistics were computed under.
-struct vcmi_gmm_em_bdiag {
-  int Dj = 0, M = 0, device = 0, cur = 0;
-  double min_covar = 0.0;
-  bool failed = false;           // an M-step reported a pair: the state takes no further E-step
-  int bad = 0;                   // ... 1 + d + D m of that pair
-  vcmi::DevBuf<double> raw;      // 2 x M (1 + 2 Dj + D)
-  vcmi::DevBuf<int> ctl;         // [latch | smallest bad index (INT_MAX: none) | loglik (a double) | the E-step preparation's report]
-  size_t nraw() const { return (size_t)M * (1 + 2 * (size_t)Dj + Dj / 2); }
-  double *params() { return raw.p + (size_t)cur * nraw(); }
-  int not_pd() const {
-    const int D = Dj / 2;
-    return vcmi::fail(VCMI_ERR_NOT_PD, "M-step: pair (%d,%d) is not positive definite", (bad - 1) % D + 1, (bad - 1) / D + 1);
-  }
-};
-
 extern "C" int vcmi_gmm_em_bdiag_create(int Dj, int M, const double *w, const double *mu, const double *covars, double min_covar,
                                         vcmi_gmm_em_bdiag **out) {
-  if (!w || !mu || !covars || !out) return fail(VCMI_ERR_ARG, "vcmi_gmm_em_bdiag_create: NULL argument");
-  *out = nullptr;
-  VCMI_TRY(estep_bdiag_check_dims("vcmi_gmm_em_bdiag_create", Dj, M));
-  if (!(min_covar >= 0.0)) return fail(VCMI_ERR_ARG, "vcmi_gmm_em_bdiag_create: min_covar must be >= 0");
-  const int D = Dj / 2;
-  const int64_t bad = first_bad_pair(covars, Dj, M);
-  if (bad >= 0)
-    return fail(VCMI_ERR_NOT_PD, "vcmi_gmm_em_bdiag_create: pair (%d,%d) is not positive definite", (int)(bad % D) + 1, (int)(bad / D) + 1);
-  VCMI_TRY(check_device());
-  vcmi_gmm_em_bdiag *h = new (std::nothrow) vcmi_gmm_em_bdiag();
-  if (!h) return fail(VCMI_ERR_OOM, "out of host memory");
-  h->Dj = Dj;
-  h->M = M;
-  h->min_covar = min_covar;
-  (void)hipGetDevice(&h->device);
-  int rc = h->raw.alloc(2 * h->nraw());
-  if (rc == VCMI_OK) rc = h->ctl.alloc(6);
-  if (rc != VCMI_OK) {
-    delete h;
-    return rc;
-  }
-  const int ctl0[6] = {0, INT32_MAX, 0, 0, INT32_MAX, 0};
-  const size_t md = (size_t)M * Dj;
-  hipError_t e = upload_now_hip(h->raw.p, w, sizeof(double) * M);
-  if (e == hipSuccess) e = upload_now_hip(h->raw.p + M, mu, sizeof(double) * md);
-  if (e == hipSuccess) e = upload_now_hip(h->raw.p + M + md, covars, sizeof(double) * M * (Dj + D));
-  if (e == hipSuccess) e = upload_now_hip(h->ctl.p, ctl0, sizeof(ctl0));
-  if (e != hipSuccess) {
-    delete h;
-    return fail(VCMI_ERR_HIP, "vcmi_gmm_em_bdiag_create: %s", hipGetErrorString(e));
-  }
-  *out = h;
-  return VCMI_OK;
+  return em2_create(kEmBdiag, "vcmi_gmm_em_bdiag_create", Dj, M, w, mu, covars, min_covar, out);
 }
 
 extern "C" int vcmi_gmm_em_bdiag_destroy(vcmi_gmm_em_bdiag *h) {
@@ -413,46 +438,13 @@ extern "C" int vcmi_gmm_em_bdiag_destroy(vcmi_gmm_em_bdiag *h) {
 }
 
 extern "C" int vcmi_gmm_em_bdiag_estep_dev(vcmi_gmm_em_bdiag *h, const double *dX, int64_t N, double *dstats, void *stream) {
-  if (!h || !dstats) return fail(VCMI_ERR_ARG, "vcmi_gmm_em_bdiag_estep_dev: NULL argument");
-  if (N < 0 || (N > 0 && !dX)) return fail(VCMI_ERR_ARG, "vcmi_gmm_em_bdiag_estep_dev: bad frame block");
-  if (h->failed) return h->not_pd();
-  // (the pairs of the block are positive definite: vcmi_gmm_em_bdiag_create and every M-step since have checked them)
-  return estep_bdiag_device_block(dX, N, h->Dj, h->M, h->params(), h->ctl.p + 4, dstats, as_stream(stream));
+  return em2_estep(h, "vcmi_gmm_em_bdiag_estep_dev", dX, N, dstats, stream);
 }
 
 extern "C" int vcmi_gmm_em_bdiag_mstep(vcmi_gmm_em_bdiag *h, const double *dstats, void *stream, double *loglik) {
-  if (!h || !dstats) return fail(VCMI_ERR_ARG, "vcmi_gmm_em_bdiag_mstep: NULL argument");
-  hipStream_t st = as_stream(stream);
-  double *next = h->raw.p + (size_t)(1 - h->cur) * h->nraw();
-  hipLaunchKernelGGL(em_mstep_bdiag_kernel, dim3(h->M), dim3(256), 0, st, dstats, h->Dj, h->M, h->min_covar, next, h->ctl.p);
-  VCMI_HIP(hipGetLastError());
-  struct {
-    int latch, bad;
-    double ll;
-  } r = {0, 0, 0.0};
-  static_assert(sizeof(r) == 16, "the control block starts with two ints and a double");
-  VCMI_HIP(hipMemcpyAsync(&r, h->ctl.p, sizeof(r), hipMemcpyDeviceToHost, st));
-  VCMI_HIP(hipStreamSynchronize(st));
-  if (loglik) *loglik = r.ll;
-  if (r.bad != INT32_MAX) {
-    if (!h->failed) {      // latch it on the device too: a later M-step kernel returns before it writes
-      const int one = 1;
-      VCMI_HIP(hipMemcpy(h->ctl.p, &one, sizeof(int), hipMemcpyHostToDevice));
-    }
-    h->failed = true;
-    h->bad = r.bad;
-    return h->not_pd();
-  }
-  h->cur = 1 - h->cur;
-  return VCMI_OK;
+  return em2_mstep(h, "vcmi_gmm_em_bdiag_mstep", dstats, stream, loglik);
 }
 
 extern "C" int vcmi_gmm_em_bdiag_get(vcmi_gmm_em_bdiag *h, double *w, double *mu, double *covars) {
-  if (!h || !w || !mu || !covars) return fail(VCMI_ERR_ARG, "vcmi_gmm_em_bdiag_get: NULL argument");
-  VCMI_HIP(hipDeviceSynchronize());
-  const size_t md = (size_t)h->M * h->Dj;
-  VCMI_HIP(hipMemcpy(w, h->params(), sizeof(double) * h->M, hipMemcpyDeviceToHost));
-  VCMI_HIP(hipMemcpy(mu, h->params() + h->M, sizeof(double) * md, hipMemcpyDeviceToHost));
-  VCMI_HIP(hipMemcpy(covars, h->params() + h->M + md, sizeof(double) * h->M * (h->Dj + h->Dj / 2), hipMemcpyDeviceToHost));
-  return VCMI_OK;
+  return em2_get(h, "vcmi_gmm_em_bdiag_get", w, mu, covars);
 }

@@ -26,8 +26,16 @@ block-diagonal E-step, the initial covariances the variances and pair covariance
 for init="kmeans" from the M=1 block-diagonal E-step statistics (data_block_covariance).  expand_block_diag gives the
 (Dj,Dj,M) tensor that GMMMap and refine= of the full fit take; TrajectoryGMMMap(precision="diag") converts with such a model
 exactly.
+
+One driver serves the three types.  train_gmm holds the only EM loop, the only best-of-n_init selection and the only
+pack / broadcast / unpack of rank 0's model (pack_model, unpack_model: a third parameter of any shape); what differs between
+the types is one _CovType entry of _COV_TYPES -- the state class, the argument check, the covariance entry every mixture
+starts from (over all frames, or over a host subsample: subsample_model, numpy only) and the result's "covariance_type".
+data_covariance, data_variance and data_block_covariance share _data_moments (unit parameters, the M=1 E-step, the
+all-reduce).  Every argument error is raised before the first collective or device call.
 """
 import ctypes as C
+from collections import namedtuple
 
 import numpy as np
 
@@ -182,47 +190,106 @@ def kmeans_init(Xs, M, rng, n_iter=10):
     return Cn
 
 
-def data_covariance(X, group=None):
-    """cov(X) (ddof=1, as np.cov) over every frame of every rank, from the M=1 full E-step statistics."""
+def _data_moments(X, estep, unit, unpack, group):
+    """The moments of every frame of every rank: the M=1 E-step of `estep` under unit parameters (weight 1, mean 0, covariance
+    entry `unit`), all-reduced -> n, sum x (Dj,) and the type's remaining statistics, each without its mixture axis."""
     import torch.distributed as dist
 
     Dj = X.shape[0]
-    st = estep_full_dev(X, np.ones(1), np.zeros((Dj, 1)), np.eye(Dj)[:, :, None])
+    st = estep(X, np.ones(1), np.zeros((Dj, 1)), unit)
     if dist.is_available() and dist.is_initialized():
         dist.all_reduce(st, group=group)
-    S0, S1, S2, _ = unpack_full_stats(st.cpu().numpy(), Dj, 1)
-    n, s1 = S0[0], S1[:, 0]
-    cv = (S2[:, :, 0] - np.outer(s1, s1) / n) / (n - 1.0)
+    S0, S1, *rest = unpack(st.cpu().numpy(), Dj, 1)[:-1]
+    return S0[0], S1[:, 0], [S[..., 0] for S in rest]
+
+
+def data_covariance(X, group=None):
+    """cov(X) (ddof=1, as np.cov) over every frame of every rank, from the M=1 full E-step statistics."""
+    n, s1, (S2,) = _data_moments(X, estep_full_dev, np.eye(X.shape[0])[:, :, None], unpack_full_stats, group)
+    cv = (S2 - np.outer(s1, s1) / n) / (n - 1.0)
     return 0.5 * (cv + cv.T)
 
 
 def data_variance(X, group=None):
     """var(X) per dimension (ddof=1, the diagonal of np.cov) over every frame of every rank, from the M=1 diagonal E-step
     statistics (N, sum x, sum x^2)."""
-    import torch.distributed as dist
-
-    Dj = X.shape[0]
-    st = estep_diag_dev(X, np.ones(1), np.zeros((Dj, 1)), np.ones((Dj, 1)))
-    if dist.is_available() and dist.is_initialized():
-        dist.all_reduce(st, group=group)
-    S0, S1, S2, _ = unpack_stats(st.cpu().numpy(), Dj, 1)
-    n, s1 = S0[0], S1[:, 0]
-    return (S2[:, 0] - s1 * s1 / n) / (n - 1.0)
+    n, s1, (S2,) = _data_moments(X, estep_diag_dev, np.ones((X.shape[0], 1)), unpack_stats, group)
+    return (S2 - s1 * s1 / n) / (n - 1.0)
 
 
 def data_block_covariance(X, group=None):
     """The (Dj + D,) variances and pair covariances cov(z_d, z_{d+D}) (ddof=1) over every frame of every rank, from the M=1
     block-diagonal E-step statistics (N, sum z, sum z^2, sum z_d z_{d+D})."""
-    import torch.distributed as dist
-
     Dj = X.shape[0]
     D = Dj // 2
-    st = estep_bdiag_dev(X, np.ones(1), np.zeros((Dj, 1)), np.vstack([np.ones((Dj, 1)), np.zeros((D, 1))]))
-    if dist.is_available() and dist.is_initialized():
-        dist.all_reduce(st, group=group)
-    S0, S1, S2, Sxy, _ = unpack_bdiag_stats(st.cpu().numpy(), Dj, 1)
-    n, s1 = S0[0], S1[:, 0]
-    return np.concatenate([S2[:, 0] - s1 * s1 / n, Sxy[:, 0] - s1[:D] * s1[D:] / n]) / (n - 1.0)
+    n, s1, (S2, Sxy) = _data_moments(X, estep_bdiag_dev, np.vstack([np.ones((Dj, 1)), np.zeros((D, 1))]), unpack_bdiag_stats, group)
+    return np.concatenate([S2 - s1 * s1 / n, Sxy - s1[:D] * s1[D:] / n]) / (n - 1.0)
+
+
+# What train_gmm knows of a covariance type.  state: its _EMState subclass (which has the shape of the third parameter and the
+# length of the statistics); check(Dj, M, refine): the argument errors of the type, None where the state's own checks are all
+# there are; data_entry(X, group, min_covar) and sample_entry(Xs, min_covar): the covariance entry every mixture starts from,
+# over every frame of every rank (init="kmeans") and over a host subsample Xs (n,Dj); label: the result's "covariance_type",
+# None for none.
+_CovType = namedtuple("_CovType", "state check data_entry sample_entry label")
+
+
+def _check_diag(Dj, M, refine):
+    if refine is not None and np.shape(refine[2]) != (Dj, M):
+        raise _lib.DimensionMismatch(f"train_gmm: covariance_type='diag' refines from variances ({Dj},{M}), got {np.shape(refine[2])}")
+
+
+def _check_block_diag(Dj, M, refine):
+    if Dj % 2:
+        raise _lib.DimensionMismatch(f"train_gmm: covariance_type='block_diag' needs an even joint dimension, got {Dj}")
+    if refine is not None and np.shape(refine[2]) != (Dj + Dj // 2, M):
+        raise _lib.DimensionMismatch(f"train_gmm: covariance_type='block_diag' refines from covars ({Dj + Dj // 2},{M}), got {np.shape(refine[2])}")
+
+
+def _block_diag_floor(Dj, min_covar):
+    """min_covar on the variances only"""
+    return np.concatenate([np.full(Dj, float(min_covar)), np.zeros(Dj // 2)])
+
+
+def _block_diag_sample_entry(Xs, min_covar):
+    Dj = Xs.shape[1]
+    D = Dj // 2
+    Xc = Xs - Xs.mean(axis=0)
+    pair = (Xc[:, :D] * Xc[:, D:]).sum(axis=0) / (len(Xs) - 1.0)
+    return np.concatenate([np.var(Xs, axis=0, ddof=1), pair]) + _block_diag_floor(Dj, min_covar)
+
+
+_COV_TYPES = {
+    "full": _CovType(EMState, None,
+                     lambda X, group, min_covar: data_covariance(X, group) + min_covar * np.eye(X.shape[0]),
+                     lambda Xs, min_covar: np.cov(Xs.T) + min_covar * np.eye(Xs.shape[1]), None),
+    "diag": _CovType(DiagEMState, _check_diag,
+                     lambda X, group, min_covar: data_variance(X, group) + min_covar,
+                     lambda Xs, min_covar: np.var(Xs, axis=0, ddof=1) + min_covar, "diag"),
+    "block_diag": _CovType(BlockDiagEMState, _check_block_diag,
+                           lambda X, group, min_covar: data_block_covariance(X, group) + _block_diag_floor(X.shape[0], min_covar),
+                           _block_diag_sample_entry, "block_diag"),
+}
+
+
+def subsample_model(Xs, M, rng, min_covar, covariance_type):
+    """The initial model of init="subsample" from the host subsample Xs (n,Dj), numpy only: uniform weights, the means of
+    kmeans_init (the only draws from rng) and the type's covariance entry of Xs for every mixture -> w (M,), mu (Dj,M) and
+    the third parameter in its Julia shape (...,M)."""
+    mu0 = kmeans_init(Xs, M, rng).T
+    entry = _COV_TYPES[covariance_type].sample_entry(Xs, min_covar)
+    return np.full(M, 1.0 / M), mu0, np.repeat(entry[..., None], M, axis=-1)
+
+
+def pack_model(w, mu, third):
+    """w (M,), mu (Dj,M) and a third parameter of any shape -> one vector, every array in Julia (column-major) order: what rank 0
+    broadcasts"""
+    return np.concatenate([np.ravel(np.asarray(a, dtype=np.float64), order="F") for a in (w, mu, third)])
+
+
+def unpack_model(h, Dj, M, third_shape):
+    """the inverse of pack_model"""
+    return h[:M].copy(), h[M:M + M * Dj].reshape((Dj, M), order="F"), h[M + M * Dj:].reshape(third_shape, order="F")
 
 
 def train_gmm(X, n_components=16, n_iter=200, n_init=2, min_covar=1e-7, tol=1e-3, refine=None, seed=0, group=None,
@@ -241,16 +308,17 @@ def train_gmm(X, n_components=16, n_iter=200, n_init=2, min_covar=1e-7, tol=1e-3
     "covariance_type": "diag".
     covariance_type="block_diag" fits the cross-diagonal model (module docstring; Dj even): refine=(w, mu, covars (Dj + Dj/2, M)),
     "covars" is (Dj + Dj/2, M) = [variances; pair cross-covariances] and the result carries "covariance_type": "block_diag".
+    Argument errors are raised before the first collective or device call.
     """
-    if covariance_type not in ("full", "diag", "block_diag"):
+    if covariance_type not in tuple(_COV_TYPES):
         raise ValueError(f"train_gmm: covariance_type must be 'full', 'diag' or 'block_diag', got {covariance_type!r}")
-    diag = covariance_type == "diag"
+    ct = _COV_TYPES[covariance_type]
     Dj, N = X.shape
     M = int(n_components)
-    if covariance_type == "block_diag":
-        return _train_gmm_block_diag(X, M, n_iter, n_init, min_covar, tol, refine, seed, group, init_sample, init)
-    if diag and refine is not None and np.shape(refine[2]) != (Dj, M):
-        raise _lib.DimensionMismatch(f"train_gmm: covariance_type='diag' refines from variances ({Dj},{M}), got {np.shape(refine[2])}")
+    if ct.check is not None:
+        ct.check(Dj, M, refine)
+    if init not in ("subsample", "kmeans"):
+        raise ValueError(f"train_gmm: init must be 'subsample' or 'kmeans', got {init!r}")
 
     import torch
     import torch.distributed as dist
@@ -261,116 +329,30 @@ def train_gmm(X, n_components=16, n_iter=200, n_init=2, min_covar=1e-7, tol=1e-3
     if distributed:
         dist.all_reduce(ntot, group=group)
     ntot = float(ntot.item())
-    if init not in ("subsample", "kmeans"):
-        raise ValueError(f"train_gmm: init must be 'subsample' or 'kmeans', got {init!r}")
     rng = np.random.default_rng(seed)
-    if init != "kmeans" or refine is not None:
-        cv_all = None
-    elif diag:
-        cv_all = data_variance(X, group) + min_covar
-    else:
-        cv_all = data_covariance(X, group) + min_covar * np.eye(Dj)
-    nsig = Dj if diag else Dj * Dj         # covariance entries per mixture
+    third_shape = ct.state._third_shape(Dj, M)
+    entry_all = ct.data_entry(X, group, min_covar) if init == "kmeans" and refine is None else None
     best = None
     for _ in range(1 if refine is not None else max(1, int(n_init))):
         if refine is not None:
-            w0, mu0, sig0 = refine
+            w0, mu0, third0 = refine
         elif init == "kmeans":
             # every rank runs the same collective k-means and gets the same centers: nothing to broadcast
             mu0 = kmeans(X, M, seed=int(rng.integers(2**31 - 1)), group=group)["centers"]
-            sig0 = np.repeat(cv_all[:, None], M, axis=1) if diag else np.repeat(cv_all[:, :, None], M, axis=2)
+            third0 = np.repeat(entry_all[..., None], M, axis=-1)
             w0 = np.full(M, 1.0 / M)
         else:
             # rank 0 draws the initial model from its shard and every rank receives the same one
-            pk = torch.empty(M * (1 + Dj + nsig), dtype=torch.float64, device=X.device)
+            pk = torch.empty(M * (1 + Dj) + int(np.prod(third_shape)), dtype=torch.float64, device=X.device)
             if rank == 0:
                 idx = rng.choice(N, size=min(N, int(init_sample)), replace=False)
                 Xs = X[:, torch.from_numpy(np.sort(idx)).to(X.device)].t().contiguous().cpu().numpy()
-                mu0 = kmeans_init(Xs, M, rng).T
-                if diag:
-                    sig0 = np.repeat((np.var(Xs, axis=0, ddof=1) + min_covar)[:, None], M, axis=1)
-                else:
-                    cv = np.cov(Xs.T) + min_covar * np.eye(Dj)
-                    sig0 = np.repeat(cv[:, :, None], M, axis=2)
-                w0 = np.full(M, 1.0 / M)
-                pk.copy_(torch.from_numpy(np.concatenate([w0, mu0.T.ravel(), sig0.T.ravel()])))
+                pk.copy_(torch.from_numpy(pack_model(*subsample_model(Xs, M, rng, min_covar, covariance_type))))
             if distributed:
                 dist.broadcast(pk, src=0, group=group)
-            h = pk.cpu().numpy()
-            w0 = h[:M].copy()
-            mu0 = h[M:M + M * Dj].reshape(M, Dj).T
-            sig0 = h[M + M * Dj:].reshape(M, Dj).T if diag else np.transpose(h[M + M * Dj:].reshape(M, Dj, Dj), (2, 1, 0))
-        em = DiagEMState(w0, mu0, sig0, min_covar) if diag else EMState(w0, mu0, sig0, min_covar)
-        stats = torch.empty(stats_len(Dj, M) if diag else full_stats_len(Dj, M), dtype=torch.float64, device=X.device)
-        hist, converged = [], False
-        for _ in range(int(n_iter)):
-            em.estep(X, out=stats)
-            if distributed:
-                dist.all_reduce(stats, group=group)
-            hist.append(em.mstep(stats) / ntot)
-            if len(hist) > 1 and abs(hist[-1] - hist[-2]) < tol:
-                converged = True
-                break
-        if best is None or hist[-1] > best[0]:
-            best = (hist[-1], em.get(), hist, converged)
-    (w, mu, sigma), hist, converged = best[1], best[2], best[3]
-    out = {"weights": w, "means": mu, "covars": sigma, "n_components": M, "loglik": hist, "converged": converged}
-    if diag:
-        out["covariance_type"] = "diag"
-    return out
-
-
-def _train_gmm_block_diag(X, M, n_iter, n_init, min_covar, tol, refine, seed, group, init_sample, init):
-    """train_gmm for covariance_type="block_diag": the rules of the other two types on BlockDiagEMState."""
-    import torch
-    import torch.distributed as dist
-
-    Dj, N = X.shape
-    if Dj % 2:
-        raise _lib.DimensionMismatch(f"train_gmm: covariance_type='block_diag' needs an even joint dimension, got {Dj}")
-    D = Dj // 2
-    if refine is not None and np.shape(refine[2]) != (Dj + D, M):
-        raise _lib.DimensionMismatch(f"train_gmm: covariance_type='block_diag' refines from covars ({Dj + D},{M}), got {np.shape(refine[2])}")
-    if init not in ("subsample", "kmeans"):
-        raise ValueError(f"train_gmm: init must be 'subsample' or 'kmeans', got {init!r}")
-    distributed = dist.is_available() and dist.is_initialized()
-    rank = dist.get_rank(group) if distributed else 0
-    ntot = torch.tensor([float(N)], dtype=torch.float64, device=X.device)
-    if distributed:
-        dist.all_reduce(ntot, group=group)
-    ntot = float(ntot.item())
-    rng = np.random.default_rng(seed)
-    floor = np.concatenate([np.full(Dj, float(min_covar)), np.zeros(D)])        # min_covar on variances only
-    cv_all = data_block_covariance(X, group) + floor if init == "kmeans" and refine is None else None
-    best = None
-    for _ in range(1 if refine is not None else max(1, int(n_init))):
-        if refine is not None:
-            w0, mu0, cv0 = refine
-        elif init == "kmeans":
-            # every rank runs the same collective k-means and gets the same centers: nothing to broadcast
-            mu0 = kmeans(X, M, seed=int(rng.integers(2**31 - 1)), group=group)["centers"]
-            cv0 = np.repeat(cv_all[:, None], M, axis=1)
-            w0 = np.full(M, 1.0 / M)
-        else:
-            # rank 0 draws the initial model from its shard and every rank receives the same one
-            pk = torch.empty(M * (1 + 2 * Dj + D), dtype=torch.float64, device=X.device)
-            if rank == 0:
-                idx = rng.choice(N, size=min(N, int(init_sample)), replace=False)
-                Xs = X[:, torch.from_numpy(np.sort(idx)).to(X.device)].t().contiguous().cpu().numpy()
-                mu0 = kmeans_init(Xs, M, rng).T
-                Xc = Xs - Xs.mean(axis=0)
-                pair = (Xc[:, :D] * Xc[:, D:]).sum(axis=0) / (len(Xs) - 1.0)
-                cv0 = np.repeat((np.concatenate([np.var(Xs, axis=0, ddof=1), pair]) + floor)[:, None], M, axis=1)
-                w0 = np.full(M, 1.0 / M)
-                pk.copy_(torch.from_numpy(np.concatenate([w0, mu0.T.ravel(), cv0.T.ravel()])))
-            if distributed:
-                dist.broadcast(pk, src=0, group=group)
-            h = pk.cpu().numpy()
-            w0 = h[:M].copy()
-            mu0 = h[M:M + M * Dj].reshape(M, Dj).T
-            cv0 = h[M + M * Dj:].reshape(M, Dj + D).T
-        em = BlockDiagEMState(w0, mu0, cv0, min_covar)
-        stats = torch.empty(bdiag_stats_len(Dj, M), dtype=torch.float64, device=X.device)
+            w0, mu0, third0 = unpack_model(pk.cpu().numpy(), Dj, M, third_shape)
+        em = ct.state(w0, mu0, third0, min_covar)
+        stats = torch.empty(em._stats_len(Dj, M), dtype=torch.float64, device=X.device)
         hist, converged = [], False
         for _ in range(int(n_iter)):
             em.estep(X, out=stats)
@@ -383,8 +365,10 @@ def _train_gmm_block_diag(X, M, n_iter, n_init, min_covar, tol, refine, seed, gr
         if best is None or hist[-1] > best[0]:
             best = (hist[-1], em.get(), hist, converged)
     (w, mu, covars), hist, converged = best[1], best[2], best[3]
-    return {"weights": w, "means": mu, "covars": covars, "n_components": M, "loglik": hist, "converged": converged,
-            "covariance_type": "block_diag"}
+    out = {"weights": w, "means": mu, "covars": covars, "n_components": M, "loglik": hist, "converged": converged}
+    if ct.label is not None:
+        out["covariance_type"] = ct.label
+    return out
 
 
 __all__ = ["EMState", "DiagEMState", "BlockDiagEMState", "train_gmm", "expand_diag", "expand_block_diag", "data_block_covariance", "kmeans_init", "data_covariance", "data_variance", "unpack_full_stats"]
