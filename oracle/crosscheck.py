@@ -363,17 +363,26 @@ def check_gvgrad_is_the_gv_likelihood_gradient(y, muv, Sigvv, gvgrad_fn, rel=1e-
     return {"gvgrad_vs_mpmath_gradient_times_(T-1)/T": worst}
 
 
-def check_gv_step_mpmath(w, mu, sig, X, muv, Sigvv, step_fn, dps=50, tol=1e-9):
+def check_gv_step_mpmath(w, mu, sig, X, muv, Sigvv, step_fn, dps=50, tol=1e-9, y_start=None, epoch_pair=None):
     """One ascent step (src/trajectory_gmmmap.jl:163-166) from the eq. (58) initial trajectory, evaluated in 50-digit
     mpmath with dense W'D^-1W, against `step_fn(y0) -> y1` (the implementation under test started from the same y0).
-    Small cases only (dense mpmath products)."""
+    Small cases only (dense mpmath products).
+    y_start (T,D) with epoch_pair = (n, n + 1): the step is taken from y_start instead -- the implementation's OWN trajectory
+    after n epochs, where var(y) != mu_v and the GV term is not zero as it is at the eq. (58) start -- and compared with
+    `step_fn(y_start, epoch_pair) -> y_{n+1}`."""
     import mpmath as mp
 
     W, Dinv, E, _ = _trajectory_system(w, mu, sig, X)
     T, D2 = X.shape
     D = D2 // 2
-    y_dense, _ = gv_ascent_dense(w, mu, sig, X, muv, Sigvv, 0, 0.0)            # eq. (58) initial value (double)
-    y1 = step_fn(y_dense)
+    assert (y_start is None) == (epoch_pair is None)
+    if y_start is None:
+        y_dense, _ = gv_ascent_dense(w, mu, sig, X, muv, Sigvv, 0, 0.0)        # eq. (58) initial value (double)
+        y1 = step_fn(y_dense)
+    else:
+        y_dense = np.array(y_start, dtype=np.float64).reshape(T, D)
+        assert epoch_pair[1] == epoch_pair[0] + 1
+        y1 = step_fn(y_dense, epoch_pair)
     with mp.workdps(dps):
         import scipy.sparse as sp
         Wm = mp.matrix(W.toarray().tolist())
@@ -398,4 +407,4 @@ def check_gv_step_mpmath(w, mu, sig, X, muv, Sigvv, step_fn, dps=50, tol=1e-9):
                 err = max(err, abs(mp.mpf(float(y1[t, d])) - want))
         out = float(err / scale)
     assert out < tol, out
-    return {"gv_step_vs_mpmath": out, "digits": dps}
+    return {"gv_step_vs_mpmath": out, "digits": dps, "epochs": epoch_pair or (0, 1)}

@@ -5,6 +5,7 @@ Tolerance 1e-6 relative: the GV ascent starts from the trajectory solve, which t
 import numpy as np
 import pytest
 
+import gv_restatement as gr
 from conftest import julia_model, relerr
 
 pytestmark = pytest.mark.gpu
@@ -50,11 +51,19 @@ def test_fixture_model_gv(vc, fixture_model):
     assert len(tgv) == 100 and vc.dim(tgv) == 40 and vc.ncomponents(tgv) == 32
     got = vc.fvconvert(tgv, z["X"].T)
     assert got.shape == (20, 100) and relerr(got, want.T) < TOL
-    # the ascent really moved the trajectory away from both the plain solve and its rescaled start
+    # the result is away from the plain solve (eq. (58) alone accounts for that) ...
     assert relerr(got, z["Y"].T) > 1e-3
     # epochs = 0 is the eq. (58) initialisation alone = VarianceScaling(mu^v) of the plain trajectory
     init = vc.fvconvert(tgv, z["X"].T, epochs=0)
     assert relerr(init, vc.fvpostf(vc.VarianceScaling(muv), vc.fvconvert(t, z["X"].T))) < 1e-12
+    # ... and the ascent moves it away from that rescaled start by more than the oracle comparison could miss -- on a second
+    # converter whose GV covariance and step make both gradient terms count (FIXTURE_COV_SCALE, FIXTURE_ALPHA, FIXTURE_EPOCHS:
+    # tests/test_gv_restatement_host.py asserts, on the CPU, that each term is >= 0.2 of the step at n = 7 and 19)
+    tgs = vc.TrajectoryGVGMMMap(t, muv, Sv * gr.FIXTURE_COV_SCALE)
+    full = vc.fvconvert(tgs, z["X"].T, epochs=gr.FIXTURE_EPOCHS, alpha=gr.FIXTURE_ALPHA)
+    start = vc.fvconvert(tgs, z["X"].T, epochs=0, alpha=gr.FIXTURE_ALPHA)
+    assert np.all(np.isfinite(full)) and relerr(full, start) > 100 * TOL
+    assert relerr(full, ref.fvconvert_gv(z["X"], muv, Sv * gr.FIXTURE_COV_SCALE, gr.FIXTURE_EPOCHS, gr.FIXTURE_ALPHA).T) < TOL
     with pytest.raises(AssertionError):
         vc.TrajectoryGVGMMMap(t, -muv, Sv)
     # ... and the HIP path against the INDEPENDENT dense evaluation (oracle/crosscheck.py: scipy.sparse W, dense LU,
@@ -87,13 +96,55 @@ def test_one_gv_step_vs_mpmath_50_digits(vc):
             return vc.fvconvert(tgv, X.T, epochs=1, alpha=self.alpha).T
 
     assert cc.check_gv_step_mpmath(w2, mu2, sig2, X, muv2, Sv2, Step())["gv_step_vs_mpmath"] < 1e-10
+    # At the eq. (58) start var(y) = mu_v and the GV gradient is zero: the step above never evaluates it.  The step 5 -> 6, from
+    # the device's own y_5, with GV statistics and a step size at which both terms count (asserted here, from the restatement)
+    from oracle import np_oracle as npo
+    tj = npo.TrajectoryGMMMap(npo.GMMMap(w2, mu2, sig2))
+    muv3, Sv3 = gr.gv_stats(np.random.default_rng(3), tj.fvconvert(X)[0])
+    tgv3 = vc.TrajectoryGVGMMMap(vc.TrajectoryGMMMap(g, 6), muv3, np.asfortranarray(Sv3))
+
+    class Step56:
+        alpha = 0.1
+
+        def __call__(self, y, pair):
+            return vc.fvconvert(tgv3, X.T, epochs=pair[1], alpha=self.alpha).T
+
+    y5 = vc.fvconvert(tgv3, X.T, epochs=5, alpha=Step56.alpha).T
+    lik, gvt, _, _ = gr.gradient_terms(gr.Pieces(tj, X, muv3, Sv3), y5)
+    dy = float(np.max(np.abs(lik + gvt)))
+    assert float(np.max(np.abs(gvt))) >= 0.2 * dy and float(np.max(np.abs(lik))) >= 0.2 * dy
+    assert Step56.alpha * dy >= 1e-5 * np.max(np.abs(y5))
+    # K 2^-53 (2 + ...) with K = 3 * 6 + 6 + 3 + 16 (tests/test_gpu_gv_steps.py) is 1e-14 of max |y|
+    out = cc.check_gv_step_mpmath(w2, mu2, sig2, X, muv3, Sv3, Step56(), tol=1e-12, y_start=y5, epoch_pair=(5, 6))
+    assert out["gv_step_vs_mpmath"] < 1e-12 and out["epochs"] == (5, 6)
 
 
 @pytest.mark.parametrize("D,M,Ts,epochs", [(40, 8, [300, 37], 20), (12, 4, [2, 3, 17, 50], 100), (25, 5, [64, 129], 30),
                                            (13, 3, [40, 9], 25), (35, 4, [70], 10)])
 def test_vs_oracle_batch(vc, D, M, Ts, epochs):
     """config-5 shape (static D=40) and ragged / tiny utterances (T=2: both stencil neighbours missing somewhere;
-    tiles of 16 frames with several mixtures; D odd -> padded k-steps)"""
+    tiles of 16 frames with several mixtures; D odd -> padded k-steps) at the reference's default alpha"""
+    _vs_oracle_batch(vc, D, M, Ts, epochs, 1.0e-5, 1.0)
+
+
+@pytest.mark.parametrize("D,M,Ts,epochs", [(40, 8, [300, 37], 20), (12, 4, [17, 50], 100), (25, 5, [64, 129], 30),
+                                           (13, 3, [40], 25), (35, 4, [70], 10)])
+def test_vs_oracle_batch_step_visible(vc, D, M, Ts, epochs):
+    """the same shapes at the step size and GV covariance scale where the ascent moves y by 1e-2 of its size and both gradient
+    terms count (gv_restatement.ORACLE_ALPHA, ORACLE_COV_SCALE; T = 2, 3 and 9 diverge there).  Besides y,
+    the INCREMENT y_epochs - y_0 is compared, each side against its own epochs = 0, relative to max |increment|.  The bar is
+    gv_restatement.increment_bar: cond(P) 2^-53 c / (max |y_init - y_ml| / max |y|) with c = 64 * 2 * 2 * s *
+    max |y_init - y_ml| / max |increment| -- the solvers' parity bar (held against a long-double reference) for each of the
+    two plain trajectories, the eq. (58) scale s, |A - I| <= 2 for an ascent that does not expand differences, and the
+    factor that turns "relative to y_init - y_ml" into "relative to the increment" for a start difference that is not
+    parallel to y_init - y_ml; every factor from the oracle's side, none from a run of the kernel.  (With c = 64 alone, the
+    proportional reading, an MI355X gives D=25, T=64 4.3e-12 against 3.0e-12 while both plain trajectories are within the
+    parity bar of the long-double solve and every epoch within its rounding bar, tests/test_gpu_gv_steps.py: a start
+    difference along the stiff directions of P is not proportional to y_init - y_ml.)"""
+    _vs_oracle_batch(vc, D, M, Ts, epochs, gr.ORACLE_ALPHA, gr.ORACLE_COV_SCALE)
+
+
+def _vs_oracle_batch(vc, D, M, Ts, epochs, alpha, cov_scale):
     from oracle import c_oracle as co, np_oracle as npo
     w, mu, sig = npo.synth_model(600 + D, 4 * D, M, lam_lo=1e-3)
     ref = co.TrajectoryGMMMap(co.GMMMap(w, mu, sig))
@@ -103,11 +154,26 @@ def test_vs_oracle_batch(vc, D, M, Ts, epochs):
     Xs = _utterances(npo, rng, w, mu, sig, D, Ts)
     y_long = ref.fvconvert(Xs[0])[0]
     muv, Sv = _gv_stats(rng, y_long if y_long.shape[0] > 2 else np.vstack([y_long, y_long + 1.0]))
+    Sv = Sv * cov_scale
     tgv = vc.TrajectoryGVGMMMap(t, muv, Sv)
-    got = tgv.fvconvert_batch([x.T for x in Xs], epochs=epochs, alpha=1.0e-5)
+    got = tgv.fvconvert_batch([x.T for x in Xs], epochs=epochs, alpha=alpha)
     for x, y in zip(Xs, got):
-        want = ref.fvconvert_gv(x, muv, Sv, epochs, 1.0e-5)
+        want = ref.fvconvert_gv(x, muv, Sv, epochs, alpha)
         assert relerr(y, want.T) < TOL, x.shape
+    if alpha != 1.0e-5:
+        got0 = tgv.fvconvert_batch([x.T for x in Xs], epochs=0, alpha=alpha)
+        missed = []
+        for x, y, y0 in zip(Xs, got, got0):
+            want, want0 = ref.fvconvert_gv(x, muv, Sv, epochs, alpha), ref.fvconvert_gv(x, muv, Sv, 0, alpha)
+            inc, inc_ref = y.T - y0.T, want - want0
+            bar, cond = gr.increment_bar((w, mu, sig), x, want, want0, ref.fvconvert(x)[0], inc_ref, muv)
+            e = float(np.max(np.abs(inc - inc_ref)) / np.max(np.abs(inc_ref)))
+            print(f"GVINC D={D} T={x.shape[0]} epochs={epochs}: increment {np.max(np.abs(inc_ref)) / np.max(np.abs(want)):.2e} of max|y|, "
+                  f"vs oracle {e:.2e} of it, bar {bar:.2e} (cond {cond:.3g})")
+            assert np.max(np.abs(inc_ref)) > 1e-3 * np.max(np.abs(want)), x.shape
+            if not e <= bar:
+                missed.append((x.shape[0], e, bar))
+        assert not missed, f"increment vs oracle beyond the bar (T, error, bar): {missed}"
     with pytest.raises(vc.DimensionMismatch):
         tgv.fvconvert_batch([Xs[0][:1].T])            # a one-frame trajectory has no variance
 

@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import call_history as ch
+import gv_restatement as gr
 from conftest import julia_model, relerr
 
 pytestmark = pytest.mark.gpu
@@ -89,17 +90,50 @@ def test_vs_oracle_batch(vc, D, M, Ts, epochs, model_seed):
     """D = 49: the first dimension above the old limit -- seven row tiles, 2D = 98 = 24 * 4 + 2 (a partial last k-step, a last
     row tile with two live rows), T = 2 with both stencil neighbours missing; D = 52: whole k-steps, a long and a short
     utterance; D = 66: the fallback solver with its window in HBM; D = 130: 2D = 260, seventeen row tiles (two passes over the
-    rows) and five k chunks."""
+    rows) and five k chunks.  The reference's default alpha."""
+    _vs_oracle_batch(vc, D, M, Ts, epochs, model_seed, ALPHA, 1.0)
+
+
+# the shapes of ORACLE_CASES without the two-frame utterance, which diverges at the step-visible values
+STEP_VISIBLE_CASES = [(49, 5, (70, 33), 20, None), (52, 4, (300, 17), 20, None), (66, 6, (40, 9), 25, None), (130, 6, (37,), 10, 731)]
+
+
+@pytest.mark.parametrize("D,M,Ts,epochs,model_seed", STEP_VISIBLE_CASES)
+def test_vs_oracle_batch_step_visible(vc, D, M, Ts, epochs, model_seed):
+    """the same shapes at the step size and GV covariance scale where the ascent moves y by 1e-2 of its size and both gradient
+    terms count (gv_restatement.ORACLE_ALPHA, ORACLE_COV_SCALE).  Besides y, the INCREMENT y_epochs - y_0 is compared, each
+    side against its own epochs = 0, relative to max |increment|, with the bar of gv_restatement.increment_bar (derived there
+    from the solvers' parity bar, the eq. (58) scale and |A - I| <= 2; see tests/test_gpu_gv.py), not taken from a run of the
+    kernel."""
+    _vs_oracle_batch(vc, D, M, Ts, epochs, model_seed, gr.ORACLE_ALPHA, gr.ORACLE_COV_SCALE)
+
+
+def _vs_oracle_batch(vc, D, M, Ts, epochs, model_seed, alpha, cov_scale):
     c = _case(D, M, Ts, None, model_seed)
-    ref, Xs, muv, Sv = c["ref"], c["Xs"], c["muv"], c["Sv"]
+    ref, Xs, muv, Sv = c["ref"], c["Xs"], c["muv"], c["Sv"] * cov_scale
     assert _mixtures_in_a_run(c["mhat0"]) >= 2, "the generator no longer mixes mixtures inside 16 frames"
-    t, tgv = _make(vc, c, max(Ts))
-    got = tgv.fvconvert_batch([x.T for x in Xs], epochs=epochs, alpha=ALPHA)
+    t = vc.TrajectoryGMMMap(vc.GMMMap(*julia_model(*c["model"])), max(Ts))
+    tgv = vc.TrajectoryGVGMMMap(t, muv, Sv)
+    got = tgv.fvconvert_batch([x.T for x in Xs], epochs=epochs, alpha=alpha)
     for x, y in zip(Xs, got):
-        want = ref.fvconvert_gv(x, muv, Sv, epochs, ALPHA)
+        want = ref.fvconvert_gv(x, muv, Sv, epochs, alpha)
         e = relerr(y, want.T)
-        print(f"GV D={D} M={M} T={x.shape[0]} epochs={epochs}: vs oracle {e:.2e}")
+        print(f"GV D={D} M={M} T={x.shape[0]} epochs={epochs} alpha={alpha:g}: vs oracle {e:.2e}")
         assert y.shape == (D, x.shape[0]) and e < TOL, x.shape
+    if alpha != ALPHA:
+        got0 = tgv.fvconvert_batch([x.T for x in Xs], epochs=0, alpha=alpha)
+        missed = []
+        for x, y, y0 in zip(Xs, got, got0):
+            want, want0 = ref.fvconvert_gv(x, muv, Sv, epochs, alpha), ref.fvconvert_gv(x, muv, Sv, 0, alpha)
+            inc, inc_ref = y.T - y0.T, want - want0
+            bar, cond = gr.increment_bar(c["model"], x, want, want0, ref.fvconvert(x)[0], inc_ref, muv)
+            e = float(np.max(np.abs(inc - inc_ref)) / np.max(np.abs(inc_ref)))
+            print(f"GVINC D={D} T={x.shape[0]} epochs={epochs}: increment {np.max(np.abs(inc_ref)) / np.max(np.abs(want)):.2e} of max|y|, "
+                  f"vs oracle {e:.2e} of it, bar {bar:.2e} (cond {cond:.3g})")
+            assert np.max(np.abs(inc_ref)) > 1e-3 * np.max(np.abs(want)), x.shape
+            if not e <= bar:
+                missed.append((x.shape[0], e, bar))
+        assert not missed, f"increment vs oracle beyond the bar (T, error, bar): {missed}"
     moved = relerr(got[0], c["y0"].T)
     print(f"   ascent vs the plain trajectory: {moved:.2e}")
     assert moved > 1e-3                                   # the ascent moved the trajectory
