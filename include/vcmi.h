@@ -176,7 +176,45 @@ int vcmi_gmmmap_convert_plan(vcmi_gmmmap *g, int64_t *mfma_issued, int *shape, d
                              double *model_undecided_frac);
 
 /* ---------------------------------------------------------------------------------------------
- * DTW -- src/dtw.jl:93-145 (fit! + backward), align -- src/align.jl:8-35
+ * Cross-diagonal GMMMap -- frame-by-frame conversion (src/gmmmap.jl:101-118, src/gmm.jl:24-58) with the model that
+ * train_gmm(covariance_type="block_diag") returns: the four blocks of every joint covariance are diagonal (Toda, Black,
+ * Tokuda 2007).  What vcmi_gmmmap_create gives on the expanded (Dj,Dj,M) covariances, at about 6 D M vector operations per frame
+ * instead of M (3 D^2 + 6 D) flop (csrc/gmmmap_bdiag.hip).
+ *
+ * A handle converts on the device it was created on; a device group (vcmi_set_devices) does not shard its calls.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct vcmi_bdmap vcmi_bdmap;
+
+/* weights (M), mu (Dj,M), covars (Dj + D, M) = [variances of the Dj rows | D pair cross-covariances], D = Dj / 2: pair d couples
+ * the rows d and d + D.  swap != 0 exchanges the halves (src/gmmmap.jl:74-78).  Dj even, 1 <= D <= 128, 1 <= M <= 256, else
+ * VCMI_ERR_DIM.  A pair with vx <= 0, vy <= 0, vx vy - c^2 <= 0 or a NaN: VCMI_ERR_NOT_PD, the message names the first such
+ * (pair, mixture) in memory order, 1-based, as vcmi_gmm_em_bdiag_create does.  A mixture with weight <= 0 has posterior 0. */
+int vcmi_bdmap_create(const double *weights, const double *mu, const double *covars, int Dj, int M, int swap,
+                      vcmi_bdmap **out);
+int vcmi_bdmap_destroy(vcmi_bdmap *h);
+int vcmi_bdmap_dim(const vcmi_bdmap *h);
+int vcmi_bdmap_ncomponents(const vcmi_bdmap *h);
+/* the regression slopes a = c / vx (D,M) */
+int vcmi_bdmap_get_a(const vcmi_bdmap *h, double *a);
+/* fvconvert for every column of X (D,T) -> Y (D,T), leading dimensions ldx, ldy >= D; one launch per device-resident call.
+ * A frame's result does not depend on the other frames of the call; identical inputs give identical bits. */
+int vcmi_bdmap_convert(vcmi_bdmap *h, const double *X, int64_t ldx, int64_t T, double *Y, int64_t ldy);
+int vcmi_bdmap_convert_dev(vcmi_bdmap *h, const double *dX, int64_t ldx, int64_t T, double *dY, int64_t ldy, void *stream);
+/* predict_proba -> P (M,T) */
+int vcmi_bdmap_posterior(vcmi_bdmap *h, const double *X, int64_t ldx, int64_t T, double *P);
+int vcmi_bdmap_posterior_dev(vcmi_bdmap *h, const double *dX, int64_t ldx, int64_t T, double *dP, void *stream);
+/* predict -> idx (T), 1-based, first maximum wins */
+int vcmi_bdmap_predict(vcmi_bdmap *h, const double *X, int64_t ldx, int64_t T, int64_t *idx);
+int vcmi_bdmap_predict_dev(vcmi_bdmap *h, const double *dX, int64_t ldx, int64_t T, int64_t *didx, void *stream);
+/* vc(c, fm), src/common.jl:7-26: fm, out (D+1,T), row 1 (power) copied; sigma2 (D, host) != NULL: the VarianceScaling filter on
+ * the converted rows before the download, as vcmi_vc_frames_postf (T = 1 then: VCMI_ERR_DIM). */
+int vcmi_vc_bdmap(vcmi_bdmap *h, const double *fm, int64_t T, const double *sigma2, double *out);
+/* the contract of vcmi_vc_frames_batch: out[u] is what vcmi_vc_bdmap(h, fm[u], T[u], sigma2, out[u]) gives, bit for bit */
+int vcmi_vc_bdmap_batch(vcmi_bdmap *h, int64_t n, const double *const *fm, const int64_t *T, const double *sigma2,
+                        double *const *out);
+
+/* ---------------------------------------------------------------------------------------------
+ * DTW --src/dtw.jl:93-145 (fit! + backward), align -- src/align.jl:8-35
  * ------------------------------------------------------------------------------------------- */
 /* fit!(DTW(fstep,bstep), template (D,S), sequence (D,T)) -> path (T).  costtable (S,T+1) f64 and
  * backpointer (S,T+1) Int64 are the fields d.costtable / d.backpointer (src/dtw.jl:15-16); pass NULL

@@ -9,6 +9,7 @@ from .common import (AbstractConverter, FrameByFrameConverter, TrajectoryConvert
                      ncomponents, size, vc, vc_batch)
 from .gmm import GMM, predict, predict_proba  # noqa: F401
 from .gmmmap import GMMMap  # noqa: F401
+from .gmmmap_bdiag import BlockDiagGMMMap  # noqa: F401
 from .dtw import DTW, backward, fit_, fit_batch, set_template_, update_  # noqa: F401,E402
 from .align import align, align_batch  # noqa: F401,E402
 from .estep import (ESTEP_AUTO, ESTEP_HARD, ESTEP_SOFT, estep_diag, estep_diag_allreduce, estep_diag_dev, estep_get_path,  # noqa: F401,E402

@@ -81,6 +81,19 @@ SIGNATURES = {
     "vcmi_gmmmap_set_prune": (_int, [_vp, C.c_double]),
     "vcmi_gmmmap_prune_stats": (_int, [_vp, _int, _ip]),
     "vcmi_gmmmap_convert_plan": (_int, [_vp, _ip, C.POINTER(_int), _dp, _dp]),
+    "vcmi_bdmap_create": (_int, [_dp, _dp, _dp, _int, _int, _int, C.POINTER(_vp)]),
+    "vcmi_bdmap_destroy": (_int, [_vp]),
+    "vcmi_bdmap_dim": (_int, [_vp]),
+    "vcmi_bdmap_ncomponents": (_int, [_vp]),
+    "vcmi_bdmap_get_a": (_int, [_vp, _dp]),
+    "vcmi_bdmap_convert": (_int, [_vp, _dp, _i64, _i64, _dp, _i64]),
+    "vcmi_bdmap_convert_dev": (_int, [_vp, _vp, _i64, _i64, _vp, _i64, _vp]),
+    "vcmi_bdmap_posterior": (_int, [_vp, _dp, _i64, _i64, _dp]),
+    "vcmi_bdmap_posterior_dev": (_int, [_vp, _vp, _i64, _i64, _vp, _vp]),
+    "vcmi_bdmap_predict": (_int, [_vp, _dp, _i64, _i64, _ip]),
+    "vcmi_bdmap_predict_dev": (_int, [_vp, _vp, _i64, _i64, _vp, _vp]),
+    "vcmi_vc_bdmap": (_int, [_vp, _dp, _i64, _dp, _dp]),
+    "vcmi_vc_bdmap_batch": (_int, [_vp, _i64, _dpp, _ip, _dp, _dpp]),
     "vcmi_dtw_fit": (_int, [_dp, _i64, _dp, _i64, _int, _int, _int, _ip, _dp, _ip]),
     "vcmi_dtw_fit_batch": (_int, [_i64, _dpp, _ip, _dpp, _ip, _int, _int, _int, _ipp]),
     "vcmi_dtw_fit_batch_dev": (_int, [_i64, _vp, _ip, _ip, _ip, _ip, _int, _int, _int, _vp, _ip, _vp]),

@@ -213,16 +213,6 @@ int estep_bdiag_check_dims(const char *who, int Dj, int M) {
   return VCMI_OK;
 }
 
-int64_t first_bad_pair(const double *covars, int Dj, int M) {
-  const int D = Dj / 2;
-  for (int m = 0; m < M; ++m) {
-    const double *cv = covars + (size_t)m * (Dj + D);
-    for (int d = 0; d < D; ++d)
-      if (!bdiag_pair_valid(cv[d], cv[D + d], cv[Dj + d])) return d + (int64_t)D * m;
-  }
-  return -1;
-}
-
 // the kernels of one E-step under the DEVICE parameter block draw; sc is entered (StreamOrderScope) by the caller
 static int estep_bdiag_run(EstepBdiagScratch &sc, const double *dX, int64_t N, int Dj, int M, const double *draw, int *dflag,
                            double *dstats, hipStream_t st) {

@@ -4,6 +4,7 @@
 // the file that defines it.
 #pragma once
 #include "vcmi_common.hpp"
+#include "bdiag_pair.hpp"
 
 struct vcmi_gmmmap;
 
@@ -44,19 +45,9 @@ int mfma_count_hook(DevBuf<unsigned long long> &count, int enable, int64_t *issu
 // are [var (Dj) | c (D)].  Every even Dj in [2, 256] and M in [1, 256]: estep_bdiag_gamma_kernel holds a 64-frame tile of
 // Dj rows in LDS, em_mstep_bdiag_kernel is one thread per pair.
 constexpr int kBdiagMaxDj = 256, kBdiagMaxM = 256;
-// vx vy - c^2 to a few ulps also where it cancels (Kahan's 2 x 2 determinant: the rounding of c c is added back)
-__host__ __device__ inline double bdiag_det(double vx, double vy, double c) {
-  const double cc = c * c;
-  return fma(vx, vy, -cc) - fma(c, c, -cc);
-}
-// the pair's 2 x 2 block is positive definite (a NaN anywhere: not)
-__host__ __device__ inline bool bdiag_pair_valid(double vx, double vy, double c) {
-  return vx > 0.0 && vy > 0.0 && bdiag_det(vx, vy, c) > 0.0;
-}
+// bdiag_det, bdiag_pair_valid and first_bad_pair: bdiag_pair.hpp (no HIP: the host-only preparation files share them)
 // VCMI_ERR_DIM unless Dj is even, 2 <= Dj <= kBdiagMaxDj and 1 <= M <= kBdiagMaxM; the message names the limit
 int estep_bdiag_check_dims(const char *who, int Dj, int M);
-// index d + D m of the first pair of covars (Dj + D, M) that is not valid, -1: none
-int64_t first_bad_pair(const double *covars, int Dj, int M);
 // The E-step of N device-resident frames from a DEVICE parameter block [w (M) | mu (Dj,M) | covars (Dj + D, M)] that the
 // caller keeps alive and orders on `st`; asynchronous, no parameter crosses the host.  *dflag (an int the caller has set to
 // INT_MAX) receives the smallest 1 + d + D m of an invalid pair; N == 0 zeroes the statistics and launches nothing.

@@ -3,6 +3,7 @@
 // routine behind vcmi_vc_traj_postf / vcmi_vc_traj_static / vcmi_vc_trajgv and their *_dev forms), and the whole-matrix device
 // scratch of the host-pointer entries of both files.
 #pragma once
+#include <functional>
 #include "vcmi_common.hpp"
 
 namespace vcmi {
@@ -56,4 +57,12 @@ struct VcScratch {
   };
 };
 VcScratch &vc_scratch();   // the calling thread's
+
+// The body of vcmi_vc_frames_batch (vc_batch.hip) for any frame-by-frame converter of dimension D: `convert` turns rows 2..D+1
+// of the packed (D+1, N) device matrix (dX, leading dimension ld) into the same rows of the result (dY, same ld), asynchronous
+// on st.  Every check, the gather, the per-utterance filter and the scatter are the shared routine's; `who` names the entry in
+// its messages.
+using FrameConvertFn = std::function<int(const double *dX, int64_t ld, int64_t N, double *dY, hipStream_t st)>;
+int vc_frames_batch(int D, const FrameConvertFn &convert, int64_t n, const double *const *fm, const int64_t *T,
+                    const double *sigma2, double *const *out, const char *who);
 }  // namespace vcmi

@@ -292,16 +292,13 @@ static int vc_traj_batch_dev(vcmi_traj *t, vcmi_trajgv *gvh, int epochs, double 
 
 using namespace vcmi;
 
-// vc(g::GMMMap, fm_u) for every utterance: one conversion over the packed (D+1, sum T) matrix, then the per-utterance filter in
-// place (vcmi_vc_frames_postf with an outer utterance index)
-extern "C" int vcmi_vc_frames_batch(vcmi_gmmmap *g, int64_t n, const double *const *fm, const int64_t *T, const double *sigma2,
-                                    double *const *out) {
-  const char *who = "vcmi_vc_frames_batch";
-  if (!g) return fail(VCMI_ERR_ARG, "%s: NULL handle", who);
+// vc(c::FrameByFrameConverter, fm_u) for every utterance: one conversion over the packed (D+1, sum T) matrix, then the
+// per-utterance filter in place (vcmi_vc_frames_postf with an outer utterance index).  postf.hpp: vc_frames_batch.
+int vcmi::vc_frames_batch(int D, const FrameConvertFn &convert, int64_t n, const double *const *fm, const int64_t *T,
+                          const double *sigma2, double *const *out, const char *who) {
   if (n < 0) return fail(VCMI_ERR_ARG, "%s: negative batch size", who);
   if (n == 0) return VCMI_OK;
   if (!fm || !T || !out) return fail(VCMI_ERR_ARG, "%s: NULL argument", who);
-  const int D = g->D;
   if (sigma2 && (D < 1 || D > 256)) return fail(VCMI_ERR_DIM, "%s: variance scaling needs 1 <= D <= 256", who);
   const VcBatchPlan plan = vc_batch_plan(n, T, false, 0, D + 1, D + 1, sigma2 != nullptr, false);
   if (plan.status != VCMI_OK) return fail(plan.status, "%s: %s", who, plan.why);
@@ -326,11 +323,19 @@ extern "C" int vcmi_vc_frames_batch(vcmi_gmmmap *g, int64_t n, const double *con
   VCMI_TRY(staged_upload_gather(din, up, nullptr));
   // the copy keeps row 1 (src/common.jl:23); the kernel then overwrites rows 2..D+1, as in vcmi_vc_frames
   VCMI_HIP(hipMemcpyAsync(dout, din, sizeof(double) * ld * N, hipMemcpyDeviceToDevice, nullptr));
-  VCMI_TRY(gmmmap_convert_device(g, din + 1, ld, N, dout + 1, ld, nullptr));
+  VCMI_TRY(convert(din + 1, ld, N, dout + 1, nullptr));
   if (sigma2)
     VCMI_TRY(vcb_filter_and_post(plan, vcb_lists_at(plan, reinterpret_cast<const int64_t *>(dlists)), dout, false, ld, D, sigma2,
                                  dout, nullptr));
   return staged_download_scatter(down, dout, nullptr);
+}
+
+extern "C" int vcmi_vc_frames_batch(vcmi_gmmmap *g, int64_t n, const double *const *fm, const int64_t *T, const double *sigma2,
+                                    double *const *out) {
+  if (!g) return fail(VCMI_ERR_ARG, "vcmi_vc_frames_batch: NULL handle");
+  return vc_frames_batch(g->D, [g](const double *dX, int64_t ld, int64_t N, double *dY, hipStream_t st) -> int {
+                           return gmmmap_convert_device(g, dX, ld, N, dY, ld, st);
+                         }, n, fm, T, sigma2, out, "vcmi_vc_frames_batch");
 }
 
 extern "C" int vcmi_vc_traj_batch(vcmi_traj *t, int64_t n, const double *const *fm, const int64_t *T, int is_static,

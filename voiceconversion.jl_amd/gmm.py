@@ -9,8 +9,13 @@ from ._arrays import current_stream_ptr, dev_matrix, is_torch, jl_matrix, jl_vec
 
 
 class GMM:
-    def __init__(self, owner):
-        self._owner = owner       # GMMMap keeping the libvcmi handle alive
+    """The view carries the four C entries of its owner's handle type (default: vcmi_gmmmap_*), so predict_proba and predict
+    below serve every frame-by-frame converter."""
+
+    def __init__(self, owner, prefix="vcmi_gmmmap"):
+        self._owner = owner       # the converter keeping the libvcmi handle alive
+        self._posterior, self._posterior_dev, self._predict, self._predict_dev = (
+            getattr(_lib.lib, f"{prefix}_{name}") for name in ("posterior", "posterior_dev", "predict", "predict_dev"))
 
     @property
     def _h(self):
@@ -28,13 +33,13 @@ def predict_proba(gmm, X):
 
         ptr, D, T, ld = dev_matrix(X, "X")
         P = torch.empty((T, M), dtype=torch.float64, device=X.device)
-        _lib.check(_lib.lib.vcmi_gmmmap_posterior_dev(gmm._h, ptr, ld, T, P.data_ptr(), current_stream_ptr()))
+        _lib.check(gmm._posterior_dev(gmm._h, ptr, ld, T, P.data_ptr(), current_stream_ptr()))
         return P.t()
     X = np.asarray(X)
     if X.ndim == 1:
         x = jl_vector(X)
         P = np.empty(M)
-        _lib.check(_lib.lib.vcmi_gmmmap_posterior(gmm._h, _lib.dptr(x), max(len(x), 1), 1, _lib.dptr(P)) if len(x) == gmm._owner._dim()
+        _lib.check(gmm._posterior(gmm._h, _lib.dptr(x), max(len(x), 1), 1, _lib.dptr(P)) if len(x) == gmm._owner._dim()
                    else _dim_error(gmm, len(x)))
         return P
     X = jl_matrix(X, "X")
@@ -42,7 +47,7 @@ def predict_proba(gmm, X):
     if D != gmm._owner._dim():
         _dim_error(gmm, D)
     P = np.empty((M, T), order="F")
-    _lib.check(_lib.lib.vcmi_gmmmap_posterior(gmm._h, _lib.dptr(X), D, T, _lib.dptr(P)))
+    _lib.check(gmm._posterior(gmm._h, _lib.dptr(X), D, T, _lib.dptr(P)))
     return P
 
 
@@ -53,7 +58,7 @@ def predict(gmm, X):
 
         ptr, D, T, ld = dev_matrix(X, "X")
         idx = torch.empty(T, dtype=torch.int64, device=X.device)
-        _lib.check(_lib.lib.vcmi_gmmmap_predict_dev(gmm._h, ptr, ld, T, idx.data_ptr(), current_stream_ptr()))
+        _lib.check(gmm._predict_dev(gmm._h, ptr, ld, T, idx.data_ptr(), current_stream_ptr()))
         return idx
     X = np.asarray(X)
     single = X.ndim == 1
@@ -62,7 +67,7 @@ def predict(gmm, X):
     if D != gmm._owner._dim():
         _dim_error(gmm, D)
     idx = np.empty(T, dtype=np.int64)
-    _lib.check(_lib.lib.vcmi_gmmmap_predict(gmm._h, _lib.dptr(Xm), D, T, _lib.iptr(idx)))
+    _lib.check(gmm._predict(gmm._h, _lib.dptr(Xm), D, T, _lib.iptr(idx)))
     return int(idx[0]) if single else idx
 
 

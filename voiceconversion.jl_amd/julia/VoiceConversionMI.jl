@@ -2,7 +2,7 @@
 #
 # Thin `ccall` wrapper over libvcmi.so (include/vcmi.h).  It keeps the reference's exported names, signatures and
 # the struct fields its own code reads (reference src/VoiceConversion.jl:12-38, src/dtw.jl:7):
-#   GMMMapParam, GMMMap (fields params, px), fvconvert, vc, dim, ncomponents, predict_proba(g.px, X),
+#   GMMMapParam, GMMMap (fields params, px), GMMMapBlockDiag (field px), fvconvert, vc, dim, ncomponents, predict_proba(g.px, X),
 #   predict(g.px, X), TrajectoryGMMMap, TrajectoryGVGMMMap, DTW, fit!, update!, set_template!, backward, align,
 #   align_mcep, push_delta, VarianceScaling, fvpostf, fvpostf!, diffgmm(params)
 # and adds the batch methods the reference lacks (fvconvert(g, X::Matrix), fit!(d, templates, sequences),
@@ -18,7 +18,7 @@ module VoiceConversionMI
 
 import LinearAlgebra
 
-export DeviceMatrix, FrameByFrameConverter, TrajectoryConverter, GMMMapParam, GMMMap, TrajectoryGMMMap, TrajectoryGVGMMMap,
+export DeviceMatrix, FrameByFrameConverter, TrajectoryConverter, GMMMapParam, GMMMap, GMMMapBlockDiag, slopes, TrajectoryGMMMap, TrajectoryGVGMMMap,
        fvconvert, vc, ncomponents, dim, em_iters, em_iters!, traj_precision, traj_precision!, cond_loglik, em_history,
        VarianceScaling, fvpostf!, fvpostf,
        align, align_mcep, push_delta, GVDataset, sp2mc, mc2sp, mc2b,
@@ -261,6 +261,94 @@ function diffgmm(p::GMMMapParam)
     μˣ, μʸ, Σˣˣ, Σˣʸ, Σʸˣ, Σʸʸ = split_joint_gmm(μd, Σd)
     GMMMapParam(p.weights, μˣ, μʸ, Σˣˣ, Σˣʸ, Σʸˣ, Σʸʸ)
 end
+
+# ------------------------------------------------------------------------------------ GMMMapBlockDiag
+# Not in the reference: frame-by-frame conversion with the CROSS-DIAGONAL joint model (Σˣˣ, Σˣʸ, Σʸˣ, Σʸʸ each diagonal) that
+# GMMEMBlockDiag trains, as it is -- Σ is (Dj + Dj/2, M) = [variances; pair cross-covariances], no (Dj,Dj,M) tensor is built
+# (include/vcmi.h: vcmi_bdmap_*).  Converts on the device it was created on.
+mutable struct BlockDiagGMM                                            # g.px of a GMMMapBlockDiag
+    h::Ptr{Cvoid}
+    D::Int
+    M::Int
+    owner::Any
+end
+
+mutable struct GMMMapBlockDiag <: FrameByFrameConverter
+    px::BlockDiagGMM
+    h::Ptr{Cvoid}
+end
+
+function GMMMapBlockDiag(weights::Vector{Float64}, μ::Matrix{Float64}, Σ::Matrix{Float64}; swap::Bool=false)
+    Dj, M = size(μ)
+    (iseven(Dj) && Dj >= 2) || throw(DimensionMismatch("the joint dimension must be even"))
+    (length(weights) == M && size(Σ) == (Dj + div(Dj, 2), M)) || throw(DimensionMismatch("weights, μ, Σ (Dj + Dj/2, M) are inconsistent"))
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ccall((:vcmi_bdmap_create, libvcmi), Cint,
+                (Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Cint, Cint, Cint, Ref{Ptr{Cvoid}}),
+                weights, μ, Σ, Dj, M, swap ? 1 : 0, h))
+    g = GMMMapBlockDiag(BlockDiagGMM(h[], div(Dj, 2), M, nothing), h[])
+    g.px.owner = g
+    finalizer(x -> ccall((:vcmi_bdmap_destroy, libvcmi), Cint, (Ptr{Cvoid},), x.h), g)
+    g
+end
+
+Base.length(g::GMMMapBlockDiag) = 1
+dim(g::GMMMapBlockDiag) = Int(ccall((:vcmi_bdmap_dim, libvcmi), Cint, (Ptr{Cvoid},), g.h))
+ncomponents(g::GMMMapBlockDiag) = Int(ccall((:vcmi_bdmap_ncomponents, libvcmi), Cint, (Ptr{Cvoid},), g.h))
+Base.size(g::GMMMapBlockDiag) = (dim(g), length(g))
+
+# the regression slopes a = c ./ vˣ (D,M): the diagonals of GMMMap's ΣʸˣΣˣˣ⁻¹
+function slopes(g::GMMMapBlockDiag)
+    a = Matrix{Float64}(undef, dim(g), ncomponents(g))
+    check(ccall((:vcmi_bdmap_get_a, libvcmi), Cint, (Ptr{Cvoid}, Ptr{Float64}), g.h, a))
+    a
+end
+
+function fvconvert(g::GMMMapBlockDiag, x::Vector{Float64})
+    length(x) == dim(g) || throw(DimensionMismatch("Inconsistent dimentions."))
+    y = Vector{Float64}(undef, dim(g))
+    check(ccall((:vcmi_bdmap_convert, libvcmi), Cint,
+                (Ptr{Cvoid}, Ptr{Float64}, Int64, Int64, Ptr{Float64}, Int64), g.h, x, dim(g), 1, y, dim(g)))
+    y
+end
+
+function fvconvert(g::GMMMapBlockDiag, X::Matrix{Float64})
+    size(X, 1) == dim(g) || throw(DimensionMismatch("Inconsistent dimentions."))
+    Y = similar(X)
+    check(ccall((:vcmi_bdmap_convert, libvcmi), Cint,
+                (Ptr{Cvoid}, Ptr{Float64}, Int64, Int64, Ptr{Float64}, Int64),
+                g.h, X, size(X, 1), size(X, 2), Y, size(Y, 1)))
+    Y
+end
+
+# vc(c::FrameByFrameConverter, fm) -- src/common.jl:7-26 (row 1 = power, kept)
+function vc(g::GMMMapBlockDiag, fm::Matrix{Float64})
+    size(fm, 1) == dim(g) + 1 || throw(DimensionMismatch("Inconsistent dimentions."))
+    out = similar(fm)
+    check(ccall((:vcmi_vc_bdmap, libvcmi), Cint, (Ptr{Cvoid}, Ptr{Float64}, Int64, Ptr{Float64}, Ptr{Float64}),
+                g.h, fm, size(fm, 2), C_NULL, out))
+    out
+end
+
+function predict_proba!(r::Matrix{Float64}, gmm::BlockDiagGMM, X::Matrix{Float64})
+    size(X, 1) == gmm.D || throw(DimensionMismatch("Inconsistent dimentions."))
+    size(r) == (gmm.M, size(X, 2)) || throw(DimensionMismatch("posterior matrix must be (M,T)"))
+    check(ccall((:vcmi_bdmap_posterior, libvcmi), Cint, (Ptr{Cvoid}, Ptr{Float64}, Int64, Int64, Ptr{Float64}),
+                gmm.h, X, size(X, 1), size(X, 2), r))
+    r
+end
+predict_proba(gmm::BlockDiagGMM, X::Matrix{Float64}) = predict_proba!(Matrix{Float64}(undef, gmm.M, size(X, 2)), gmm, X)
+predict_proba(gmm::BlockDiagGMM, x::Vector{Float64}) = vec(predict_proba(gmm, reshape(x, length(x), 1)))
+
+function predict!(r::Vector{Int}, gmm::BlockDiagGMM, X::Matrix{Float64})
+    size(X, 1) == gmm.D || throw(DimensionMismatch("Inconsistent dimentions."))
+    length(r) == size(X, 2) || throw(DimensionMismatch("label vector must have one entry per frame"))
+    check(ccall((:vcmi_bdmap_predict, libvcmi), Cint, (Ptr{Cvoid}, Ptr{Float64}, Int64, Int64, Ptr{Int64}),
+                gmm.h, X, size(X, 1), size(X, 2), r))
+    r
+end
+predict(gmm::BlockDiagGMM, X::Matrix{Float64}) = predict!(Vector{Int}(undef, size(X, 2)), gmm, X)
+predict(gmm::BlockDiagGMM, x::Vector{Float64}) = predict(gmm, reshape(x, length(x), 1))[1]
 
 # ---------------------------------------------------------------------------------- TrajectoryGMMMap
 mutable struct TrajectoryGMMMap <: TrajectoryConverter                 # src/trajectory_gmmmap.jl:3
@@ -578,6 +666,14 @@ function vc(g::GMMMap, fm::Matrix{Float64}, vs::VarianceScaling)
                 g.h, fm, size(fm, 2), vs.σ², out))
     out
 end
+function vc(g::GMMMapBlockDiag, fm::Matrix{Float64}, vs::VarianceScaling)
+    size(fm, 1) == dim(g) + 1 || throw(DimensionMismatch("Inconsistent dimentions."))
+    length(vs.σ²) == dim(g) || throw(DimensionMismatch("σ² must have one entry per converted feature row"))
+    out = similar(fm)
+    check(ccall((:vcmi_vc_bdmap, libvcmi), Cint, (Ptr{Cvoid}, Ptr{Float64}, Int64, Ptr{Float64}, Ptr{Float64}),
+                g.h, fm, size(fm, 2), vs.σ², out))
+    out
+end
 # vc(t, fm, vs; delta): vs === nothing is the plain conversion.  delta=true: fm holds the STATIC features (D+1,T) and the
 # library builds [fm[1,:]; push_delta(fm[2:end,:])] on the device over the WHOLE matrix before the chunks are cut --
 # bin/vc.jl:75-82 in one call (frame kL+1 takes its delta from frame kL of the previous chunk)
@@ -631,6 +727,18 @@ function vc(g::GMMMap, fms::Vector{Matrix{Float64}}, vs::Union{VarianceScaling,N
     outs = [similar(fm) for fm in fms]
     GC.@preserve fms outs σ² begin
         check(ccall((:vcmi_vc_frames_batch, libvcmi), Cint,
+                    (Ptr{Cvoid}, Int64, Ptr{Ptr{Float64}}, Ptr{Int64}, Ptr{Float64}, Ptr{Ptr{Float64}}),
+                    g.h, length(fms), pointer.(fms), T, σ²pointer(vs, σ²), pointer.(outs)))
+    end
+    outs
+end
+function vc(g::GMMMapBlockDiag, fms::Vector{Matrix{Float64}}, vs::Union{VarianceScaling,Nothing}=nothing)
+    all(size(fm, 1) == dim(g) + 1 for fm in fms) || throw(DimensionMismatch("Inconsistent dimentions."))
+    σ² = σ²vector(vs, dim(g))
+    T = Int64[size(fm, 2) for fm in fms]
+    outs = [similar(fm) for fm in fms]
+    GC.@preserve fms outs σ² begin
+        check(ccall((:vcmi_vc_bdmap_batch, libvcmi), Cint,
                     (Ptr{Cvoid}, Int64, Ptr{Ptr{Float64}}, Ptr{Int64}, Ptr{Float64}, Ptr{Ptr{Float64}}),
                     g.h, length(fms), pointer.(fms), T, σ²pointer(vs, σ²), pointer.(outs)))
     end

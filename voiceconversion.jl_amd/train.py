@@ -24,8 +24,8 @@ Tokuda 2007): Dj is even, D = Dj/2, dimension d couples with dimension d + D onl
 keeps covars (Dj + D, M) = [variances; cross-covariances c_dm]; the statistics are the M(1 + 2Dj + D) + 1 doubles of the
 block-diagonal E-step, the initial covariances the variances and pair covariances of the data + min_covar on the variances --
 for init="kmeans" from the M=1 block-diagonal E-step statistics (data_block_covariance).  expand_block_diag gives the
-(Dj,Dj,M) tensor that GMMMap and refine= of the full fit take; TrajectoryGMMMap(precision="diag") converts with such a model
-exactly.
+(Dj,Dj,M) tensor that GMMMap and refine= of the full fit take; BlockDiagGMMMap(weights, means, covars) converts frame by
+frame with the result as it is (no expansion), TrajectoryGMMMap(precision="diag") converts with such a model exactly.
 
 One driver serves the three types.  train_gmm holds the only EM loop, the only best-of-n_init selection and the only
 pack / broadcast / unpack of rank 0's model (pack_model, unpack_model: a third parameter of any shape); what differs between
@@ -143,7 +143,8 @@ class BlockDiagEMState(_EMState):
 
 def expand_block_diag(covars):
     """covars (Dj + D, M) of a cross-diagonal model -> the (Dj,Dj,M) covariance tensor: the variances on the diagonals, c at
-    (d, d + D) and (d + D, d).  What GMMMap and train_gmm(X, refine=(w, mu, expand_block_diag(covars))) take."""
+    (d, d + D) and (d + D, d).  What GMMMap and train_gmm(X, refine=(w, mu, expand_block_diag(covars))) take; the native
+    frame-by-frame converter of such a model, BlockDiagGMMMap, takes covars itself."""
     v = np.asarray(covars, dtype=np.float64)
     if v.ndim != 2 or v.shape[0] % 3:
         raise _lib.DimensionMismatch(f"expand_block_diag: covars must be (Dj + Dj/2, M), got {v.shape}")

@@ -6,6 +6,7 @@ import numpy as np
 from . import _lib
 from ._arrays import current_stream_ptr, dev_matrix, is_torch, jl_matrix, sigma2_arg
 from .common import TrajectoryConverter
+from .gmmmap_bdiag import BlockDiagGMMMap
 
 
 def constructW(D, T):
@@ -131,6 +132,9 @@ class TrajectoryGMMMap(TrajectoryConverter):
     _PRECISIONS = ("full", "diag")          # VCMI_TRAJ_PRECISION_FULL, VCMI_TRAJ_PRECISION_DIAG
 
     def __init__(self, g, T, em_iters=0, precision="full"):
+        if isinstance(g, BlockDiagGMMMap):
+            raise TypeError("TrajectoryGMMMap takes a GMMMap, not a BlockDiagGMMMap: build it from "
+                            "GMMMap(weights, mu, expand_block_diag(covars)) (precision=\"diag\" then converts with the model exactly)")
         self.gmmmap = g
         h = C.c_void_p()
         _lib.check(_lib.lib.vcmi_traj_create(g._h, int(T), C.byref(h)))
