@@ -431,6 +431,22 @@ typedef struct vcmi_traj vcmi_traj;
 /* TrajectoryGMMMap(g, T): g's dim is 2D (static+delta); precomputes Dy_m = inv(Sigma^yy_m - A_m Sigma^xy_m)
  * (:24-28).  T only sets length(t) (:34); W is a stencil and is never materialised.  g must outlive t. */
 int vcmi_traj_create(vcmi_gmmmap *g, int64_t T, vcmi_traj **out);
+/* TrajectoryGMMMap straight from a cross-diagonal model over static+delta features (dim(b) = 2D, the joint model has
+ * Dj = 4D and joint row k is coupled with row k + 2D only).  The conditional covariance of such a model is diagonal exactly:
+ * q_km = 1 / (vy_km - a_km c_km), a = c / vx, so the result is an ordinary vcmi_traj whose precision is VCMI_TRAJ_PRECISION_DIAG
+ * for good -- every entry that takes a vcmi_traj* (vcmi_traj_convert[_batch[_dev]], the vcmi_vc_traj family,
+ * vcmi_vc_traj_batch[_dev]) converts with it through the tridiagonal solver.  The dense model is never formed, on the host or
+ * on the device: the handle holds q (2D M doubles) and the per-call scratch (mhat, g, workspace, descriptors); the arg-max
+ * and g_t = q_mhat (.) (mu_y + a (x - mu_x)) of a call are one pass of b's kernel (csrc/gmmmap_bdiag.hip, mode 3), which reads
+ * b's log-density table and a [M][2D][mu_x, a, mu_y, q] table that vcmi_bdmap_create uploads.  mhat is the first maximum of
+ * the centred log-density of vcmi_bdmap_predict.  Equal to vcmi_traj_create over the expanded model with
+ * vcmi_traj_set_precision(DIAG) to rounding.  b must outlive t.
+ * VCMI_ERR_DIM: dim(b) odd.  VCMI_ERR_NOT_PD: a conditional variance that is zero, negative or not finite in FP64 (a valid pair
+ * with |c| within rounding of sqrt(vx vy)); the message names the pair.  The handle follows vcmi_bdmap's device rule: it
+ * converts on the device b was created on, a device group does not shard its calls, a call from another device is
+ * VCMI_ERR_ARG.  VCMI_ERR_ARG, the handle usable afterwards: vcmi_traj_set_precision(t, FULL), vcmi_traj_set_em(t, n > 0),
+ * vcmi_traj_cond_loglik[_dev], and every convert entry of a vcmi_trajgv over t. */
+int vcmi_traj_create_bdiag(vcmi_bdmap *b, int64_t T, vcmi_traj **out);
 int vcmi_traj_destroy(vcmi_traj *t);
 /* length(t).  As in the reference, fvconvert rebuilds W when the sequence length differs (src/trajectory_gmmmap.jl:70-72),
  * so after vcmi_traj_convert(t, X, T, Y) the length is T, and after vcmi_vc_traj it is the length of the last chunk --

@@ -139,6 +139,7 @@ SIGNATURES = {
     "vcmi_kmeans_seed_trials": (_int, [_vp, _vp, _i64, _vp, _int, _vp, _dp]),
     "vcmi_kmeans_mind2_dev": (_int, [_vp, _i64, _vp, _vp]),
     "vcmi_traj_create": (_int, [_vp, _i64, C.POINTER(_vp)]),
+    "vcmi_traj_create_bdiag": (_int, [_vp, _i64, C.POINTER(_vp)]),
     "vcmi_traj_destroy": (_int, [_vp]),
     "vcmi_traj_length": (_i64, [_vp]),
     "vcmi_traj_convert": (_int, [_vp, _dp, _i64, _dp]),

@@ -8,7 +8,8 @@
 //   y_dt = sum_m p_tm (muy_dm + a_dm (x_dt - mux_dm)),  a = c / vx
 // about 6 D M FP64 vector operations per frame where the dense converter issues M (3 D^2 + 6 D) flop.
 //
-// One kernel, three modes (0 fvconvert, 1 predict_proba, 2 predict), one launch per call.  A workgroup of eight waves takes
+// One kernel, four modes (0 fvconvert, 1 predict_proba, 2 predict, 3 the arg-max + g_t pass of trajectory conversion straight
+// from the model: below), one launch per call.  A workgroup of eight waves takes
 // FB consecutive frames (64; 32 where the two tiles below would not fit the LDS of a CU), lane = frame:
 //   stage    the frames, read once, transposed into LDS: xs[d][frame]
 //   phase 1  wave w takes the mixtures 4 w .. 4 w + 3, then + 32, ...: one LDS read of x_d serves four mixtures, whose
@@ -19,21 +20,20 @@
 //   phase 3  wave w takes the dimensions 2 w, 2 w + 1, then + 16, ...: y over all mixtures, the posteriors read from LDS once
 //            per pair of dimensions; y replaces x in xs (each element is read and written by the same lane)
 //   store    y (or P, or the index), written once, consecutive lanes on consecutive addresses
+// Mode 3 (vcmi_traj_create_bdiag) shares the staging, phase 1 and mode 2's first-maximum reduction; the index
+// goes to LDS as well as to HBM, and in place of phase 3
+//   phase 3t thread (part, frame): g_d = q_d,mhat (mu_y + a (x_d - mu_x)) for the dimensions part, part + NP, ... and the frame's
+//            OWN mixture only -- the mixture is per lane now, so the [mu_x, a, mu_y, q] row of (mhat, d) is a 32-byte gather
+//            from prm4; the lanes of a wave are consecutive frames, which mostly share a mixture: one or two cache lines per load
+// then the same store.
 // Nothing per (frame, mixture) goes to HBM.  Every index is a function of (D, M, T, ld) and the thread alone; a frame's
 // arithmetic does not depend on its lane, its workgroup or the other frames: no atomics, same bits in every call.
+#include "gmmmap_bdiag_handle.hpp"
 #include "gmmmap_bdiag_prepare.hpp"
 #include "hostpipe.hpp"
 #include "postf.hpp"
 
 #include <cmath>
-
-// The handle converts on the device it was created on: device groups (vcmi_set_devices) do not shard its calls.
-struct vcmi_bdmap {
-  int D = 0, DP = 0, M = 0, device = 0;
-  int FB = 64;                        // frames per workgroup
-  vcmi::DevBuf<double> prm1, prm3, cst;      // BdmapTable's, resident
-  std::vector<double> h_a;            // (D,M)
-};
 
 namespace vcmi {
 
@@ -42,14 +42,25 @@ static constexpr size_t kBdmLdsBudget = 160 * 1024;
 // chunks of the host pipeline hold at least this many frames (as the dense converter's: one full round of workgroups)
 static constexpr int64_t kBdmMinChunkFrames = 98304;
 
+typedef double bdm_d4 __attribute__((ext_vector_type(4)));
+
 static size_t bdmap_lds_bytes(int DP, int M, int FB) {
   return ((size_t)DP * (FB + 1) + (size_t)M * FB + kBdmThreads) * sizeof(double) + kBdmThreads * sizeof(int);
+}
+
+// the tile in xs, written once: consecutive lanes on consecutive addresses
+template <int FB>
+__device__ __forceinline__ void bdmap_store_tile(const double *xs, double *Y, int64_t ldy, int64_t f0, int nf, int D, int DP) {
+  for (int i = threadIdx.x; i < FB * DP; i += kBdmThreads) {
+    const int yf = i / DP, d = i - yf * DP;
+    if (yf < nf && d < D) Y[(f0 + yf) * ldy + d] = xs[d * (FB + 1) + yf];
+  }
 }
 
 template <int MODE, int FB>
 __global__ void __launch_bounds__(kBdmThreads)
 bdmap_kernel(const double *X, int64_t ldx, int64_t T, int D, int DP, int M, const double *__restrict__ prm1,
-             const double *__restrict__ prm3, const double *__restrict__ cst, void *out, int64_t ldy) {
+             const double *__restrict__ prm3, const double *__restrict__ cst, void *out, int64_t ldy, int64_t *mhat) {
   extern __shared__ double lds[];
   constexpr int RS = FB + 1, NS = 64 / FB, NP = kBdmThreads / FB, NW = kBdmThreads / 64;
   double *xs = lds;                               // [DP][RS]
@@ -98,7 +109,7 @@ bdmap_kernel(const double *X, int64_t ldx, int64_t T, int D, int DP, int M, cons
 
   // phase 2
   const int fr = tid & (FB - 1), part = tid / FB;
-  if (MODE == 2) {
+  if (MODE >= 2) {
     double best = -INFINITY;
     int bi = M;
     for (int m = part; m < M; m += NP) {
@@ -111,7 +122,7 @@ bdmap_kernel(const double *X, int64_t ldx, int64_t T, int D, int DP, int M, cons
     red[part * FB + fr] = best;
     redi[part * FB + fr] = bi;
     __syncthreads();
-    if (part == 0 && fr < nf) {
+    if (part == 0 && (MODE == 3 || fr < nf)) {
       for (int k = 1; k < NP; ++k) {
         const double v = red[k * FB + fr];
         const int i = redi[k * FB + fr];
@@ -120,8 +131,25 @@ bdmap_kernel(const double *X, int64_t ldx, int64_t T, int D, int DP, int M, cons
           bi = i;
         }
       }
-      reinterpret_cast<int64_t *>(out)[f0 + fr] = (bi < M) ? bi + 1 : 1;     // (no log-density above -inf: a NaN frame)
+      if (MODE == 2) reinterpret_cast<int64_t *>(out)[f0 + fr] = (bi < M) ? bi + 1 : 1;     // (no log-density above -inf: a NaN frame)
+      if (MODE == 3) {
+        if (bi >= M) bi = 0;
+        redi[fr] = bi;                  // (slot 0 of the frame: written, and read before, by this thread alone)
+        if (fr < nf) mhat[f0 + fr] = bi + 1;
+      }
     }
+    if (MODE == 2) return;
+    __syncthreads();
+    // phase 3t: prm3 is the trajectory table here, [M][DP][mu_x, a, mu_y, q]; the rows of the tile's padding frames (x = 0,
+    // some mixture of the model) and of the padding dimensions (zeros) are computed and never stored
+    const double *tp = prm3 + (size_t)redi[fr] * DP * kBdmapPrm4;
+#pragma unroll 4
+    for (int d = part; d < DP; d += NP) {
+      const bdm_d4 r = *reinterpret_cast<const bdm_d4 *>(tp + (size_t)d * kBdmapPrm4);
+      xs[d * RS + fr] = r[3] * fma(r[1], xs[d * RS + fr] - r[0], r[2]);
+    }
+    __syncthreads();
+    bdmap_store_tile<FB>(xs, reinterpret_cast<double *>(out), ldy, f0, nf, D, DP);
     return;
   }
   {
@@ -175,27 +203,25 @@ bdmap_kernel(const double *X, int64_t ldx, int64_t T, int D, int DP, int M, cons
     }
   }
   __syncthreads();
-  double *Y = reinterpret_cast<double *>(out);
-  for (int i = tid; i < FB * DP; i += kBdmThreads) {
-    const int yf = i / DP, d = i - yf * DP;
-    if (yf < nf && d < D) Y[(f0 + yf) * ldy + d] = xs[d * RS + yf];
-  }
+  bdmap_store_tile<FB>(xs, reinterpret_cast<double *>(out), ldy, f0, nf, D, DP);
 }
 
 template <int MODE, int FB>
-static int bdmap_launch(const vcmi_bdmap *h, const double *dX, int64_t ldx, int64_t T, void *out, int64_t ldy, hipStream_t st) {
+static int bdmap_launch(const vcmi_bdmap *h, const double *dX, int64_t ldx, int64_t T, void *out, int64_t ldy, hipStream_t st,
+                        int64_t *mhat = nullptr) {
   static std::atomic<bool> attr_done[64];
   VCMI_TRY(set_max_dynamic_lds(bdmap_kernel<MODE, FB>, bdmap_lds_bytes(kBdmapMaxD, FB == 64 ? 128 : kBdmapMaxM, FB), attr_done));
   const int64_t nb = (T + FB - 1) / FB;
   hipLaunchKernelGGL((bdmap_kernel<MODE, FB>), dim3((unsigned)nb), dim3(kBdmThreads), bdmap_lds_bytes(h->DP, h->M, FB), st, dX, ldx, T,
-                     h->D, h->DP, h->M, h->prm1.p, h->prm3.p, h->cst.p, out, ldy);
+                     h->D, h->DP, h->M, h->prm1.p, MODE == 3 ? h->prm4.p : h->prm3.p, h->cst.p, out, ldy, mhat);
   VCMI_HIP(hipGetLastError());
   return VCMI_OK;
 }
 
-// mode 0: out = Y (leading dimension ldy), 1: out = P [T][M], 2: out = int64 indices; asynchronous on st
+// mode 0: out = Y (leading dimension ldy), 1: out = P [T][M], 2: out = int64 indices, 3: out = G (ldy) and the indices to mhat;
+// asynchronous on st
 static int bdmap_device(const vcmi_bdmap *h, int mode, const double *dX, int64_t ldx, int64_t T, void *out, int64_t ldy,
-                        hipStream_t st) {
+                        hipStream_t st, int64_t *mhat = nullptr) {
   if (T == 0) return VCMI_OK;
   int dev = 0;
   VCMI_HIP(hipGetDevice(&dev));
@@ -205,10 +231,12 @@ static int bdmap_device(const vcmi_bdmap *h, int mode, const double *dX, int64_t
   if (h->FB == 64) {
     if (mode == 0) return bdmap_launch<0, 64>(h, dX, ldx, T, out, ldy, st);
     if (mode == 1) return bdmap_launch<1, 64>(h, dX, ldx, T, out, ldy, st);
+    if (mode == 3) return bdmap_launch<3, 64>(h, dX, ldx, T, out, ldy, st, mhat);
     return bdmap_launch<2, 64>(h, dX, ldx, T, out, ldy, st);
   }
   if (mode == 0) return bdmap_launch<0, 32>(h, dX, ldx, T, out, ldy, st);
   if (mode == 1) return bdmap_launch<1, 32>(h, dX, ldx, T, out, ldy, st);
+  if (mode == 3) return bdmap_launch<3, 32>(h, dX, ldx, T, out, ldy, st, mhat);
   return bdmap_launch<2, 32>(h, dX, ldx, T, out, ldy, st);
 }
 
@@ -219,6 +247,10 @@ static int bdmap_check_xy(const vcmi_bdmap *h, const void *X, int64_t ldx, int64
   if (ldx < h->D) return fail(VCMI_ERR_DIM, "%s: Inconsistent dimensions (leading dimension %lld < dim %d)", who, (long long)ldx, h->D);
   if (ldy < h->D) return fail(VCMI_ERR_DIM, "%s: ldy %lld < dim %d", who, (long long)ldy, h->D);
   return VCMI_OK;
+}
+
+int bdmap_traj_device(const vcmi_bdmap *h, const double *dX, int64_t T, int64_t *mhat, double *G, hipStream_t st) {
+  return bdmap_device(h, 3, dX, h->D, T, G, h->D, st, mhat);
 }
 
 }  // namespace vcmi
@@ -252,11 +284,14 @@ extern "C" int vcmi_bdmap_create(const double *weights, const double *mu, const 
   int rc = upload_now(h->prm1, t.prm1);
   if (rc == VCMI_OK) rc = upload_now(h->prm3, t.prm3);
   if (rc == VCMI_OK) rc = upload_now(h->cst, t.cst);
+  if (rc == VCMI_OK) rc = upload_now(h->prm4, t.prm4);
   if (rc != VCMI_OK) {
     delete h;
     return rc;
   }
   h->h_a = std::move(t.a);
+  h->h_q = std::move(t.q);
+  h->q_bad = t.q_bad;
   *out = h;
   return VCMI_OK;
 }

@@ -20,6 +20,9 @@ int64_t bdmap_prepare(const double *weights, const double *mu, const double *cov
   out->prm3.assign((size_t)M * DP * kBdmapPrm3, 0.0);
   out->cst.assign((size_t)M, 0.0);
   out->a.assign((size_t)M * D, 0.0);
+  out->q.assign((size_t)M * D, 0.0);
+  out->prm4.assign((size_t)M * DP * kBdmapPrm4, 0.0);
+  out->q_bad = -1;
   const int xo = swap ? D : 0, yo = swap ? 0 : D;       // rows of the source and of the target half
   for (int m = 0; m < M; ++m) {
     const double *mm = mu + (size_t)m * Dj, *cv = covars + (size_t)m * (Dj + D);
@@ -32,6 +35,15 @@ int64_t bdmap_prepare(const double *weights, const double *mu, const double *cov
       p3[1] = c / vx;
       p3[2] = mm[yo + d];
       out->a[(size_t)m * D + d] = p3[1];
+      // the conditional variance v_y - a c with one rounding, whatever the compiler contracts elsewhere
+      const double cvar = std::fma(-p3[1], c, cv[yo + d]), q = 1.0 / cvar;
+      if (!(cvar > 0.0 && std::isfinite(cvar)) && out->q_bad < 0) out->q_bad = d + (int64_t)D * m;
+      double *p4 = out->prm4.data() + ((size_t)m * DP + d) * kBdmapPrm4;
+      p4[0] = p3[0];
+      p4[1] = p3[1];
+      p4[2] = p3[2];
+      p4[3] = q;
+      out->q[(size_t)m * D + d] = q;
       const double lv = std::log(vx), t = s + lv;
       comp += (std::fabs(s) >= std::fabs(lv)) ? (s - t) + lv : (lv - t) + s;
       s = t;

@@ -10,6 +10,7 @@ namespace vcmi {
 constexpr int kBdmapMaxD = 128, kBdmapMaxM = 256;   // what the cross-diagonal training can produce (estep_internal.hpp)
 constexpr int kBdmapPrm1 = 2;                       // doubles per (mixture, dimension) of the log-density table
 constexpr int kBdmapPrm3 = 4;                       // ... and of the regression table
+constexpr int kBdmapPrm4 = 4;                       // ... and of the trajectory table
 
 struct BdmapTable {
   int D = 0, DP = 0, M = 0;        // DP: D rounded up to a multiple of 4 (the log-density pass takes four dimensions at once)
@@ -22,6 +23,17 @@ struct BdmapTable {
   // (Neumaier) accumulator; -infinity for w_m <= 0
   std::vector<double> cst;
   std::vector<double> a;           // (D,M), dimension fastest: vcmi_bdmap_get_a
+  // What trajectory conversion straight from the model reads (vcmi_traj_create_bdiag); the frame-by-frame
+  // passes read none of it.  The conditional covariance of a cross-diagonal model is diagonal exactly:
+  // q[d + D m] = 1 / fma(-a, c, v_y), the reciprocal conditional variance, (D,M) dimension fastest -- the [M][2 D_static]
+  // table the tridiagonal solver indexes (traj_diag.hip);
+  // prm4[(m DP + d) 4 + .] = [mu_x, a, mu_y, q], one 32-byte row per (mixture, dimension) for the per-frame gather of the
+  // fused arg-max + g_t pass; rows d >= D are zeros.
+  // q_bad: index d + D m of the first pair in memory order whose conditional variance is zero, negative or not finite in
+  // FP64 (a valid pair can round there: |c| within an ulp of sqrt(v_x v_y)), -1: none.  The entries of such a pair hold what
+  // the division gave.
+  std::vector<double> q, prm4;
+  int64_t q_bad = -1;
 };
 
 // weights (M), mu (Dj,M), covars (Dj + D, M) = [variances of the Dj rows | D pair cross-covariances], D = Dj / 2 (the caller

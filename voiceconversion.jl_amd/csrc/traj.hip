@@ -201,11 +201,13 @@ int traj_run(vcmi_traj *t, std::vector<TrajUtt> &utts, int64_t nframes, bool con
   VCMI_TRY(t->mhat.reserve((size_t)nframes));
   VCMI_TRY(t->gbuf.reserve((size_t)nframes * D2));
   // (1) mhat = predict(g.px, X), src/trajectory_gmmmap.jl:82
-  const bool g_mfma = t->NT <= 6 && !debug_flag(kDbgTrajGScalar);   // g_t on MFMA tiles (one workgroup per utterance)
+  // g_t on MFMA tiles (one workgroup per utterance); a cross-diagonal handle has made g_t in the arg-max pass
+  const bool g_mfma = !t->b && t->NT <= 6 && !debug_flag(kDbgTrajGScalar);
   // diagonal conditional precisions: the same g_t kernels on the images of diag(q_m), then the tridiagonal solver
   const bool diag = t->precision == VCMI_TRAJ_PRECISION_DIAG;
   const double *QT = diag ? t->dg_QT.p : t->QT.p, *Qfrag = diag ? t->dg_Qfrag.p : t->Qfrag.p;
   auto arg_max = [&](const double *X, int64_t T, int64_t f0) -> int {     // ... and g_t where the scalar kernel runs
+    if (t->b) return bdmap_traj_device(t->b, X, T, t->mhat.p + f0, t->gbuf.p + (size_t)f0 * D2, st);   // both, fused
     VCMI_TRY(gmmmap_predict_device(t->g, X, D2, T, t->mhat.p + f0, st, /*allow_screen=*/false));
     if (!g_mfma)
       hipLaunchKernelGGL(traj_g_kernel, dim3((unsigned)T), dim3(128), 2 * D2 * sizeof(double), st, X, T, D2, t->mhat.p + f0, t->AT.p,
@@ -227,7 +229,7 @@ int traj_run(vcmi_traj *t, std::vector<TrajUtt> &utts, int64_t nframes, bool con
   VCMI_TRY(upload_now(t->uttbuf.p, utts.data(), sizeof(TrajUtt) * n));
   const TrajUtt *du = reinterpret_cast<const TrajUtt *>(t->uttbuf.p);
   if (g_mfma) {
-    const int cus = t->g->cus;
+    const int cus = t->g->cus;      // (g_mfma: never a cross-diagonal handle, whose g is NULL)
     VCMI_TRY(t->gperm.reserve((size_t)nframes + (size_t)16 * t->M * n));
     const int nthr = 64 * t->NT;
     const size_t shg = ((size_t)4 * t->KS * 16 + (size_t)4 * t->NT * 64) * sizeof(double) + (2 + (size_t)t->NT) * (size_t)t->M * sizeof(int);
@@ -315,12 +317,16 @@ static void reset_stale_replicas(H *h) {
 }
 
 static void traj_sync_replicas(vcmi_traj *t) {
-  gmmmap_sync_replicas(t->g);
+  if (!t->b) gmmmap_sync_replicas(t->g);
   reset_stale_replicas(t);
 }
 
 // member i's trajectory converter: t itself when member i got t's own GMMMap, else a replica over the member's GMMMap
 static int traj_member(vcmi_traj *t, int member, vcmi_traj **out) {
+  if (t->b) {     // (traj_host_batch keeps such a handle on its own device)
+    *out = t;
+    return VCMI_OK;
+  }
   vcmi_gmmmap *g = nullptr;
   VCMI_TRY(gmmmap_member(t->g, member, &g));
   if (g == t->g) {
@@ -352,7 +358,8 @@ int traj_host_batch(vcmi_traj *t, int64_t n, const double *const *X, const int64
     if (T[u] > 0 && (!X[u] || !Y[u])) return fail(VCMI_ERR_ARG, "trajectory: NULL matrix");
   }
   const int m = group_size();
-  if (m == 0 || n < kGroupMinUtts) return traj_host_batch_local(t, n, X, T, Y, gv);
+  // a cross-diagonal handle follows vcmi_bdmap's rule: it converts on the device it was created on, groups do not shard it
+  if (m == 0 || n < kGroupMinUtts || t->b) return traj_host_batch_local(t, n, X, T, Y, gv);
   traj_sync_replicas(t);
   if (gvh) reset_stale_replicas(gvh);
   std::vector<int64_t> costs((size_t)n);
@@ -436,6 +443,34 @@ extern "C" int vcmi_traj_create(vcmi_gmmmap *g, int64_t T, vcmi_traj **out) {
     const hipError_t e = upload_now_hip(im.dev.p, im.host.data(), im.host.size() * 8);
     if (e != hipSuccess) return fail(VCMI_ERR_HIP, im.msg, hipGetErrorString(e));
   }
+  *out = t.release();
+  return VCMI_OK;
+}
+
+// TrajectoryGMMMap straight from a cross-diagonal model: the conditional covariance of every mixture is
+// diagonal exactly, so the converter IS a diagonal-precision one -- q from the pairs (gmmmap_bdiag_prepare.cpp), nothing dense.
+extern "C" int vcmi_traj_create_bdiag(vcmi_bdmap *b, int64_t T, vcmi_traj **out) {
+  if (!b || !out) return fail(VCMI_ERR_ARG, "vcmi_traj_create_bdiag: NULL argument");
+  *out = nullptr;
+  if (b->D & 1) return fail(VCMI_ERR_DIM, "TrajectoryGMMMap: dim(g) = %d must be even (static + delta)", b->D);
+  if (T < 0) return fail(VCMI_ERR_ARG, "TrajectoryGMMMap: negative length");
+  if (b->q_bad >= 0)
+    return fail(VCMI_ERR_NOT_PD, "vcmi_traj_create_bdiag: the conditional variance of pair (%d,%d) is not positive and finite",
+                (int)(b->q_bad % b->D) + 1, (int)(b->q_bad / b->D) + 1);
+  int dev = 0;
+  VCMI_HIP(hipGetDevice(&dev));
+  if (dev != b->device)
+    return fail(VCMI_ERR_ARG, "vcmi_traj_create_bdiag: the handle was created on device %d, the call runs on device %d", b->device, dev);
+  std::unique_ptr<vcmi_traj> t(new (std::nothrow) vcmi_traj());
+  if (!t) return fail(VCMI_ERR_OOM, "out of host memory");
+  t->b = b;
+  t->D2 = b->D;
+  t->D = b->D / 2;
+  t->M = b->M;
+  t->length = T;
+  t->precision = VCMI_TRAJ_PRECISION_DIAG;
+  VCMI_TRY(upload_now(t->dg_q, b->h_q));       // [M][2D]: (D,M) dimension fastest is that layout
+  t->diag_ready = true;
   *out = t.release();
   return VCMI_OK;
 }

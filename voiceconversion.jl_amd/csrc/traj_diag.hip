@@ -156,7 +156,7 @@ int traj_diag_launch(vcmi_traj *t, const TrajSolvePlan &p, hipStream_t st) {
 }
 
 int traj_diag_ensure(vcmi_traj *t) {
-  if (t->diag_ready) return VCMI_OK;
+  if (t->diag_ready) return VCMI_OK;      // (always so for a cross-diagonal handle: vcmi_traj_create_bdiag, g is NULL)
   const vcmi_gmmmap *g = t->g;
   TrajDiagModel dm;     // the host arithmetic: traj_prepare.cpp
   VCMI_TRY(traj_prepare_diag(g->h_A, g->h_Sxy, g->h_Syy, t->D2, t->M, dm));
@@ -181,6 +181,9 @@ extern "C" int vcmi_traj_set_precision(vcmi_traj *t, int kind) {
   if (!t) return fail(VCMI_ERR_ARG, "vcmi_traj_set_precision: NULL handle");
   if (kind != VCMI_TRAJ_PRECISION_FULL && kind != VCMI_TRAJ_PRECISION_DIAG)
     return fail(VCMI_ERR_ARG, "vcmi_traj_set_precision: unknown kind %d", kind);
+  if (kind == VCMI_TRAJ_PRECISION_FULL && t->b)
+    return fail(VCMI_ERR_ARG, "vcmi_traj_set_precision: the converter was made from a cross-diagonal model (vcmi_traj_create_bdiag): "
+                              "its conditional precisions are diagonal, there is no full matrix to switch to");
   if (kind == VCMI_TRAJ_PRECISION_DIAG) {
     if (t->em_iters > 0)      // the M-step blends full precision matrices
       return fail(VCMI_ERR_ARG, "vcmi_traj_set_precision: the converter has EM re-estimation switched on (vcmi_traj_set_em)");

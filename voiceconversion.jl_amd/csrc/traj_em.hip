@@ -613,6 +613,8 @@ extern "C" int vcmi_traj_em_history(const vcmi_traj *t, double *L, int cap) {
 extern "C" int vcmi_traj_cond_loglik_dev(vcmi_traj *t, const double *dX, const double *dY, int64_t T, double *dL, void *stream) {
   if (!t || !dL) return fail(VCMI_ERR_ARG, "vcmi_traj_cond_loglik_dev: NULL argument");
   if (T < 0 || T > INT32_MAX || (T > 0 && (!dX || !dY))) return fail(VCMI_ERR_ARG, "vcmi_traj_cond_loglik_dev: bad argument");
+  if (t->b)      // (the E-step evaluates the dense model: not for a handle without one)
+    return fail(VCMI_ERR_ARG, "vcmi_traj_cond_loglik: the converter was made from a cross-diagonal model (vcmi_traj_create_bdiag)");
   if (!t->em_pd) return fail(VCMI_ERR_NOT_PD, "vcmi_traj_cond_loglik: (Q_m + Q_m')/2 of some mixture is not positive definite");
   hipStream_t st = as_stream(stream);
   if (T == 0) {
@@ -636,6 +638,8 @@ extern "C" int vcmi_traj_cond_loglik(vcmi_traj *t, const double *X, const double
   if (!t || !L) return fail(VCMI_ERR_ARG, "vcmi_traj_cond_loglik: NULL argument");
   if (T < 0 || T > INT32_MAX || (T > 0 && (!X || !Y))) return fail(VCMI_ERR_ARG, "vcmi_traj_cond_loglik: bad argument");
   *L = 0.0;
+  if (t->b)
+    return fail(VCMI_ERR_ARG, "vcmi_traj_cond_loglik: the converter was made from a cross-diagonal model (vcmi_traj_create_bdiag)");
   if (T == 0) return VCMI_OK;
   VCMI_TRY(t->xbuf.reserve((size_t)T * t->D2));
   VCMI_TRY(t->ybuf.reserve((size_t)T * t->D + 1));

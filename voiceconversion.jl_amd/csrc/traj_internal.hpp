@@ -3,6 +3,7 @@
 #pragma once
 #include "vcmi_common.hpp"
 #include "gmmmap_handle.hpp"
+#include "gmmmap_bdiag_handle.hpp"
 
 namespace vcmi {
 struct EmTimes {           // what vcmi_debug_traj_em_times reports
@@ -14,6 +15,10 @@ struct EmTimes {           // what vcmi_debug_traj_em_times reports
 
 struct vcmi_traj {
   vcmi_gmmmap *g = nullptr;
+  // A converter made straight from a cross-diagonal model (vcmi_traj_create_bdiag) has b in place of g: precision is DIAG for
+  // good, dg_q holds b's q, the arg-max and g_t of a call are one pass of b's kernel (bdmap_traj_device), and every dense
+  // buffer below (AT .. Afrag, Qpad, cm, dg_QT, dg_Qfrag) stays empty.  No replicas: b converts on its own device.
+  vcmi_bdmap *b = nullptr;
   int D2 = 0;          // dim(t) = 2D (static + delta), src/trajectory_gmmmap.jl:35
   int D = 0;           // static dimension
   int M = 0;

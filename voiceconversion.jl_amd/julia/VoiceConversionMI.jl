@@ -18,7 +18,8 @@ module VoiceConversionMI
 
 import LinearAlgebra
 
-export DeviceMatrix, FrameByFrameConverter, TrajectoryConverter, GMMMapParam, GMMMap, GMMMapBlockDiag, slopes, TrajectoryGMMMap, TrajectoryGVGMMMap,
+export DeviceMatrix, FrameByFrameConverter, TrajectoryConverter, GMMMapParam, GMMMap, GMMMapBlockDiag, slopes, TrajectoryGMMMap, TrajectoryGMMMapBlockDiag,
+       TrajectoryGVGMMMap,
        fvconvert, vc, ncomponents, dim, em_iters, em_iters!, traj_precision, traj_precision!, cond_loglik, em_history,
        VarianceScaling, fvpostf!, fvpostf,
        align, align_mcep, push_delta, GVDataset, sp2mc, mc2sp, mc2b,
@@ -820,6 +821,88 @@ function fvpostf!(vs::VarianceScaling, src::DeviceMatrix; stream::Ptr{Cvoid}=C_N
                 (Ptr{Float64}, Int64, Cint, Int64, Ptr{Float64}, Ptr{Float64}, Int64, Ptr{Cvoid}),
                 src.ptr, src.ld, src.rows, src.cols, vs.σ², src.ptr, src.ld, stream))
     src
+end
+
+# ---- TrajectoryGMMMapBlockDiag: trajectory conversion straight from a cross-diagonal model (vcmi_traj_create_bdiag) ----------
+# g over static+delta features (dim(g) = 2D).  The conditional covariance of such a model is diagonal exactly, so the converter
+# runs the tridiagonal solver (traj_precision is :diag for good) and the dense model is never formed.  It converts on the device
+# g was created on; em_iters!, traj_precision!(t, :full), cond_loglik and a TrajectoryGVGMMMap over it are refused by the library.
+mutable struct TrajectoryGMMMapBlockDiag <: TrajectoryConverter
+    gmmmap::GMMMapBlockDiag
+    h::Ptr{Cvoid}
+    function TrajectoryGMMMapBlockDiag(g::GMMMapBlockDiag, T::Int)
+        h = Ref{Ptr{Cvoid}}(C_NULL)
+        check(ccall((:vcmi_traj_create_bdiag, libvcmi), Cint, (Ptr{Cvoid}, Int64, Ref{Ptr{Cvoid}}), g.h, T, h))
+        t = new(g, h[])
+        finalizer(x -> ccall((:vcmi_traj_destroy, libvcmi), Cint, (Ptr{Cvoid},), x.h), t)
+        t
+    end
+end
+traj_precision(t::TrajectoryGMMMapBlockDiag) = TRAJ_PRECISIONS[Int(ccall((:vcmi_traj_get_precision, libvcmi), Cint, (Ptr{Cvoid},), t.h)) + 1]
+em_iters(t::TrajectoryGMMMapBlockDiag) = Int(ccall((:vcmi_traj_get_em, libvcmi), Cint, (Ptr{Cvoid},), t.h))
+Base.length(t::TrajectoryGMMMapBlockDiag) = Int(ccall((:vcmi_traj_length, libvcmi), Int64, (Ptr{Cvoid},), t.h))
+dim(t::TrajectoryGMMMapBlockDiag) = dim(t.gmmmap)
+ncomponents(t::TrajectoryGMMMapBlockDiag) = ncomponents(t.gmmmap)
+Base.size(t::TrajectoryGMMMapBlockDiag) = (dim(t), length(t))
+function fvconvert(t::TrajectoryGMMMapBlockDiag, X::Matrix{Float64})
+    size(X, 1) == dim(t) || throw(DimensionMismatch("Inconsistent dimentions."))
+    Y = Matrix{Float64}(undef, size(X, 1) >> 1, size(X, 2))
+    check(ccall((:vcmi_traj_convert, libvcmi), Cint, (Ptr{Cvoid}, Ptr{Float64}, Int64, Ptr{Float64}),
+                t.h, X, size(X, 2), Y))
+    Y
+end
+function fvconvert(t::TrajectoryGMMMapBlockDiag, Xs::Vector{Matrix{Float64}})
+    all(size(x, 1) == dim(t) for x in Xs) || throw(DimensionMismatch("Inconsistent dimentions."))
+    T = Int64[size(x, 2) for x in Xs]
+    Ys = [Matrix{Float64}(undef, dim(t) >> 1, k) for k in T]
+    GC.@preserve Xs Ys begin
+        check(ccall((:vcmi_traj_convert_batch, libvcmi), Cint,
+                    (Ptr{Cvoid}, Int64, Ptr{Ptr{Float64}}, Ptr{Int64}, Ptr{Ptr{Float64}}),
+                    t.h, length(Xs), pointer.(Xs), T, pointer.(Ys)))
+    end
+    Ys
+end
+function vc(t::TrajectoryGMMMapBlockDiag, fm::Matrix{Float64}, vs::Union{VarianceScaling,Nothing}=nothing; delta::Bool=false)
+    D = dim(t) >> 1
+    size(fm, 1) == (delta ? D : 2D) + 1 || throw(DimensionMismatch("Inconsistent dimentions."))
+    σ² = σ²vector(vs, D)
+    out = Matrix{Float64}(undef, D + 1, size(fm, 2))
+    GC.@preserve σ² begin
+        if delta
+            check(ccall((:vcmi_vc_traj_static, libvcmi), Cint, (Ptr{Cvoid}, Ptr{Float64}, Int64, Ptr{Float64}, Ptr{Float64}),
+                        t.h, fm, size(fm, 2), σ²pointer(vs, σ²), out))
+        else
+            check(ccall((:vcmi_vc_traj_postf, libvcmi), Cint, (Ptr{Cvoid}, Ptr{Float64}, Int64, Ptr{Float64}, Ptr{Float64}),
+                        t.h, fm, size(fm, 2), σ²pointer(vs, σ²), out))
+        end
+    end
+    out
+end
+function vc(t::TrajectoryGMMMapBlockDiag, fms::Vector{Matrix{Float64}}, vs::Union{VarianceScaling,Nothing}=nothing; delta::Bool=false)
+    D = dim(t) >> 1
+    all(size(fm, 1) == (delta ? D : 2D) + 1 for fm in fms) || throw(DimensionMismatch("Inconsistent dimentions."))
+    σ² = σ²vector(vs, D)
+    T = Int64[size(fm, 2) for fm in fms]
+    outs = [Matrix{Float64}(undef, D + 1, k) for k in T]
+    GC.@preserve fms outs σ² begin
+        check(ccall((:vcmi_vc_traj_batch, libvcmi), Cint,
+                    (Ptr{Cvoid}, Int64, Ptr{Ptr{Float64}}, Ptr{Int64}, Cint, Ptr{Float64}, Ptr{Ptr{Float64}}),
+                    t.h, length(fms), pointer.(fms), T, delta ? 1 : 0, σ²pointer(vs, σ²), pointer.(outs)))
+    end
+    outs
+end
+function vc(t::TrajectoryGMMMapBlockDiag, fm::DeviceMatrix, out::DeviceMatrix, vs::Union{VarianceScaling,Nothing}=nothing;
+            delta::Bool=false, stream::Ptr{Cvoid}=C_NULL)
+    D = dim(t) >> 1
+    fm.rows == (delta ? D : 2D) + 1 || throw(DimensionMismatch("Inconsistent dimentions."))
+    (out.rows == D + 1 && out.cols == fm.cols) || throw(DimensionMismatch("out must be (D+1,T)"))
+    σ² = σ²vector(vs, D)
+    GC.@preserve σ² begin
+        check(ccall((:vcmi_vc_traj_dev, libvcmi), Cint,
+                    (Ptr{Cvoid}, Ptr{Float64}, Int64, Int64, Cint, Ptr{Float64}, Ptr{Float64}, Int64, Ptr{Cvoid}),
+                    t.h, fm.ptr, fm.ld, fm.cols, delta ? 1 : 0, σ²pointer(vs, σ²), out.ptr, out.ld, stream))
+    end
+    out
 end
 
 # align_mcep(src, tgt, α, fftlen; threshold, remove_silence) -- src/align.jl:38-55 (mc2e included)

@@ -134,7 +134,8 @@ class TrajectoryGMMMap(TrajectoryConverter):
     def __init__(self, g, T, em_iters=0, precision="full"):
         if isinstance(g, BlockDiagGMMMap):
             raise TypeError("TrajectoryGMMMap takes a GMMMap, not a BlockDiagGMMMap: build it from "
-                            "GMMMap(weights, mu, expand_block_diag(covars)) (precision=\"diag\" then converts with the model exactly)")
+                            "GMMMap(weights, mu, expand_block_diag(covars)) (precision=\"diag\" then converts with the model exactly), "
+                            "or use BlockDiagTrajectoryGMMMap(g, T), which converts straight from the cross-diagonal model")
         self.gmmmap = g
         h = C.c_void_p()
         _lib.check(_lib.lib.vcmi_traj_create(g._h, int(T), C.byref(h)))
@@ -269,6 +270,24 @@ class TrajectoryGMMMap(TrajectoryConverter):
             return _lib.lib.vcmi_vc_traj_batch_dev(self._h, *args)
 
         return _vc_batch(self, fms, postfilter, delta, host, dev)
+
+
+class BlockDiagTrajectoryGMMMap(TrajectoryGMMMap):
+    """BlockDiagTrajectoryGMMMap(g::BlockDiagGMMMap, T): trajectory conversion straight from a cross-diagonal model over
+    static+delta features (dim(g) = 2D) -- what train_gmm(covariance_type="block_diag") returns, as it is.  The conditional
+    covariance of such a model is diagonal exactly, so the converter runs the tridiagonal solver of precision="diag" and the dense
+    (4D,4D,M) model is never formed (include/vcmi.h: vcmi_traj_create_bdiag; csrc/gmmmap_bdiag.hip, mode 3).  Equal to
+    TrajectoryGMMMap(GMMMap(weights, mu, expand_block_diag(covars)), T, precision="diag") to rounding.  fvconvert,
+    fvconvert_batch, vc and vc_batch are TrajectoryGMMMap's; precision is "diag" for good, and em_iters > 0, precision = "full",
+    cond_loglik and a TrajectoryGVGMMMap over it are refused (VCMIError).  Converts on the device g was created on."""
+
+    def __init__(self, g, T):
+        if not isinstance(g, BlockDiagGMMMap):
+            raise TypeError(f"BlockDiagTrajectoryGMMMap takes a BlockDiagGMMMap, not a {type(g).__name__}")
+        self.gmmmap = g                     # (kept alive: the library's handle reads g's tables in every call)
+        h = C.c_void_p()
+        _lib.check(_lib.lib.vcmi_traj_create_bdiag(g._h, int(T), C.byref(h)))
+        self._h = h
 
 
 class TrajectoryGVGMMMap(TrajectoryConverter):
