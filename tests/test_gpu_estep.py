@@ -365,7 +365,10 @@ def test_hard_assignment_path_all_frames_owned(vc, N, Dj, M, sep, zw):
         assert a[0][zw] == 0.0 and not a[1][:, zw].any()
 
 
-@pytest.mark.parametrize("N,Dj,M", [(70_000, 80, 128), (66_000, 48, 24), (80_000, 64, 100)])
+@pytest.mark.parametrize("N,Dj,M", [(70_000, 80, 128), (66_000, 48, 24), (80_000, 64, 100),
+                                    # the gathered frames through the other two FP64 bodies of the plan (csrc/estep_plan.hpp):
+                                    # estep_mfma_kernel with shared tiles (32 < M <= 64), estep_small_kernel<DJ, 1> (M <= 16)
+                                    (65_536, 48, 40), (65_536, 48, 16)])
 def test_hard_assignment_path_mixed_frames(vc, N, Dj, M):
     """Half of the mixtures far apart, the other half overlapping: the owned frames are settled by the screen, the others
     (thousands) are gathered and go through the FP64 kernel -- sum of the two equals the one-kernel path and the oracle."""

@@ -23,29 +23,19 @@
 // fraction of the previous call and stays on the one-kernel path while it is high.
 #pragma once
 #include "bf16_split.hpp"
+#include "estep_cfg.hpp"
 #include "grouping.hpp"
 
 namespace vcmi {
 
-constexpr int kHardPiece = 256;        // hard frames per workgroup of the statistics kernel
-constexpr int kHardMaxM = 128;         // mixtures (the one-kernel path's limit; more go through the groups of estep_mfma_groups_launch)
+// kHardPiece, kHardMaxM, kHardKeyThreads, kHardChunk and EstepHardCfg<DJ> (the layout of W in bf16 for the key kernel): estep_cfg.hpp
+static_assert(kHardChunk == kGroupChunk, "the hard-assignment path sorts with the chunks of grouping.hpp");
 // Largest margin the key kernel trusts.  With NWmax < 2^114 every W operand is a finite float (|W_m| <= 2^12 NWmax), and with
 // E = NWmax |[x^2 ; x]| + NCmax < 2^114 every product and partial sum of l^ stays below 2^127 < FLT_MAX (|c_m| <= 2^12 E,
 // sum |W_m,i z_i| <= |W_m| |z| <= 2^12 E).  Beyond it an operand or a product can overflow FP32: l^ turns -inf or NaN, and a NaN
 // drops out of the best / second-best comparison -- a mixture with var < ~1.5e-39 (-1/(2 var) is -inf in FP32) could own a
 // frame that is then certified "hard" to another mixture.  Such frames are left soft.
 constexpr float kHardFinite = 0x1p114f;
-// W in bf16 for the key kernel: per mixture tile mt (16 mixtures) and instruction i (x dimensions 16 i .. 16 i + 15):
-// [hi 64 x 16 B | lo 64 x 16 B]; slot j of lane group g <-> j < 4: -1/(2 var) of dimension 16 i + 4 g + j (multiplies x^2),
-// j >= 4: mu / var of dimension 16 i + 4 g + (j - 4) (multiplies x).  Then per tile 48 floats: c (16), 2^-12 |W_m| (16, rounded
-// up), 2^-12 |c_m| (16, rounded up); a mixture without weight or beyond M: c = -1e30, margins 0 (its l^ is certified hopeless).
-template <int DJ>
-struct EstepHardCfg {
-  static constexpr int NI = (DJ + 15) / 16;                  // K = 32 instructions per term
-  static constexpr int TILE_BYTES = NI * 2048 + 192;         // operands of one mixture tile
-  static constexpr size_t lds_bytes(int mt) { return (size_t)mt * TILE_BYTES; }
-};
-
 template <int DJ>
 __global__ void __launch_bounds__(256)
 estep_hard_prep_kernel(const double *__restrict__ raw, const double *__restrict__ cinit, int M, int dj, unsigned char *__restrict__ W16) {
@@ -97,7 +87,6 @@ estep_hard_prep_kernel(const double *__restrict__ raw, const double *__restrict_
 }
 
 // keys + one histogram per chunk of kGroupChunk frames (keys 0 .. M: M = soft), as gmmmap_group_key_kernel
-constexpr int kHardKeyThreads = 512;      // one workgroup per CU (the operands of all mixtures fill half its LDS): eight waves of two frame tiles each (256 registers: sixteen waves of two tiles spill at Dj = 80)
 template <int DJ>
 __global__ void __launch_bounds__(kHardKeyThreads)
 estep_hard_key_kernel(const unsigned char *__restrict__ W16, int M, int dj, const double *__restrict__ X, int64_t N,

@@ -15,9 +15,7 @@
 
 namespace vcmi {
 
-// ctl (int64, device): [0] 1: the hard-assignment path runs / 0: every frame through estep_mfma_kernel; [1] frames of the
-// "everything soft" launch (N or 0); [2] soft frames found by the hard-assignment path (estep_hard_gather_kernel)
-enum { kCtlHard = 0, kCtlAllSoft = 1, kCtlNSoft = 2, kCtlLen = 4 };
+// the control words ctl[kCtlHard], ctl[kCtlAllSoft], ctl[kCtlNSoft]: estep_cfg.hpp
 
 // decision from the sample's histograms (hist[c][k], k = M: no owner): hard iff at most a quarter of the sample has no owner.
 // force: -1 decide, 0 / 1 set.

@@ -32,6 +32,7 @@
 // The arithmetic of a frame is that of estep_mfma_kernel (same expanded form, same refinement rule, same table exp); the
 // partial statistics have the same row layout (row = workgroup x half) and go through estep_reduce_kernel.
 #pragma once
+#include "estep_cfg.hpp"
 
 #ifndef VCMI_SMALL_PRIO
 #define VCMI_SMALL_PRIO 1
@@ -42,36 +43,7 @@
 
 namespace vcmi {
 
-template <int DJ, int MT>
-struct EstepSmallCfg {
-  static_assert(MT == 1 || MT == 2, "one or two mixture tiles");
-  static constexpr int KS = 2 * DJ / 4, NDT = 2 * DJ / 16;
-  static constexpr int NW = 2 * MT;                              // waves per workgroup
-  // frames per block.  MT = 2: two frame tiles of 16, a wave = (mixture tile, frame tile) in step A.  MT = 1: ONE frame tile,
-  // and the two waves split the contraction of step A by k-steps (partial sums in two planes of LDS, added by the softmax) --
-  // half the LDS per workgroup, so that four of them fit a CU and every SIMD has its two waves (with 32-frame blocks a CU
-  // held two workgroups of two waves: one wave per SIMD, 0.55 ms per 1.25e6 frames at M = 16)
-  static constexpr int FB = MT == 1 ? 16 : 32;
-  static constexpr bool SPLITK = MT == 1;
-  static constexpr int PLANES = SPLITK ? 2 : 1;
-  static constexpr int RSX = (DJ + 2 + 13) / 32 * 32 + 18;       // as EstepCfg: 16-byte rows, conflict-free column reads
-  static constexpr int NCHUNK = (FB * RSX * 8 + 1023) / 1024;    // 1 KB wave-instructions of the LDS-DMA per x image
-  // doubles between two x images.  MT = 1: exactly the image -- the last wave-instruction of an image is cut off behind it
-  // (kLastLanes) -- because there every byte counts: four workgroups per CU have 40 KB each
-  static constexpr int XBUF = SPLITK ? FB * RSX : NCHUNK * 128;
-  static constexpr int kLastLanes = SPLITK ? (FB * RSX * 8 - 1024 * (NCHUNK - 1)) / 16 : 64;
-  static constexpr int NV = 16 * MT * FB / (64 * NW);            // softmax values per lane: 4 (MT = 2) / 2 (MT = 1)
-  static constexpr int LPF = 16 * MT / NV;                       // softmax lanes per frame
-  static_assert(LPF == 8 && 64 / LPF * NW == FB, "one softmax pass per wave and block");
-  // LDS row stride of l / gamma (doubles): the softmax's half-wave (four frames x eight consecutive doubles) lands on 64
-  // distinct banks -- MT = 2: rows 80 dwords apart -> 0, 16, 32, 48 mod 64; MT = 1: 48 dwords -> 0, 48, 32, 16
-  static constexpr int RSG = MT == 2 ? 40 : 24;
-  static constexpr int WG_PER_CU = MT == 2 ? 2 : 4;
-  // [x 3][l / gamma PLANES x FB x RSG][etab 64][thresholds 16 MT] doubles + [DMA source offsets: NCHUNK x 64 lanes] shorts
-  static constexpr size_t LDS_BYTES = ((size_t)3 * XBUF + (size_t)PLANES * FB * RSG + 64 + 16 * MT) * sizeof(double) + (size_t)NCHUNK * 64 * sizeof(unsigned short);
-  static_assert(FB * 80 * 8 < 65536 && (XBUF * 8) % 16 == 0, "offsets fit 16 bits; images are 16-byte aligned");
-  static_assert(LDS_BYTES * WG_PER_CU <= 160 * 1024, "LDS");
-};
+// EstepSmallCfg<DJ, MT>: estep_cfg.hpp
 
 // a lane permutation within DPP rows (quad_perm / row_half_mirror: every lane has a source) without the copy of the destination's
 // old value that update_dpp's tied operand costs -- two VALU instructions per double and step

@@ -20,27 +20,11 @@
 // Between two barriers a wave thus runs B(b-1), A(b+1) and the exps of block b at its own pace; the two waves of a SIMD are
 // rarely in the same phase.  LDS at Dj = 80: 4 x 20.5 KB of x + 8 waves x 2 planes x 4.25 KB + 9.3 KB of tables = 159.3 KB.
 #pragma once
+#include "estep_cfg.hpp"
 
 namespace vcmi {
 
-template <int DJ>
-struct EstepWaveCfg {
-  static constexpr int KS = 2 * DJ / 4, NDT = 2 * DJ / 16;
-  static constexpr int FB = 32;                                  // frames per block
-  static constexpr int RSX = (DJ + 2 + 13) / 32 * 32 + 18;       // as EstepCfg: 16-byte rows, conflict-free column reads
-  static constexpr int XBUF = FB * RSX;                          // doubles per x buffer (the last 1 KB wave-instruction of the DMA is masked)
-  static constexpr int NXB = 4;
-  // a private plane holds value (frame f, mixture c of the wave's 16) at (c & 7) * PROW + 2 f + (c >> 3): the softmax lanes
-  // (lane = 2 f + half, value i = c & 7) read and write stride-1 across the wave, step A's stores (rows of 8 dwords, 8 dwords
-  // apart) are conflict-free too; the 4 spare doubles of each row hold 1 / S of the block's frames (step B)
-  static constexpr int PROW = 2 * FB + 4;
-  static constexpr int PLANE = 8 * PROW;                         // doubles per private plane (l, then e in place); two per wave
-  static constexpr int XSET = 8 * FB;                            // doubles per table set: [wave][frame]
-  // doubles: [x NXB][planes 8 x 2][maxima 2 sets][sums 2 sets][etab 64]; bytes: [counts 2 x 8 x FB][frame order 8 x FB]
-  static constexpr size_t LDS_DOUBLES = (size_t)NXB * XBUF + 16 * PLANE + 4 * XSET + 64;
-  static constexpr size_t LDS_BYTES = LDS_DOUBLES * 8 + (size_t)2 * 8 * FB + 8 * FB;
-  static_assert(LDS_BYTES <= 160 * 1024, "LDS");
-};
+// EstepWaveCfg<DJ>: estep_cfg.hpp
 
 template <int DJ>
 __global__ void __launch_bounds__(512)
