@@ -445,7 +445,8 @@ int vcmi_traj_create(vcmi_gmmmap *g, int64_t T, vcmi_traj **out);
  * with |c| within rounding of sqrt(vx vy)); the message names the pair.  The handle follows vcmi_bdmap's device rule: it
  * converts on the device b was created on, a device group does not shard its calls, a call from another device is
  * VCMI_ERR_ARG.  VCMI_ERR_ARG, the handle usable afterwards: vcmi_traj_set_precision(t, FULL), vcmi_traj_set_em(t, n > 0),
- * vcmi_traj_cond_loglik[_dev], and every convert entry of a vcmi_trajgv over t. */
+ * vcmi_traj_cond_loglik[_dev], and every convert entry of a vcmi_trajgv of vcmi_trajgv_create over t (the GV ascent over such a
+ * converter: vcmi_trajgv_create_diag). */
 int vcmi_traj_create_bdiag(vcmi_bdmap *b, int64_t T, vcmi_traj **out);
 int vcmi_traj_destroy(vcmi_traj *t);
 /* length(t).  As in the reference, fvconvert rebuilds W when the sequence length differs (src/trajectory_gmmmap.jl:70-72),
@@ -466,7 +467,8 @@ int vcmi_traj_convert_batch_dev(vcmi_traj *t, int64_t n, const double *dX, const
  * _batch, _batch_dev and the vcmi_vc_traj family (per chunk) honour it, also on the replicas of a device group.
  * iters < 0: VCMI_ERR_ARG; iters > 0 on a model with some (Q_m + Q_m')/2 not positive definite (no log-determinant):
  * VCMI_ERR_NOT_PD -- with 0 such a model converts as before.  A vcmi_trajgv over a handle with iters > 0 returns VCMI_ERR_ARG
- * from every convert entry before anything runs (the GV ascent reads one mixture per frame): EM with GV is not provided.
+ * from every convert entry before anything runs (the GV ascent reads one mixture per frame): EM with GV is not provided, with
+ * either kind of GV handle.
  * Device scratch while EM runs, on the handle: log pi and gamma, M T doubles each; lse, flags and indices, ~4 T words; and the
  * precision table (M + n_mixed) (2Ds)^2 doubles, Ds the dimension the solver runs in (D, or the padded one), n_mixed the frames
  * of a slice with 1 - max_m gamma >= 2^-53.  A batch is processed in slices of whole utterances so that the table stays under
@@ -489,7 +491,8 @@ int vcmi_traj_get_em(const vcmi_traj *t);
  * switch to DIAG, on the calling thread's device, and kept.
  * VCMI_ERR_NOT_PD: a conditional variance that is zero, negative or not finite.  VCMI_ERR_ARG, the setting unchanged: an unknown
  * kind; DIAG on a handle with EM iterations > 0, and vcmi_traj_set_em(t, n > 0) on a DIAG handle.  Every convert entry of a
- * vcmi_trajgv over a DIAG handle returns VCMI_ERR_ARG before anything runs.  vcmi_traj_cond_loglik[_dev] ignores the setting:
+ * vcmi_trajgv made by vcmi_trajgv_create returns VCMI_ERR_ARG before anything runs while its converter is DIAG; one made by
+ * vcmi_trajgv_create_diag converts exactly then (below).  vcmi_traj_cond_loglik[_dev] ignores the setting:
  * it always evaluates the full-covariance model. */
 #define VCMI_TRAJ_PRECISION_FULL 0
 #define VCMI_TRAJ_PRECISION_DIAG 1
@@ -557,6 +560,21 @@ typedef struct vcmi_trajgv vcmi_trajgv;
  * is the larger of the two for every D >= 3.  D > 512 returns VCMI_ERR_ARG from the convert entries (the arg-max of the
  * trajectory converter ends at 2D = 320). */
 int vcmi_trajgv_create(vcmi_traj *t, const double *muv, const double *sigmavv, vcmi_trajgv **out);
+/* The same converter over a trajectory handle with DIAGONAL conditional precisions: vcmi_traj_set_precision(t, DIAG) or
+ * vcmi_traj_create_bdiag.  Arguments and checks of vcmi_trajgv_create; VCMI_ERR_ARG if t's precision is not DIAG now.  The
+ * handle goes to the same entries (vcmi_trajgv_convert, _batch, _batch_dev, vcmi_vc_trajgv, _dev, _batch, _batch_dev,
+ * vcmi_trajgv_destroy) and converts only while t's precision is DIAG: after vcmi_traj_set_precision(t, FULL) every convert
+ * entry returns VCMI_ERR_ARG before anything runs, and the handle is usable again after the switch back.  A handle of
+ * vcmi_trajgv_create over the same t keeps refusing while t is DIAG.
+ * With D^-1 = diag(q) the likelihood gradient is a three-point stencil per static dimension, (P y)_t = c0_t y_t +
+ * c2_t y_{t-2} + c2_{t+2} y_{t+2} (csrc/traj_gv_diag.hip): O(T D) per epoch, a Jacobi step on two y buffers.  traj_gvd_kernel
+ * runs one workgroup per utterance with all epochs inside; as many of its five (T,D) arrays (y, second y, c2, c0, r) as fit
+ * the 160 KB of LDS stay there across the epochs, chosen from D and the longest utterance of the call
+ * (csrc/traj_gvd_plan.hpp), the rest is streamed: every T >= 2 converts.  An utterance's result does not depend on the batch
+ * it came in.  Scratch on the trajectory handle: 5 D N doubles for the N frames of a call (the solver's D N and four more).
+ * D > 512: VCMI_ERR_ARG.  Device groups: an ordinary DIAG converter shards as vcmi_trajgv_create's does; one of
+ * vcmi_traj_create_bdiag converts on its own device. */
+int vcmi_trajgv_create_diag(vcmi_traj *t, const double *muv, const double *sigmavv, vcmi_trajgv **out);
 int vcmi_trajgv_destroy(vcmi_trajgv *h);
 /* fvconvert(tgv, X; epochs=100, alpha=1.0e-5) :139-168: trajectory solve, eq.(58) rescaling, then `epochs` steps of
  * y += alpha (omega (W'D^-1E - W'D^-1W y) + gvgrad(y)), all on the device.  X (2D,T) -> Y (D,T). */
@@ -595,7 +613,8 @@ int vcmi_vc_trajgv_dev(vcmi_trajgv *h, const double *dfm, int64_t ldf, int64_t T
  * n = 0 is a no-op; T[u] = 0 is allowed and yields nothing for u.  Refused before anything is uploaded or launched, with every
  * output untouched and length(t) as it was: sigma2 with some T[u] = 1: VCMI_ERR_DIM; a GV converter with a one-frame chunk
  * (T[u] mod L = 1): VCMI_ERR_DIM; length(t) < 1, n < 0, T[u] < 0, a NULL matrix with T[u] > 0: VCMI_ERR_ARG; a GV converter
- * over a handle with EM switched on or with diagonal precisions: VCMI_ERR_ARG (as vcmi_vc_trajgv).
+ * over a handle with EM switched on, or whose precision setting is not the one the GV handle was made for (vcmi_trajgv_create:
+ * FULL, vcmi_trajgv_create_diag: DIAG): VCMI_ERR_ARG (as vcmi_vc_trajgv).
  * The entries run on the calling thread's device (the device group of vcmi_set_devices is not used), in the per-thread
  * scratch of the vcmi_vc_traj_static family under its rule (a host-pointer entry frees it on return above 256 MiB).  Footprint,
  * N = sum T: converter input and result, 3 D N doubles; the host-pointer entries add the staging matrix with the inputs and

@@ -248,7 +248,11 @@ int traj_run(vcmi_traj *t, std::vector<TrajUtt> &utts, int64_t nframes, bool con
   TrajSolvePlan plan;      // (its host work runs beside the g_t kernel)
   VCMI_TRY(traj_solve_plan(t, utts, nframes, Tmax, gv != nullptr, &plan));
   t->em_run_iters = 0;
-  if (diag) return traj_diag_launch(t, plan, st);     // (no EM, no GV over a diagonal handle: refused where they are set)
+  if (diag) {     // (no EM over a diagonal handle: refused where it is set; GV: a handle of vcmi_trajgv_create_diag)
+    VCMI_TRY(traj_diag_launch(t, plan, st));
+    if (gv && gv->epochs >= 0) VCMI_TRY(traj_gvd_launch(t, plan, *gv, st));
+    return VCMI_OK;
+  }
   VCMI_TRY(traj_solve_launch(t, plan, plan.padded ? t->Qpad.p : t->Q.p, t->mhat.p, 0, n, st));
   if (t->em_iters > 0) VCMI_TRY(traj_em_run(t, utts, plan, contiguous, dX0, st));
   // (3) global-variance ascent on the solved trajectories, in place
@@ -388,6 +392,7 @@ int traj_host_batch(vcmi_traj *t, int64_t n, const double *const *X, const int64
           gr = new (std::nothrow) vcmi_trajgv();
           if (!gr) return fail(VCMI_ERR_OOM, "out of host memory");
           gr->t = r;
+          gr->diag = gvh->diag;
           VCMI_TRY(gr->muv.alloc(gvh->h_muv.size()));
           VCMI_TRY(gr->pv.alloc(gvh->h_pv.size()));
           VCMI_TRY(upload_now(gr->muv.p, gvh->h_muv.data(), gvh->h_muv.size() * 8));

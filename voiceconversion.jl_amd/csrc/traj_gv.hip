@@ -1,8 +1,10 @@
 // traj_gv.hip -- TrajectoryGVGMMMap (reference src/trajectory_gmmmap.jl:114-189): the handle, the three kernels of the
 // global-variance ascent on solved trajectories (two for 2D <= 96, traj_gvw_kernel above that), and the host function that
-// chooses between them (traj_internal.hpp: traj_gv_launch).
+// chooses between them (traj_internal.hpp: traj_gv_launch).  The ascent over diagonal conditional precisions: traj_gv_diag.hip.
 #include "traj_internal.hpp"
 #include "traj_blk_prof.hpp"
+#include "traj_gv_moments.hpp"
+#include "traj_gvd_plan.hpp"
 #include "host_linalg.hpp"
 #include "hostpipe.hpp"
 
@@ -17,62 +19,6 @@ namespace vcmi {
 // of Q; the tile's frames usually share one or two mixtures, so the product is accumulated over the DISTINCT
 // mixtures of the tile with the B operand masked to that mixture's frames (exact: the other frames add 0).
 // ------------------------------------------------------------------------------------------------
-template <typename YP>
-__device__ void gv_moments(YP y, int D, int T, int nthr, double *red, double *mean, double *var) {
-  const int tid = threadIdx.x;
-  const int NG = nthr / D;                 // frame groups per dimension
-  const int d = tid % D, g = tid / D;
-  double s = 0.0;
-  if (g < NG) {
-    // 8 loads in flight per thread (a plain loop keeps one: with one workgroup per CU the passes of this kernel are
-    // bound by memory-level parallelism, not by HBM bandwidth); the additions stay in frame order
-    int t = g;
-    for (; t + 7 * NG < T; t += 8 * NG) {
-      double v[8];
-#pragma unroll
-      for (int q = 0; q < 8; ++q) v[q] = y[(size_t)(t + q * NG) * D + d];
-#pragma unroll
-      for (int q = 0; q < 8; ++q) s += v[q];
-    }
-    for (; t < T; t += NG) s += y[(size_t)t * D + d];
-  }
-  if (g < NG) red[g * D + d] = s;
-  __syncthreads();
-  if (tid < D) {
-    double m = 0.0;
-    for (int k = 0; k < NG; ++k) m += red[k * D + tid];
-    mean[tid] = m / (double)T;
-  }
-  __syncthreads();
-  s = 0.0;
-  if (g < NG) {
-    const double m = mean[d];
-    int t = g;
-    for (; t + 7 * NG < T; t += 8 * NG) {
-      double v[8];
-#pragma unroll
-      for (int q = 0; q < 8; ++q) v[q] = y[(size_t)(t + q * NG) * D + d];
-#pragma unroll
-      for (int q = 0; q < 8; ++q) {
-        const double e = v[q] - m;
-        s = fma(e, e, s);
-      }
-    }
-    for (; t < T; t += NG) {
-      const double e = y[(size_t)t * D + d] - m;
-      s = fma(e, e, s);
-    }
-    red[g * D + d] = s;
-  }
-  __syncthreads();
-  if (tid < D) {
-    double v = 0.0;
-    for (int k = 0; k < NG; ++k) v += red[k * D + tid];
-    var[tid] = v / (double)(T - 1);        // Julia's var: corrected
-  }
-  __syncthreads();
-}
-
 typedef double gv_d4 __attribute__((ext_vector_type(4)));
 static constexpr int kGvNB = 8;   // 16-frame tiles per round of the GV product
 static constexpr int kGvMaxKS = 24;   // k-steps of the widest supported feature vector (2D <= 96)
@@ -820,8 +766,14 @@ int trajgv_args(const vcmi_trajgv *h, int64_t n, const int64_t *T, int epochs, T
     return fail(VCMI_ERR_ARG, "TrajectoryGVGMMMap: static dimension %d beyond %d", h->t->D, kGvwThreads);
   if (h->t->em_iters > 0)    // the GV ascent groups frames by mhat[t] <= M and reads Qfrag: no blended precisions
     return fail(VCMI_ERR_ARG, "TrajectoryGVGMMMap: the trajectory converter has EM re-estimation switched on (vcmi_traj_set_em)");
-  if (h->t->precision == VCMI_TRAJ_PRECISION_DIAG)    // ... and it multiplies by the full Q_m
-    return fail(VCMI_ERR_ARG, "TrajectoryGVGMMMap: the trajectory converter has diagonal conditional precisions (vcmi_traj_set_precision)");
+  if (h->diag) {      // a handle of vcmi_trajgv_create_diag runs traj_gvd_kernel, which reads q alone
+    if (h->t->precision != VCMI_TRAJ_PRECISION_DIAG)
+      return fail(VCMI_ERR_ARG, "DiagTrajectoryGVGMMMap: the trajectory converter has been switched to full conditional precisions "
+                                "(vcmi_traj_set_precision): switch it back, or make the handle with vcmi_trajgv_create");
+    if (h->t->D > kGvdThreads) return fail(VCMI_ERR_ARG, "DiagTrajectoryGVGMMMap: static dimension %d beyond %d", h->t->D, kGvdThreads);
+  } else if (h->t->precision == VCMI_TRAJ_PRECISION_DIAG)    // ... and it multiplies by the full Q_m
+    return fail(VCMI_ERR_ARG, "TrajectoryGVGMMMap: the trajectory converter has diagonal conditional precisions (vcmi_traj_set_precision); "
+                              "vcmi_trajgv_create_diag makes a handle for such a converter");
   for (int64_t u = 0; T && u < n; ++u)
     if (T[u] == 1) return fail(VCMI_ERR_DIM, "TrajectoryGVGMMMap: the variance of a one-frame trajectory is undefined");
   gv->muv = h->muv.p;
@@ -835,9 +787,14 @@ int trajgv_args(const vcmi_trajgv *h, int64_t n, const int64_t *T, int epochs, T
 using namespace vcmi;
 
 // ---- TrajectoryGVGMMMap, src/trajectory_gmmmap.jl:114-189 ----------------------------------------
-extern "C" int vcmi_trajgv_create(vcmi_traj *t, const double *muv, const double *sigmavv, vcmi_trajgv **out) {
-  if (!t || !muv || !sigmavv || !out) return fail(VCMI_ERR_ARG, "vcmi_trajgv_create: NULL argument");
+static int trajgv_create(vcmi_traj *t, const double *muv, const double *sigmavv, bool diag, vcmi_trajgv **out) {
+  const char *who = diag ? "vcmi_trajgv_create_diag" : "vcmi_trajgv_create";
+  if (!t || !muv || !sigmavv || !out) return fail(VCMI_ERR_ARG, "%s: NULL argument", who);
   *out = nullptr;
+  if (diag && t->precision != VCMI_TRAJ_PRECISION_DIAG)
+    return fail(VCMI_ERR_ARG, "vcmi_trajgv_create_diag: the trajectory converter has full conditional precisions "
+                              "(vcmi_traj_set_precision): vcmi_trajgv_create makes the handle for it");
+  if (diag && t->D > kGvdThreads) return fail(VCMI_ERR_ARG, "DiagTrajectoryGVGMMMap: static dimension %d beyond %d", t->D, kGvdThreads);
   const int D = t->D;
   for (int d = 0; d < D; ++d)
     if (muv[d] < 0.0) return fail(VCMI_ERR_ARG, "TrajectoryGVGMMMap: the GV mean must be non-negative");   // the @assert of :124
@@ -851,6 +808,7 @@ extern "C" int vcmi_trajgv_create(vcmi_traj *t, const double *muv, const double 
   vcmi_trajgv *h = new (std::nothrow) vcmi_trajgv();
   if (!h) return fail(VCMI_ERR_OOM, "out of host memory");
   h->t = t;
+  h->diag = diag;
   int rc = VCMI_OK;
   if ((rc = h->muv.alloc(D)) || (rc = h->pv.alloc((size_t)D * D))) {
     delete h;
@@ -866,6 +824,15 @@ extern "C" int vcmi_trajgv_create(vcmi_traj *t, const double *muv, const double 
   h->h_pv = Pj;
   *out = h;
   return VCMI_OK;
+}
+
+extern "C" int vcmi_trajgv_create(vcmi_traj *t, const double *muv, const double *sigmavv, vcmi_trajgv **out) {
+  return trajgv_create(t, muv, sigmavv, false, out);
+}
+
+// ... over a converter with diagonal conditional precisions (vcmi_traj_set_precision, vcmi_traj_create_bdiag): traj_gv_diag.hip
+extern "C" int vcmi_trajgv_create_diag(vcmi_traj *t, const double *muv, const double *sigmavv, vcmi_trajgv **out) {
+  return trajgv_create(t, muv, sigmavv, true, out);
 }
 
 extern "C" int vcmi_trajgv_destroy(vcmi_trajgv *h) {

@@ -2,6 +2,7 @@
 // pad / unpad kernels, and the one dispatch behind traj_run and the EM loop (traj_internal.hpp: traj_solve_plan / _launch).
 #include "traj_internal.hpp"
 #include "traj_prepare.hpp"
+#include "traj_gvd_plan.hpp"
 #include "traj_blk_prof.hpp"
 #include "hostpipe.hpp"
 #include "lds_dma.hpp"
@@ -467,15 +468,17 @@ int traj_solve_plan(vcmi_traj *t, const std::vector<TrajUtt> &utts, int64_t nfra
   p.n = n;
   p.Tmax = Tmax;
   p.nframes = nframes;
+  int dev = 0;
+  (void)hipGetDevice(&dev);
+  (void)hipDeviceGetAttribute(&p.cus, hipDeviceAttributeMultiprocessorCount, dev);
   if (t->precision == VCMI_TRAJ_PRECISION_DIAG) {   // traj_diag.hip: one double per frame and dimension, indexed by frame0; nothing else
     p.Ds = D;
     p.du = p.dus = reinterpret_cast<const TrajUtt *>(t->uttbuf.p);
     p.gs = t->gbuf.p;
-    return t->ws.reserve((size_t)nframes * D);
+    p.grid = std::min(n, p.cus);            // workgroups of the GV ascent (traj_gvd_kernel)
+    p.ws_stride = gvd_ws_doubles(nframes, D, with_gv);     // the whole reserve, not a stride: traj_gvd_launch checks it
+    return t->ws.reserve((size_t)p.ws_stride);
   }
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  (void)hipDeviceGetAttribute(&p.cus, hipDeviceAttributeMultiprocessorCount, dev);
   p.grid = std::min(n, p.cus);
   p.ws_stride = (int64_t)Tmax * (3 * D + 1) * D;
   if (with_gv) p.ws_stride = std::max<int64_t>(p.ws_stride, (int64_t)Tmax * 3 * D + (17 * (int64_t)Tmax + 1) / 2 + 16);   // V, r, perm

@@ -19,7 +19,7 @@ module VoiceConversionMI
 import LinearAlgebra
 
 export DeviceMatrix, FrameByFrameConverter, TrajectoryConverter, GMMMapParam, GMMMap, GMMMapBlockDiag, slopes, TrajectoryGMMMap, TrajectoryGMMMapBlockDiag,
-       TrajectoryGVGMMMap,
+       TrajectoryGVGMMMap, TrajectoryGVGMMMapDiag,
        fvconvert, vc, ncomponents, dim, em_iters, em_iters!, traj_precision, traj_precision!, cond_loglik, em_history,
        VarianceScaling, fvpostf!, fvpostf,
        align, align_mcep, push_delta, GVDataset, sp2mc, mc2sp, mc2b,
@@ -377,7 +377,7 @@ function em_iters!(t::TrajectoryGMMMap, n::Int)
 end
 # The conditional precisions of the conversion: :full (the reference's Dy_m) or :diag (the conditional covariances taken as
 # diagonal: tridiagonal systems per static dimension and frame parity, csrc/traj_diag.hip).  A setting of the converter, like
-# em_iters; not together with em_iters > 0 or under a TrajectoryGVGMMMap.
+# em_iters; not together with em_iters > 0 or under a TrajectoryGVGMMMap (GV over :diag: TrajectoryGVGMMMapDiag).
 const TRAJ_PRECISIONS = (:full, :diag)                                # VCMI_TRAJ_PRECISION_FULL, VCMI_TRAJ_PRECISION_DIAG
 traj_precision(t::TrajectoryGMMMap) = TRAJ_PRECISIONS[Int(ccall((:vcmi_traj_get_precision, libvcmi), Cint, (Ptr{Cvoid},), t.h)) + 1]
 function traj_precision!(t::TrajectoryGMMMap, kind::Symbol)
@@ -590,7 +590,7 @@ end
 # --------------------------------------------------------------------------- GV trajectory converter, post filter
 # TrajectoryGVGMMMap(tgmm, μᵛ, Σᵛᵛ) and fvconvert(tgv, X; epochs, α) -- src/trajectory_gmmmap.jl:114-189
 mutable struct TrajectoryGVGMMMap <: TrajectoryConverter
-    tgmm::TrajectoryGMMMap
+    tgmm::TrajectoryConverter        # a TrajectoryGMMMap; under TrajectoryGVGMMMapDiag also a TrajectoryGMMMapBlockDiag
     μᵛ::Vector{Float64}
     Σᵛᵛ::Matrix{Float64}
     h::Ptr{Cvoid}
@@ -598,6 +598,16 @@ mutable struct TrajectoryGVGMMMap <: TrajectoryConverter
         @assert sum(μᵛ .< 0) == 0                                       # src/trajectory_gmmmap.jl:124
         h = Ref{Ptr{Cvoid}}(C_NULL)
         check(ccall((:vcmi_trajgv_create, libvcmi), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ref{Ptr{Cvoid}}),
+                    tgmm.h, μᵛ, Σᵛᵛ, h))
+        tgv = new(tgmm, μᵛ, Σᵛᵛ, h[])
+        finalizer(x -> ccall((:vcmi_trajgv_destroy, libvcmi), Cint, (Ptr{Cvoid},), x.h), tgv)
+        tgv
+    end
+    # over a converter with diagonal conditional precisions (vcmi_trajgv_create_diag): TrajectoryGVGMMMapDiag below
+    function TrajectoryGVGMMMap(tgmm::TrajectoryConverter, μᵛ::Vector{Float64}, Σᵛᵛ::Matrix{Float64}, diag::Bool)
+        @assert diag && sum(μᵛ .< 0) == 0
+        h = Ref{Ptr{Cvoid}}(C_NULL)
+        check(ccall((:vcmi_trajgv_create_diag, libvcmi), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ref{Ptr{Cvoid}}),
                     tgmm.h, μᵛ, Σᵛᵛ, h))
         tgv = new(tgmm, μᵛ, Σᵛᵛ, h[])
         finalizer(x -> ccall((:vcmi_trajgv_destroy, libvcmi), Cint, (Ptr{Cvoid},), x.h), tgv)
@@ -826,7 +836,7 @@ end
 # ---- TrajectoryGMMMapBlockDiag: trajectory conversion straight from a cross-diagonal model (vcmi_traj_create_bdiag) ----------
 # g over static+delta features (dim(g) = 2D).  The conditional covariance of such a model is diagonal exactly, so the converter
 # runs the tridiagonal solver (traj_precision is :diag for good) and the dense model is never formed.  It converts on the device
-# g was created on; em_iters!, traj_precision!(t, :full), cond_loglik and a TrajectoryGVGMMMap over it are refused by the library.
+# g was created on; em_iters!, traj_precision!(t, :full) and cond_loglik are refused by the library; GV: TrajectoryGVGMMMapDiag.
 mutable struct TrajectoryGMMMapBlockDiag <: TrajectoryConverter
     gmmmap::GMMMapBlockDiag
     h::Ptr{Cvoid}
@@ -838,6 +848,13 @@ mutable struct TrajectoryGMMMapBlockDiag <: TrajectoryConverter
         t
     end
 end
+# TrajectoryGVGMMMapDiag(tgmm, μᵛ, Σᵛᵛ): the GV converter over DIAGONAL conditional precisions -- tgmm a TrajectoryGMMMap with
+# traj_precision :diag, or a TrajectoryGMMMapBlockDiag.  The likelihood gradient of the ascent is a three-point stencil per static
+# dimension, O(T D) per epoch (csrc/traj_gv_diag.hip).  A TrajectoryGVGMMMap in every other respect: fvconvert, vc and their
+# batch and device forms are the methods above.  It converts only while tgmm's precision is :diag (the library refuses otherwise,
+# and a TrajectoryGVGMMMap(tgmm, μᵛ, Σᵛᵛ) over the same tgmm keeps refusing while it is).
+TrajectoryGVGMMMapDiag(tgmm::Union{TrajectoryGMMMap,TrajectoryGMMMapBlockDiag}, μᵛ::Vector{Float64}, Σᵛᵛ::Matrix{Float64}) =
+    TrajectoryGVGMMMap(tgmm, μᵛ, Σᵛᵛ, true)
 traj_precision(t::TrajectoryGMMMapBlockDiag) = TRAJ_PRECISIONS[Int(ccall((:vcmi_traj_get_precision, libvcmi), Cint, (Ptr{Cvoid},), t.h)) + 1]
 em_iters(t::TrajectoryGMMMapBlockDiag) = Int(ccall((:vcmi_traj_get_em, libvcmi), Cint, (Ptr{Cvoid},), t.h))
 Base.length(t::TrajectoryGMMMapBlockDiag) = Int(ccall((:vcmi_traj_length, libvcmi), Int64, (Ptr{Cvoid},), t.h))

@@ -151,8 +151,8 @@ class TrajectoryGMMMap(TrajectoryConverter):
         reference's conversion.  "diag": the conditional covariance of every mixture taken as diagonal, as MLPG is commonly
         run -- the normal equations fall apart into tridiagonal systems per static dimension and frame parity, solved in
         O(T D) (csrc/traj_diag.hip).  fvconvert, fvconvert_batch, vc and vc_batch pick the setting up from the converter.
-        Not together with em_iters > 0 or under a TrajectoryGVGMMMap (VCMIError); cond_loglik always evaluates the
-        full-covariance model."""
+        Not together with em_iters > 0 or under a TrajectoryGVGMMMap (VCMIError; the GV converter over "diag" is
+        DiagTrajectoryGVGMMMap); cond_loglik always evaluates the full-covariance model."""
         return self._PRECISIONS[int(_lib.lib.vcmi_traj_get_precision(self._h))]
 
     @precision.setter
@@ -279,7 +279,8 @@ class BlockDiagTrajectoryGMMMap(TrajectoryGMMMap):
     (4D,4D,M) model is never formed (include/vcmi.h: vcmi_traj_create_bdiag; csrc/gmmmap_bdiag.hip, mode 3).  Equal to
     TrajectoryGMMMap(GMMMap(weights, mu, expand_block_diag(covars)), T, precision="diag") to rounding.  fvconvert,
     fvconvert_batch, vc and vc_batch are TrajectoryGMMMap's; precision is "diag" for good, and em_iters > 0, precision = "full",
-    cond_loglik and a TrajectoryGVGMMMap over it are refused (VCMIError).  Converts on the device g was created on."""
+    cond_loglik and a TrajectoryGVGMMMap over it are refused (VCMIError); global variance: DiagTrajectoryGVGMMMap.  Converts on the
+    device g was created on."""
 
     def __init__(self, g, T):
         if not isinstance(g, BlockDiagGMMMap):
@@ -294,6 +295,8 @@ class TrajectoryGVGMMMap(TrajectoryConverter):
     """TrajectoryGVGMMMap(tgmm, mu^v, Sigma^vv) -- src/trajectory_gmmmap.jl:114-137: trajectory conversion followed
     by gradient ascent on the likelihood that includes the global variance (Toda et al. 2007, eqs. (52), (58))."""
 
+    _create = staticmethod(_lib.lib.vcmi_trajgv_create)
+
     def __init__(self, tgmm, muv, sigmavv):
         muv = np.ascontiguousarray(np.asarray(muv, dtype=np.float64).reshape(-1))
         sigmavv = jl_matrix(sigmavv, "sigmavv")
@@ -304,7 +307,7 @@ class TrajectoryGVGMMMap(TrajectoryConverter):
             raise AssertionError("the GV mean must be non-negative")
         self.tgmm = tgmm
         h = C.c_void_p()
-        _lib.check(_lib.lib.vcmi_trajgv_create(tgmm._h, _lib.dptr(muv), _lib.dptr(sigmavv), C.byref(h)))
+        _lib.check(self._create(tgmm._h, _lib.dptr(muv), _lib.dptr(sigmavv), C.byref(h)))
         self._h = h
 
     def __del__(self, _destroy=_lib.lib.vcmi_trajgv_destroy):     # bound at definition: module globals may be gone at exit
@@ -379,3 +382,14 @@ class TrajectoryGVGMMMap(TrajectoryConverter):
                                                      out_off, stream)
 
         return _vc_batch(self, fms, postfilter, delta, host, dev)
+
+
+class DiagTrajectoryGVGMMMap(TrajectoryGVGMMMap):
+    """DiagTrajectoryGVGMMMap(tgmm, mu^v, Sigma^vv): the global-variance conversion of TrajectoryGVGMMMap over a converter with
+    DIAGONAL conditional precisions -- a TrajectoryGMMMap(precision="diag") or a BlockDiagTrajectoryGMMMap.  The likelihood
+    gradient of the ascent is then a three-point stencil per static dimension, O(T D) per epoch (csrc/traj_gv_diag.hip;
+    include/vcmi.h: vcmi_trajgv_create_diag).  fvconvert, fvconvert_batch, vc and vc_batch are TrajectoryGVGMMMap's.  The
+    converter must have precision "diag" when this is made and whenever it converts (VCMIError otherwise; usable again after
+    the switch back); a TrajectoryGVGMMMap over the same converter keeps refusing while the precision is "diag"."""
+
+    _create = staticmethod(_lib.lib.vcmi_trajgv_create_diag)
