@@ -508,6 +508,24 @@ int vcmi_traj_cond_loglik_dev(vcmi_traj *t, const double *dX, const double *dY, 
 /* objective at each E-step of the handle's last conversion call, summed over its utterances: min(cap, iters) values
  * (entry k = L(y^k), k = 0 .. iters-1; entries beyond the iterations of that call are NaN) */
 int vcmi_traj_em_history(const vcmi_traj *t, double *L, int cap);
+/* The same re-estimation over a handle of vcmi_traj_create_bdiag (any other handle: VCMI_ERR_ARG; iters < 0: VCMI_ERR_ARG), in
+ * closed form on the vector pipe: the conditional covariance of a cross-diagonal model is diagonal exactly, so Q_m = diag(q_m),
+ * the quadratic form is sum_k q_km e_k^2, the blended precision of a frame is a vector of 2D doubles and the M-step is the
+ * tridiagonal solve of vcmi_traj_set_precision(DIAG) over a per-frame table (statement: csrc/traj_em_bdiag.hip).  One fused
+ * kernel per iteration does the E-step and both M-step sums, then the per-utterance objective and the solve; nothing per
+ * (frame, mixture) goes to HBM and nothing is read back inside the loop.  vcmi_traj_get_em and vcmi_traj_em_history report the
+ * setting and the objective; vcmi_traj_convert, _batch, _batch_dev, the vcmi_vc_traj family and vcmi_vc_traj_batch[_dev] honour
+ * it; with 0 the handle issues the launches of vcmi_traj_create_bdiag alone.  vcmi_traj_set_em(t, n > 0) keeps refusing such
+ * a handle.  Every convert entry of a vcmi_trajgv of vcmi_trajgv_create_diag over t returns VCMI_ERR_ARG while iters > 0 (GV over
+ * re-estimated trajectories is not provided) and converts again after vcmi_traj_set_em_bdiag(t, 0).
+ * Device scratch while EM runs, on the handle, for the N frames of a call: qbar, 2D N doubles; lse and the identity index the
+ * solver reads, N words each (N > 2^31 - 2: VCMI_ERR_DIM before any launch); the tile job list, 8 bytes per 64 (or 32) frames;
+ * released as vcmi_traj_set_em's. */
+int vcmi_traj_set_em_bdiag(vcmi_traj *t, int iters);
+/* L(y) = log P(W y | X) for a handle of vcmi_traj_create_bdiag: vcmi_traj_cond_loglik[_dev]'s arguments and rules, evaluated by
+ * the fused kernel's L-only mode. */
+int vcmi_traj_cond_loglik_bdiag(vcmi_traj *t, const double *X, const double *Y, int64_t T, double *L);
+int vcmi_traj_cond_loglik_bdiag_dev(vcmi_traj *t, const double *dX, const double *dY, int64_t T, double *dL, void *stream);
 /* vc(c::TrajectoryConverter, fm (2D+1,T)) -> out (D+1,T) in chunks of length(t) frames; src/common.jl:31-63 */
 int vcmi_vc_traj(vcmi_traj *t, const double *fm, int64_t T, double *out);
 /* push_delta(src (D,T)) -> out (2D,T); src/datasets.jl:6-13.  Host matrices, host arithmetic (O(DT), no device needed). */

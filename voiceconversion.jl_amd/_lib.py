@@ -152,6 +152,9 @@ SIGNATURES = {
     "vcmi_traj_cond_loglik": (_int, [_vp, _dp, _dp, _i64, _dp]),
     "vcmi_traj_cond_loglik_dev": (_int, [_vp, _vp, _vp, _i64, _vp, _vp]),
     "vcmi_traj_em_history": (_int, [_vp, _dp, _int]),
+    "vcmi_traj_set_em_bdiag": (_int, [_vp, _int]),
+    "vcmi_traj_cond_loglik_bdiag": (_int, [_vp, _dp, _dp, _i64, _dp]),
+    "vcmi_traj_cond_loglik_bdiag_dev": (_int, [_vp, _vp, _vp, _i64, _vp, _vp]),
     "vcmi_vc_traj": (_int, [_vp, _dp, _i64, _dp]),
     "vcmi_push_delta": (_int, [_dp, _int, _i64, _dp]),
     "vcmi_push_delta_dev": (_int, [_vp, _i64, _int, _i64, _vp, _i64, _vp]),

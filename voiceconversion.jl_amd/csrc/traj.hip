@@ -248,8 +248,9 @@ int traj_run(vcmi_traj *t, std::vector<TrajUtt> &utts, int64_t nframes, bool con
   TrajSolvePlan plan;      // (its host work runs beside the g_t kernel)
   VCMI_TRY(traj_solve_plan(t, utts, nframes, Tmax, gv != nullptr, &plan));
   t->em_run_iters = 0;
-  if (diag) {     // (no EM over a diagonal handle: refused where it is set; GV: a handle of vcmi_trajgv_create_diag)
-    VCMI_TRY(traj_diag_launch(t, plan, st));
+  if (diag) {     // (EM: over a cross-diagonal handle only, vcmi_traj_set_em_bdiag; GV: a handle of vcmi_trajgv_create_diag)
+    VCMI_TRY(traj_diag_launch(t, plan, t->dg_q.p, t->mhat.p, st));
+    if (t->b && t->em_iters > 0) VCMI_TRY(traj_em_bdiag_run(t, utts, plan, st));
     if (gv && gv->epochs >= 0) VCMI_TRY(traj_gvd_launch(t, plan, *gv, st));
     return VCMI_OK;
   }

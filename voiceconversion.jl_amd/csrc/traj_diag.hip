@@ -147,10 +147,10 @@ traj_diag_solve_kernel(const TrajUtt *__restrict__ utts, int nslab, int D, const
   }
 }
 
-int traj_diag_launch(vcmi_traj *t, const TrajSolvePlan &p, hipStream_t st) {
+int traj_diag_launch(vcmi_traj *t, const TrajSolvePlan &p, const double *q, const int64_t *mh, hipStream_t st) {
   const int nslab = (t->D + 31) / 32;
-  hipLaunchKernelGGL(traj_diag_solve_kernel, dim3((unsigned)((int64_t)p.n * nslab)), dim3(64), 0, st, p.du, nslab, t->D, t->dg_q.p,
-                     t->mhat.p, t->gbuf.p, t->ws.p);
+  hipLaunchKernelGGL(traj_diag_solve_kernel, dim3((unsigned)((int64_t)p.n * nslab)), dim3(64), 0, st, p.du, nslab, t->D, q, mh,
+                     t->gbuf.p, t->ws.p);
   VCMI_HIP(hipGetLastError());
   return VCMI_OK;
 }
@@ -185,7 +185,7 @@ extern "C" int vcmi_traj_set_precision(vcmi_traj *t, int kind) {
     return fail(VCMI_ERR_ARG, "vcmi_traj_set_precision: the converter was made from a cross-diagonal model (vcmi_traj_create_bdiag): "
                               "its conditional precisions are diagonal, there is no full matrix to switch to");
   if (kind == VCMI_TRAJ_PRECISION_DIAG) {
-    if (t->em_iters > 0)      // the M-step blends full precision matrices
+    if (t->em_iters > 0 && !t->b)      // the M-step blends full precision matrices (a cross-diagonal handle is DIAG already)
       return fail(VCMI_ERR_ARG, "vcmi_traj_set_precision: the converter has EM re-estimation switched on (vcmi_traj_set_em)");
     VCMI_TRY(traj_diag_ensure(t));
   }

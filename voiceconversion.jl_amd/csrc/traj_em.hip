@@ -542,6 +542,12 @@ int traj_em_run(vcmi_traj *t, const std::vector<TrajUtt> &utts, const TrajSolveP
   return VCMI_OK;
 }
 
+int traj_em_sum_launch(const TrajUtt *du, int n, const double *lse, double *L, hipStream_t st) {
+  hipLaunchKernelGGL(traj_em_sum_kernel, dim3((unsigned)n), dim3(256), 0, st, du, lse, L);
+  VCMI_HIP(hipGetLastError());
+  return VCMI_OK;
+}
+
 // the EM scratch of the handle in bytes: what the release rule weighs
 static size_t traj_em_scratch_bytes(const vcmi_traj *t) {
   return (t->em_lp.n + t->em_gamma.n + t->em_lse.n + t->em_table.n + t->em_L.n + t->em_mh.n) * sizeof(double) +

@@ -49,6 +49,7 @@ struct vcmi_traj {
   vcmi::DevBuf<double> em_lp, em_gamma, em_lse, em_table, em_L;   // log pi and gamma (frames, M); lse (frames); [Q_1..Q_M | Qbar of the mixed frames]; L (iteration, utterance)
   vcmi::DevBuf<int> em_pure, em_mix;      // per frame: mixture of a pure frame or -1; the mixed frames, then their count
   vcmi::DevBuf<int64_t> em_mh;            // table index + 1 per frame
+  vcmi::DevBuf<int32_t> em_jobs;          // cross-diagonal EM (traj_em_bdiag.hip): the tile jobs of a call, (utterance, first frame)
   int em_run_iters = 0, em_run_n = 0;     // shape of em_L in the last call
   std::vector<double> em_hist;            // L at each E-step of the last call, summed over its utterances
   bool em_time = false;                   // measurement hook (vcmi_debug_traj_em_times): hip events around the steps of an iteration
@@ -139,9 +140,10 @@ int traj_solve_launch(vcmi_traj *t, const TrajSolvePlan &plan, const double *Qs,
 // arithmetic.  Synchronous.
 int traj_diag_ensure(vcmi_traj *t);
 // Solve of the plan's utterances with diagonal conditional precisions: right-hand sides in t->gbuf (made with the diagonal
-// images), t->dg_q, t->mhat; workspace t->ws, nframes * D doubles indexed by frame0 (a plan made in diagonal mode).  Asynchronous
-// on st; never writes t->status.
-int traj_diag_launch(vcmi_traj *t, const TrajSolvePlan &plan, hipStream_t st);
+// images), the precision table q [.][2D] indexed by the low 32 bits of mh[t] - 1 (t->dg_q with t->mhat, or the cross-diagonal
+// EM loop's per-frame table with its identity index); workspace t->ws, nframes * D doubles indexed by frame0 (a plan made in
+// diagonal mode).  Asynchronous on st; never writes t->status.
+int traj_diag_launch(vcmi_traj *t, const TrajSolvePlan &plan, const double *q, const int64_t *mh, hipStream_t st);
 
 // ---- traj_gv.hip ----
 // The GV ascent on the solved trajectories of the plan's utterances, in place (two-team kernel where the frame permutation of
@@ -169,6 +171,14 @@ struct TrajEmRelease {
   vcmi_traj *t;
   ~TrajEmRelease();
 };
+// L[U.idx] = sum of lse over the frames of each of the n utterances du, in a fixed order (traj_em_sum_kernel).  Asynchronous on st.
+int traj_em_sum_launch(const TrajUtt *du, int n, const double *lse, double *L, hipStream_t st);
+
+// ---- traj_em_bdiag.hip ----
+// t->em_iters E/M pairs over a cross-diagonal handle (t->b) after the arg-max solve of traj_run, on st behind it: per iteration
+// the fused E-step + M-step sums, traj_em_sum_launch and traj_diag_launch on the per-frame table.  Nothing is read back inside
+// the loop; the job list is uploaded once (synchronous) before it.  utts: the sorted list the plan was made for.
+int traj_em_bdiag_run(vcmi_traj *t, const std::vector<TrajUtt> &utts, const TrajSolvePlan &plan, hipStream_t st);
 
 // ---- traj.hip ----
 // fvconvert of the utterances (dense X and Y on the device; the list comes back sorted longest first): arg-max, g_t, solve, the EM

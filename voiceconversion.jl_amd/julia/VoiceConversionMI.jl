@@ -18,7 +18,7 @@ module VoiceConversionMI
 
 import LinearAlgebra
 
-export DeviceMatrix, FrameByFrameConverter, TrajectoryConverter, GMMMapParam, GMMMap, GMMMapBlockDiag, slopes, TrajectoryGMMMap, TrajectoryGMMMapBlockDiag,
+export DeviceMatrix, FrameByFrameConverter, TrajectoryConverter, GMMMapParam, GMMMap, GMMMapBlockDiag, slopes, TrajectoryGMMMap, TrajectoryGMMMapBlockDiag, TrajectoryGMMMapBlockDiagEM,
        TrajectoryGVGMMMap, TrajectoryGVGMMMapDiag,
        fvconvert, vc, ncomponents, dim, em_iters, em_iters!, traj_precision, traj_precision!, cond_loglik, em_history,
        VarianceScaling, fvpostf!, fvpostf,
@@ -836,7 +836,8 @@ end
 # ---- TrajectoryGMMMapBlockDiag: trajectory conversion straight from a cross-diagonal model (vcmi_traj_create_bdiag) ----------
 # g over static+delta features (dim(g) = 2D).  The conditional covariance of such a model is diagonal exactly, so the converter
 # runs the tridiagonal solver (traj_precision is :diag for good) and the dense model is never formed.  It converts on the device
-# g was created on; em_iters!, traj_precision!(t, :full) and cond_loglik are refused by the library; GV: TrajectoryGVGMMMapDiag.
+# g was created on; traj_precision!(t, :full) is refused by the library; EM re-estimation: TrajectoryGMMMapBlockDiagEM below;
+# GV: TrajectoryGVGMMMapDiag.
 mutable struct TrajectoryGMMMapBlockDiag <: TrajectoryConverter
     gmmmap::GMMMapBlockDiag
     h::Ptr{Cvoid}
@@ -855,6 +856,33 @@ end
 # and a TrajectoryGVGMMMap(tgmm, μᵛ, Σᵛᵛ) over the same tgmm keeps refusing while it is).
 TrajectoryGVGMMMapDiag(tgmm::Union{TrajectoryGMMMap,TrajectoryGMMMapBlockDiag}, μᵛ::Vector{Float64}, Σᵛᵛ::Matrix{Float64}) =
     TrajectoryGVGMMMap(tgmm, μᵛ, Σᵛᵛ, true)
+# TrajectoryGMMMapBlockDiagEM(g, T; em_iters=1): a TrajectoryGMMMapBlockDiag with EM re-estimation over all mixtures after the
+# arg-max solution (vcmi_traj_set_em_bdiag, csrc/traj_em_bdiag.hip): the same struct -- every method below applies -- with the
+# setting made; em_iters!(t, n) changes it (0: the plain conversion), cond_loglik(t, X, Y) is the objective the iterations
+# raise, em_history(t) its values in the last call.  A TrajectoryGVGMMMapDiag over it converts only while em_iters(t) == 0.
+function TrajectoryGMMMapBlockDiagEM(g::GMMMapBlockDiag, T::Int; em_iters::Int=1)
+    t = TrajectoryGMMMapBlockDiag(g, T)
+    em_iters!(t, em_iters)
+    t
+end
+function em_iters!(t::TrajectoryGMMMapBlockDiag, n::Integer)
+    check(ccall((:vcmi_traj_set_em_bdiag, libvcmi), Cint, (Ptr{Cvoid}, Cint), t.h, n))
+    t
+end
+function cond_loglik(t::TrajectoryGMMMapBlockDiag, X::Matrix{Float64}, Y::Matrix{Float64})
+    (size(X, 1) == dim(t) && 2 * size(Y, 1) == size(X, 1) && size(X, 2) == size(Y, 2)) || throw(DimensionMismatch("Inconsistent dimentions."))
+    L = Ref{Float64}(0.0)
+    check(ccall((:vcmi_traj_cond_loglik_bdiag, libvcmi), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Int64, Ref{Float64}),
+                t.h, X, Y, size(X, 2), L))
+    L[]
+end
+function em_history(t::TrajectoryGMMMapBlockDiag)
+    n = max(em_iters(t), 1024)
+    L = Vector{Float64}(undef, n)
+    check(ccall((:vcmi_traj_em_history, libvcmi), Cint, (Ptr{Cvoid}, Ptr{Float64}, Cint), t.h, L, n))
+    k = findfirst(isnan, L)
+    k === nothing ? L : L[1:k - 1]
+end
 traj_precision(t::TrajectoryGMMMapBlockDiag) = TRAJ_PRECISIONS[Int(ccall((:vcmi_traj_get_precision, libvcmi), Cint, (Ptr{Cvoid},), t.h)) + 1]
 em_iters(t::TrajectoryGMMMapBlockDiag) = Int(ccall((:vcmi_traj_get_em, libvcmi), Cint, (Ptr{Cvoid},), t.h))
 Base.length(t::TrajectoryGMMMapBlockDiag) = Int(ccall((:vcmi_traj_length, libvcmi), Int64, (Ptr{Cvoid},), t.h))

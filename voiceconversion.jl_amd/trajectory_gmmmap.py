@@ -152,7 +152,8 @@ class TrajectoryGMMMap(TrajectoryConverter):
         run -- the normal equations fall apart into tridiagonal systems per static dimension and frame parity, solved in
         O(T D) (csrc/traj_diag.hip).  fvconvert, fvconvert_batch, vc and vc_batch pick the setting up from the converter.
         Not together with em_iters > 0 or under a TrajectoryGVGMMMap (VCMIError; the GV converter over "diag" is
-        DiagTrajectoryGVGMMMap); cond_loglik always evaluates the full-covariance model."""
+        DiagTrajectoryGVGMMMap); cond_loglik always evaluates the full-covariance model.  EM re-estimation over diagonal
+        precisions exists where they are exact: BlockDiagTrajectoryEMGMMMap, over a cross-diagonal model."""
         return self._PRECISIONS[int(_lib.lib.vcmi_traj_get_precision(self._h))]
 
     @precision.setter
@@ -172,6 +173,9 @@ class TrajectoryGMMMap(TrajectoryConverter):
     def em_iters(self, n):
         _lib.check(_lib.lib.vcmi_traj_set_em(self._h, int(n)))
 
+    _cond_loglik = staticmethod(_lib.lib.vcmi_traj_cond_loglik)
+    _cond_loglik_dev = staticmethod(_lib.lib.vcmi_traj_cond_loglik_dev)
+
     def cond_loglik(self, X, Y):
         """L(y) = log P(W y | X) for one utterance, X (2D,T), Y (D,T): the objective the EM iterations raise.  numpy
         matrices give a float; device tensors (dense, unit stride along the features) a one-element device tensor."""
@@ -185,13 +189,13 @@ class TrajectoryGMMMap(TrajectoryConverter):
             if T > 1 and (ldx != D2 or ldy != D):
                 raise ValueError("cond_loglik: X and Y must be dense")
             out = torch.empty(1, dtype=torch.float64, device=X.device)
-            _lib.check(_lib.lib.vcmi_traj_cond_loglik_dev(self._h, xp, yp, T, out.data_ptr(), current_stream_ptr()))
+            _lib.check(self._cond_loglik_dev(self._h, xp, yp, T, out.data_ptr(), current_stream_ptr()))
             return out
         X, Y = jl_matrix(X, "X"), jl_matrix(Y, "Y")
         if X.shape[0] != self._dim() or 2 * Y.shape[0] != X.shape[0] or X.shape[1] != Y.shape[1]:
             raise _lib.DimensionMismatch("Inconsistent dimentions.")
         L = C.c_double(0.0)
-        _lib.check(_lib.lib.vcmi_traj_cond_loglik(self._h, _lib.dptr(X), _lib.dptr(Y), X.shape[1], C.byref(L)))
+        _lib.check(self._cond_loglik(self._h, _lib.dptr(X), _lib.dptr(Y), X.shape[1], C.byref(L)))
         return float(L.value)
 
     def em_history(self):
@@ -280,7 +284,7 @@ class BlockDiagTrajectoryGMMMap(TrajectoryGMMMap):
     TrajectoryGMMMap(GMMMap(weights, mu, expand_block_diag(covars)), T, precision="diag") to rounding.  fvconvert,
     fvconvert_batch, vc and vc_batch are TrajectoryGMMMap's; precision is "diag" for good, and em_iters > 0, precision = "full",
     cond_loglik and a TrajectoryGVGMMMap over it are refused (VCMIError); global variance: DiagTrajectoryGVGMMMap.  Converts on the
-    device g was created on."""
+    device g was created on.  EM re-estimation over all mixtures and cond_loglik for such a model: BlockDiagTrajectoryEMGMMMap."""
 
     def __init__(self, g, T):
         if not isinstance(g, BlockDiagGMMMap):
@@ -289,6 +293,33 @@ class BlockDiagTrajectoryGMMMap(TrajectoryGMMMap):
         h = C.c_void_p()
         _lib.check(_lib.lib.vcmi_traj_create_bdiag(g._h, int(T), C.byref(h)))
         self._h = h
+
+
+class BlockDiagTrajectoryEMGMMMap(BlockDiagTrajectoryGMMMap):
+    """BlockDiagTrajectoryEMGMMMap(g::BlockDiagGMMMap, T, em_iters=1): BlockDiagTrajectoryGMMMap with EM re-estimation over ALL
+    mixtures (Toda et al. 2007, eqs. 30-36: every mixture weighted by P(m | X_t, Y_t)) after the arg-max solution, in closed
+    form from the cross-diagonal parameters: the blended precision of a frame is a vector of 2D doubles and every M-step is the
+    tridiagonal solve again (include/vcmi.h: vcmi_traj_set_em_bdiag; csrc/traj_em_bdiag.hip).  Equal to
+    TrajectoryGMMMap(GMMMap(weights, mu, expand_block_diag(covars)), T, em_iters=n) to rounding.  em_iters may be changed at any
+    time (0: BlockDiagTrajectoryGMMMap's conversion, launch for launch); cond_loglik evaluates L(y) = log P(W y | X); fvconvert,
+    fvconvert_batch, vc, vc_batch and em_history are inherited.  A DiagTrajectoryGVGMMMap over it converts only while
+    em_iters == 0 (VCMIError otherwise)."""
+
+    _cond_loglik = staticmethod(_lib.lib.vcmi_traj_cond_loglik_bdiag)
+    _cond_loglik_dev = staticmethod(_lib.lib.vcmi_traj_cond_loglik_bdiag_dev)
+
+    def __init__(self, g, T, em_iters=1):
+        super().__init__(g, T)
+        self.em_iters = em_iters
+
+    @property
+    def em_iters(self):
+        """EM iterations after the arg-max solution; 0: the conversion of BlockDiagTrajectoryGMMMap"""
+        return int(_lib.lib.vcmi_traj_get_em(self._h))
+
+    @em_iters.setter
+    def em_iters(self, n):
+        _lib.check(_lib.lib.vcmi_traj_set_em_bdiag(self._h, int(n)))
 
 
 class TrajectoryGVGMMMap(TrajectoryConverter):
