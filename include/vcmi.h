@@ -174,6 +174,16 @@ int vcmi_gmmmap_prune_stats(vcmi_gmmmap *g, int enable, int64_t *evaluated);
  *                               every shape gives the dense loop's y to rounding. */
 int vcmi_gmmmap_convert_plan(vcmi_gmmmap *g, int64_t *mfma_issued, int *shape, double *model_active_frac,
                              double *model_undecided_frac);
+/* The group radius of shape 3, for measurement.  For every mixture g the library derives at creation, on the host, a radius R_g
+ * such that a frame with |z_g|^2 < R_g has every other mixture more than `prune` nats under mixture g (a lower bound of
+ * |z_m|^2 + lambda |z_g|^2 from both covariances, up to 128 mixtures); a workgroup all of whose frames belong to one group and lie
+ * inside its radius does not run the screen at all.  It skips a proof, never a term: y is the same bit for bit.
+ *   *skipped (may be NULL)    workgroups that skipped the screen since vcmi_gmmmap_prune_stats last enabled the counters
+ *                             (0 while they are off); synchronises;
+ *   *in_use (may be NULL)     1 when the kernel takes the test for this model: decided once, at creation, when at least 254 of
+ *                             the 256 frames drawn from the model itself lie inside the radius of their mixture;
+ *   *pass_frac (may be NULL)  that share. */
+int vcmi_gmmmap_screen_radius_stats(vcmi_gmmmap *g, int64_t *skipped, int *in_use, double *pass_frac);
 
 /* ---------------------------------------------------------------------------------------------
  * Cross-diagonal GMMMap -- frame-by-frame conversion (src/gmmmap.jl:101-118, src/gmm.jl:24-58) with the model that

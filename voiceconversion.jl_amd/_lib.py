@@ -81,6 +81,7 @@ SIGNATURES = {
     "vcmi_gmmmap_set_prune": (_int, [_vp, C.c_double]),
     "vcmi_gmmmap_prune_stats": (_int, [_vp, _int, _ip]),
     "vcmi_gmmmap_convert_plan": (_int, [_vp, _ip, C.POINTER(_int), _dp, _dp]),
+    "vcmi_gmmmap_screen_radius_stats": (_int, [_vp, _ip, C.POINTER(_int), _dp]),
     "vcmi_bdmap_create": (_int, [_dp, _dp, _dp, _int, _int, _int, C.POINTER(_vp)]),
     "vcmi_bdmap_destroy": (_int, [_vp]),
     "vcmi_bdmap_dim": (_int, [_vp]),
@@ -284,6 +285,7 @@ DBG_GROUP_KEY_FP64 = 67108864
 DBG_ESTEP_NO_HARD = 134217728
 DBG_ESTEP_NO_SMALL = 1024
 DBG_MC2E_TWO_WAVES, DBG_MC2E_ONE_WAVE = 268435456, 536870912
+DBG_SCREEN_NO_RADIUS = 1073741824
 
 
 def estep_last_soft():
@@ -295,6 +297,23 @@ def estep_last_soft():
     v = C.c_int64(0)
     check(fn(C.byref(v)))
     return int(v.value)
+
+
+def screen_radius_host(w, mu, sigma, swap=False, prune=46.0):
+    """Test hook (host only, no device): the group radius of the screened fvconvert for the joint model (w (M), mu (Dj,M),
+    sigma (Dj,Dj,M), Julia memory images).  Returns (c (M,M,J) with NaN where there is no bound, R (M), lmin (M), the share of
+    the model's own profile frames inside their radius); lambda_j = 2^(j - 3)."""
+    import numpy as np
+    fn = lib.vcmi_debug_screen_radius
+    fn.argtypes = [_dp, _dp, _dp, _int, _int, _int, C.c_double, _dp, _dp, _dp, _dp]
+    fn.restype = _int
+    w = np.ascontiguousarray(w, dtype=np.float64)
+    mu = np.asfortranarray(mu, dtype=np.float64)
+    sigma = np.asfortranarray(sigma, dtype=np.float64)
+    Dj, M = mu.shape
+    c, R, lmin, frac = np.empty((M, M, 7)), np.empty(M), np.empty(M), C.c_double(0.0)
+    check(fn(dptr(w), dptr(mu), dptr(sigma), Dj, M, 1 if swap else 0, float(prune), dptr(c), dptr(R), dptr(lmin), C.byref(frac)))
+    return c, R, lmin, frac.value
 
 
 def debug_force(flags):

@@ -816,7 +816,8 @@ static int launch_screen(const vcmi_gmmmap *g, const double *dX, int64_t ldx, in
   VCMI_TRY(set_max_dynamic_lds(kern, shmem, attr_done));
   const int64_t per_wg = (int64_t)16 * FT * WAVES;
   hipLaunchKernelGGL(kern, dim3((unsigned)((T + per_wg - 1) / per_wg)), dim3(WAVES * 64), shmem, st, g->packed.p, B16 ? g->packedQ16.p : g->packedQ.p, g->screen_rpm,
-                     g->M, g->D, dX, ldx, T, dY, ldy, g->prune, g->prune_count.p, perm, gbase, B16 ? g->packedQ2.p : nullptr);
+                     g->M, g->D, dX, ldx, T, dY, ldy, g->prune, g->prune_count.p, perm, gbase, B16 ? g->packedQ2.p : nullptr,
+                     g->radius_on && !debug_flag(kDbgScreenNoRadius) ? g->lmin.p : nullptr);
   VCMI_HIP(hipGetLastError());
   return VCMI_OK;
 }

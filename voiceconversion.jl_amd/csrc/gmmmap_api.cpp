@@ -46,7 +46,10 @@ int gmmmap_member(vcmi_gmmmap *g, int member, vcmi_gmmmap **out) {
     r = n;
   }
   r->kernel_choice = g->kernel_choice;
-  r->prune = g->prune;
+  if (r->prune != g->prune) {
+    r->prune = g->prune;
+    VCMI_TRY(screen_radius_upload(r));           // (on the member's device: this runs on its worker thread)
+  }
   *out = r;
   return VCMI_OK;
 }
@@ -133,8 +136,8 @@ extern "C" int vcmi_gmmmap_prune_stats(vcmi_gmmmap *g, int enable, int64_t *eval
     }
   }
   if (enable) {
-    if (!g->prune_count.p) VCMI_TRY(g->prune_count.alloc(3));
-    VCMI_HIP(hipMemset(g->prune_count.p, 0, 3 * sizeof(unsigned long long)));
+    if (!g->prune_count.p) VCMI_TRY(g->prune_count.alloc(4));
+    VCMI_HIP(hipMemset(g->prune_count.p, 0, 4 * sizeof(unsigned long long)));
   } else {
     g->prune_count.release();
   }
@@ -161,7 +164,31 @@ extern "C" int vcmi_gmmmap_convert_plan(vcmi_gmmmap *g, int64_t *mfma_issued, in
 extern "C" int vcmi_gmmmap_set_prune(vcmi_gmmmap *g, double nats) {
   if (!g) return fail(VCMI_ERR_ARG, "vcmi_gmmmap_set_prune: NULL handle");
   if (!(nats >= 40.0)) return fail(VCMI_ERR_ARG, "vcmi_gmmmap_set_prune: threshold %g nats would change y at double precision (>= 40)", nats);
-  g->prune = nats >= 1e300 ? INFINITY : nats;
+  const double prune = nats >= 1e300 ? INFINITY : nats;
+  if (prune == g->prune) return VCMI_OK;
+  g->prune = prune;
+  // the group radii of shape 3 depend on it: lmin again from the host table (no factorisation), on the handle's device
+  if (g->radius.empty()) return VCMI_OK;
+  int dev = 0;
+  VCMI_HIP(hipGetDevice(&dev));
+  if (dev != g->device) VCMI_HIP(hipSetDevice(g->device));
+  const int rc = screen_radius_upload(g);
+  if (dev != g->device) VCMI_HIP(hipSetDevice(dev));
+  return rc;
+}
+
+extern "C" int vcmi_gmmmap_screen_radius_stats(vcmi_gmmmap *g, int64_t *skipped, int *in_use, double *pass_frac) {
+  if (!g) return fail(VCMI_ERR_ARG, "vcmi_gmmmap_screen_radius_stats: NULL handle");
+  if (skipped) {
+    *skipped = 0;
+    if (g->prune_count.p) {
+      unsigned long long h = 0;
+      VCMI_HIP(hipMemcpy(&h, g->prune_count.p + 3, sizeof(h), hipMemcpyDeviceToHost));
+      *skipped = (int64_t)h;
+    }
+  }
+  if (in_use) *in_use = g->radius_on ? 1 : 0;
+  if (pass_frac) *pass_frac = g->radius_pass_frac;
   return VCMI_OK;
 }
 

@@ -20,6 +20,26 @@ struct ModelProfile {
   // ... whose four-row bound reaches the frame's best log-density: what predict's screen (gmmmap_screen_argmax_kernel) would
   // have to evaluate in full besides the frame's own mixture
   double argmax_survivors = 1.0;
+  // the mixture every one of the 256 frames was drawn from and its exact |z|^2 there: what the group radius is judged on
+  std::vector<int> own_m;
+  std::vector<double> own_z2;
+};
+
+// The certified radius of every group for the screen of shape 3 (gmmmap_prepare.cpp: screen_radius_table, screen_radius_lmin;
+// gmmmap_screen.hpp, step 1b).  For a group g, another mixture m, d = mu_m - mu_g and any lambda > 0, every x has
+//   |z_m(x)|^2 + lambda |z_g(x)|^2 >= c_gm(lambda) = d' inv(Sxx_m + Sxx_g / lambda) d          (the minimum of a convex quadratic)
+// so l_m(x) < l_g(x) - prune whenever |z_g(x)|^2 < (c_gm(lambda) - 2 (lc_m - lc_g + prune)) / (1 + lambda): weak duality, any
+// lambda gives a valid radius, the grid only decides how sharp it is.  The table depends on the model alone and stays on the
+// host; the radii follow from it for any prune without a factorisation.
+struct ScreenRadius {
+  static constexpr int J = 7;                         // lambda_j = 2^(j - 3): 1/8 .. 8, closed under 1 / lambda (c_mg(1 / lambda) = c_gm(lambda) / lambda)
+  static constexpr int kMaxM = 128;                   // the cap: M^2 J doubles are 0.9 MB and M (M - 1) J / 2 = 57 k D x D factorisations there
+  static double lambda(int j) { return (double)(1 << j) / 8.0; }
+  int D = 0, M = 0;
+  std::vector<double> c;                              // [M][M][J]; NaN: no bound (the diagonal, a factorisation that failed)
+  std::vector<double> lc, mu_norm, l_norm;            // [M]: log-constants, |mu^x_m|, |L_m|_F (>= the longest half-axis of the unit ellipsoid)
+  double u_norm = 0.0;                                // max over m of |U_m|_F
+  bool empty() const { return c.empty(); }
 };
 }  // namespace vcmi
 
@@ -32,12 +52,19 @@ struct vcmi_gmmmap {
   // fvconvert skips the regression of mixture m for a 16-frame tile when l_m < max_l - prune (nats) for all its frames:
   // the posterior there is below e^-prune (1e-20 at 46: under the rounding error of the sum).  +inf: dense loop.
   double prune = 46.0;
-  vcmi::DevBuf<unsigned long long> prune_count;   // optional diagnostic counters (vcmi_gmmmap_prune_stats): [0] (tile, mixture) regressions, [1] FP64 MFMAs issued, [2] BF16 MFMAs of the screen
+  vcmi::DevBuf<unsigned long long> prune_count;   // optional diagnostic counters (vcmi_gmmmap_prune_stats): [0] (tile, mixture) regressions, [1] FP64 MFMAs issued, [2] BF16 MFMAs of the screen, [3] workgroups that skipped the screen (group radius)
   vcmi::ModelProfile model;
   // rows per mixture of fvconvert's screen (choose_screen_rows(): the cheapest for this model) and what that many rows leave
   // undecided (model.undecided_rows): small (<= kScreenModelFrac) -> grouped calls run the screening kernel
   int screen_rpm = 4;
   double model_undecided4_frac = 1.0;
+  // the group radius of shape 3 (ScreenRadius above): the host table, lmin[g] = lc_g - R_g / 2 on the device for the current
+  // prune (+inf: nothing is certified for g), the share of the model's own 256 frames inside their mixture's radius and
+  // whether the kernel looks at lmin at all (decided once, at creation: choose_screen_radius)
+  vcmi::ScreenRadius radius;
+  vcmi::DevBuf<double> lmin;
+  double radius_pass_frac = 0.0;
+  bool radius_on = false;
 
   // host copies kept for accessors and for TrajectoryGMMMap's constructor (row-major (D,D) per mixture)
   std::vector<double> h_A_julia;   // Julia memory image (D,D,M) of ΣʸˣΣˣˣ⁻¹
@@ -123,6 +150,9 @@ int gmmmap_posterior_device(vcmi_gmmmap *g, const double *dX, int64_t ldx, int64
 int gmmmap_predict_device(vcmi_gmmmap *g, const double *dX, int64_t ldx, int64_t T, int64_t *didx, hipStream_t st, bool allow_screen = true);
 // vcmi_gmmmap_convert_plan's shape: -1 no tile kernel for g, 0 dense (prune = +inf), 1 broad, 2 peaked, 3 screened
 int gmmmap_convert_plan_shape(const vcmi_gmmmap *g);
+// lmin of g->radius for g->prune -> g->lmin on the current device (gmmmap_prepare.cpp); waits for the handle's last grouped
+// call, whose kernel may still read the buffer.  Nothing to do for a handle without a table.
+int screen_radius_upload(vcmi_gmmmap *g);
 // Device group support (devgroup.hpp, gmmmap_api.cpp): gmmmap_sync_replicas is called by the host thread before group_run; inside the
 // run member i obtains its converter (g itself on g's device, else a replica created on first use).
 void gmmmap_sync_replicas(vcmi_gmmmap *g);

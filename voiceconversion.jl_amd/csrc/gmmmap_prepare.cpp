@@ -40,6 +40,8 @@ int factor_model(vcmi_gmmmap *g, HostModel &hm, const double *w, const double *m
   hm = HostModel{D, DP, M, px_only, /*U, A*/ V(pp * M), V(reg * pp * M), /*cz, b*/ V((size_t)DP * M), V(reg * DP * M), /*lc*/ V(M),
                  /*P, cP*/ V(want_screen ? (size_t)M * 4 * DP : 0), V(want_screen ? (size_t)M * 4 : 0),
                  /*P2, cP2*/ V(want_screen2 ? (size_t)M * 16 * DP : 0), V(want_screen2 ? (size_t)M * 16 : 0)};
+  // (the group radius of that screen: the Hermitian source blocks themselves, where the M^2 table stays small)
+  if (want_screen && screen_has_kernel(DP) && M >= 2 && M <= ScreenRadius::kMaxM) hm.Sxx.assign(dd * M, 0.0);
   V &hU = hm.U, &hA = hm.A, &hcz = hm.cz, &hb = hm.b, &hlc = hm.lc, &hP = hm.P, &hcP = hm.cP, &hP2 = hm.P2, &hcP2 = hm.cP2;
   const int xo = (swap && !px_only) ? D : 0, yo = px_only ? 0 : (swap ? 0 : D);   // src/gmmmap.jl:74-78
   const double LOG2PI = 1.8378770664093454835606594728112;
@@ -89,6 +91,9 @@ int factor_model(vcmi_gmmmap *g, HostModel &hm, const double *w, const double *m
       continue;
     }
     la::lower_inverse(L.data(), D, Ui.data());
+    if (!hm.Sxx.empty())
+      for (int r = 0; r < D; ++r)
+        for (int c = 0; c < D; ++c) hm.Sxx[dd * m + (size_t)r * D + c] = r <= c ? Sxx[(size_t)r * D + c] : Sxx[(size_t)c * D + r];
     double logdiag = 0.0;
     for (int d = 0; d < D; ++d) logdiag += std::log(L[(size_t)d * D + d]);
     hlc[m] = (w[m] > 0.0) ? std::log(w[m]) - 0.5 * (D * LOG2PI + 2.0 * logdiag)
@@ -172,6 +177,8 @@ ModelProfile profile_model(const HostModel &hm, const std::vector<double> &hmux,
   // per frame, the mixtures {within e^-46 of the best | ... on the last 16-row whitening tile's share alone | whose bound from
   // four rows reaches the best log-density (predict's screen) | ... on the 4 / 2 / 1 strongest screening rows alone (shape 3)}
   std::vector<int> tally(6 * S, 0);
+  pf.own_m.assign(S, 0);
+  pf.own_z2.assign(S, 0.0);
   const int r_last = 16 * ((DP + 15) / 16 - 1);                       // first row of the last whitening tile
   host_parallel_for(S, 8, [&](int64_t lo, int64_t hi) {
     std::vector<double> x(D), z(D);
@@ -219,6 +226,10 @@ ModelProfile profile_model(const HostModel &hm, const std::vector<double> &hmux,
               if (i < (4 >> c)) ql4[c] += pz * pz;
           }
         l[n] = hlc[n] - 0.5 * q;
+        if (n == m) {
+          pf.own_m[s] = m;
+          pf.own_z2[s] = q;
+        }
         qlast[n] = ql;
         for (int c = 0; c < 3; ++c) qlast4[3 * (size_t)n + c] = ql4[c];
         best = std::max(best, l[n]);
@@ -258,6 +269,123 @@ int choose_screen_rows(const ModelProfile &pf, int DP, int M) {
     }
   }
   return best;
+}
+
+// ------------------------------------------------------------------------------------------------
+// the group radius of shape 3 (ScreenRadius, gmmmap_handle.hpp)
+// ------------------------------------------------------------------------------------------------
+static double sum_of_squares(const double *v, int n);
+
+ScreenRadius screen_radius_table(const HostModel &hm, const std::vector<double> &hmux) {
+  constexpr int J = ScreenRadius::J;
+  const int D = hm.D, DP = hm.DP, M = hm.M;
+  const size_t dd = (size_t)D * D, pp = (size_t)DP * DP;
+  ScreenRadius rt;
+  rt.D = D;
+  rt.M = M;
+  rt.c.assign((size_t)M * M * J, std::numeric_limits<double>::quiet_NaN());
+  rt.lc = hm.lc;
+  rt.mu_norm.resize(M);
+  rt.l_norm.resize(M);
+  for (int m = 0; m < M; ++m) {
+    rt.mu_norm[m] = std::sqrt(sum_of_squares(&hmux[(size_t)D * m], D));
+    double tr = 0.0;                                            // |L_m|_F^2 = trace(Sxx_m)
+    for (int d = 0; d < D; ++d) tr += hm.Sxx[dd * m + (size_t)d * D + d];
+    rt.l_norm[m] = std::sqrt(tr);
+    rt.u_norm = std::max(rt.u_norm, std::sqrt(sum_of_squares(&hm.U[pp * m], (int)pp)));
+  }
+  // unordered pairs g < m, a row of the triangle per index: the rows are shared out in pairs (g, M - 2 - g) of equal length
+  host_parallel_for(M - 1, 1, [&](int64_t lo, int64_t hi) {
+    std::vector<double> K(dd), L(dd), d(D), y(D);
+    for (int64_t i = lo; i < hi; ++i) {
+      const int g = (i & 1) ? M - 2 - (int)(i >> 1) : (int)(i >> 1);
+      for (int m = g + 1; m < M; ++m) {
+        if (!(hm.lc[g] > -INFINITY) || !(hm.lc[m] > -INFINITY)) continue;      // (a zero-weight mixture is neither a group nor a competitor)
+        for (int k = 0; k < D; ++k) d[k] = hmux[(size_t)D * m + k] - hmux[(size_t)D * g + k];
+        for (int j = 0; j < J; ++j) {
+          const double lam = ScreenRadius::lambda(j), il = 1.0 / lam;
+          for (int r = 0; r < D; ++r)
+            for (int c = r; c < D; ++c) K[(size_t)r * D + c] = hm.Sxx[dd * m + (size_t)r * D + c] + il * hm.Sxx[dd * g + (size_t)r * D + c];
+          if (!la::cholesky_from_upper(K.data(), D, L.data())) continue;
+          double q = 0.0;                                       // |inv(L) d|^2 = d' inv(K) d
+          for (int r = 0; r < D; ++r) {
+            double acc = d[r];
+            for (int c = 0; c < r; ++c) acc -= L[(size_t)r * D + c] * y[c];
+            y[r] = acc / L[(size_t)r * D + r];
+            q += y[r] * y[r];
+          }
+          rt.c[((size_t)g * M + m) * J + j] = q;
+          rt.c[((size_t)m * M + g) * J + (J - 1 - j)] = q * il; // c_mg(1 / lambda) = c_gm(lambda) / lambda
+        }
+      }
+    }
+  });
+  return rt;
+}
+
+// The rounding margin.  The kernel compares FP64 values of l_m = lc_m - |U_m x - cz_m|^2 / 2; the certificate is about the exact
+// ones.  For x inside the radius |x| <= X = |mu_g| + sqrt(R) |L_g|_F, so every component sum of U_m x - cz_m (D + 1 terms, each
+// at most |U_m row| X) is off by at most (D + 3) eps |U_m row| X and the vector z_m by delta = (D + 3) eps |U_m|_F X in norm --
+// whatever the size of x, which is where models shifted by thousands come in.  |z|^2 is then off by 2 |z| delta + delta^2 plus
+// (D + 2) eps |z|^2 of its own sum, l by half of that plus eps (|lc| + |z|^2 / 2).  The inequality that has to survive is
+// |z_m|^2 - |z_g|^2 - 2 (lc_m - lc_g + prune) > 0 with |z_g|^2 < R and |z_m|^2 >= the bound B <= C = max c: beyond B the left
+// side grows faster than its error (1 against delta / |z_m|), so the error at |z_m|^2 = B counts:
+//   E = 2 (sqrt(C) + sqrt(R)) delta + 2 delta^2 + 2^-40 (C + R + 4 max |lc| + 2 prune)
+// with delta taken sixteen times larger than derived.  R loses FOUR times E (1 + lambda >= 1 turns a loss of R into at least that
+// much room in the inequality) and a factor 1 - 2^-20 on top: the benchmark's radii leave 70 nats unused, nothing here is tight.
+void screen_radius_lmin(const ScreenRadius &rt, double prune, std::vector<double> &R, std::vector<double> &lmin) {
+  constexpr int J = ScreenRadius::J;
+  const int M = rt.M;
+  R.assign(M, -INFINITY);
+  lmin.assign(M, INFINITY);
+  double lcmax = 0.0;
+  for (int m = 0; m < M; ++m)
+    if (rt.lc[m] > -INFINITY) lcmax = std::max(lcmax, std::fabs(rt.lc[m]));
+  for (int g = 0; g < M; ++g) {
+    if (!(rt.lc[g] > -INFINITY) || !(prune < 1e300)) continue;   // a zero-weight group, the dense loop: nothing is certified
+    double r0 = 1e12, cmax = 0.0;                                // (no competitor at all: a radius that still lets a NaN fail)
+    for (int m = 0; m < M; ++m) {
+      if (m == g || !(rt.lc[m] > -INFINITY)) continue;           // a zero-weight mixture is nobody's competitor
+      double best = -INFINITY;
+      for (int j = 0; j < J; ++j) {
+        const double c = rt.c[((size_t)g * M + m) * J + j];
+        if (!(c == c)) continue;
+        cmax = std::max(cmax, c);
+        best = std::max(best, (c - 2.0 * (rt.lc[m] - rt.lc[g] + prune)) / (1.0 + ScreenRadius::lambda(j)));
+      }
+      r0 = std::min(r0, best);
+    }
+    if (!(r0 > 0.0)) continue;
+    const double eps = 0x1p-53;
+    const double xmax = rt.mu_norm[g] + std::sqrt(r0) * rt.l_norm[g];
+    const double delta = 16.0 * (rt.D + 3) * eps * rt.u_norm * xmax;
+    const double E = 2.0 * (std::sqrt(cmax) + std::sqrt(r0)) * delta + 2.0 * delta * delta + 0x1p-40 * (cmax + r0 + 4.0 * lcmax + 2.0 * prune);
+    const double r = (r0 - 4.0 * E) * (1.0 - 0x1p-20);
+    R[g] = r;
+    if (r > 0.0) lmin[g] = rt.lc[g] - 0.5 * r;
+  }
+}
+
+double screen_radius_pass_frac(const ModelProfile &pf, const ScreenRadius &rt, const std::vector<double> &lmin) {
+  if (pf.own_m.empty() || rt.empty()) return 0.0;
+  int pass = 0;
+  for (size_t s = 0; s < pf.own_m.size(); ++s) pass += (rt.lc[pf.own_m[s]] - 0.5 * pf.own_z2[s] >= lmin[pf.own_m[s]]);
+  return (double)pass / (double)pf.own_m.size();
+}
+
+// The test is taken per WORKGROUP: one frame outside its radius and the 128 of them run the screen after all, one L2 round trip
+// later than they would have (stage 0 is then fetched behind the test, not at the top of the kernel).  With a share p of frames
+// inside, p^128 of the workgroups skip about a fifth of the kernel and the others lose about a thirtieth of it: even near
+// p^128 = 0.15, p = 0.985.  254 of the profile's 256 frames (0.992, p^128 = 0.37) is the first count above that; the peaked
+// synthetic models pass with all 256, a model with lam_lo = 1e-2 with a third of them.
+bool choose_screen_radius(double pass_frac) { return pass_frac >= 254.0 / 256.0; }
+
+int screen_radius_upload(vcmi_gmmmap *g) {
+  if (g->radius.empty()) return VCMI_OK;
+  std::vector<double> R, lmin;
+  screen_radius_lmin(g->radius, g->prune, R, lmin);
+  if (g->grp_order.last_use) VCMI_HIP(hipEventSynchronize(g->grp_order.last_use));      // the last grouped call may still read lmin
+  return upload_now(g->lmin, lmin);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -496,6 +624,18 @@ int gmmmap_prepare(vcmi_gmmmap *g, const double *w, const double *mu, const doub
       VCMI_TRY(upload_now(g->packedQ2, pack_screen2_bf16(hm)));
     }
   }
+  // the group radius of that screen: the table, lmin for the handle's prune, and whether this model's own frames stay inside
+  g->radius = ScreenRadius{};
+  g->radius_on = false;
+  g->radius_pass_frac = 0.0;
+  if (!hm.Sxx.empty() && g->packedQ.p) {
+    g->radius = screen_radius_table(hm, g->h_mux);
+    std::vector<double> R, lmin;
+    screen_radius_lmin(g->radius, g->prune, R, lmin);
+    g->radius_pass_frac = screen_radius_pass_frac(g->model, g->radius, lmin);
+    g->radius_on = choose_screen_radius(g->radius_pass_frac);
+    VCMI_TRY(upload_now(g->lmin, lmin));
+  }
   // ... and predict's (gmmmap_screen_argmax_kernel): always four rows per mixture, every tile-kernel dimension
   if (!hm.P.empty()) VCMI_TRY(upload_now(g->packedQA, pack_screen(hm, 4)));
   if (!g->h_mux.empty()) {                            // fvconvert's frame grouping (made for every handle, p(x)-only ones too)
@@ -530,6 +670,29 @@ int gmm_px_create(const double *w, const double *mu, const double *sigma, int D,
 }
 
 }  // namespace vcmi
+
+// Test hook, deliberately absent from include/vcmi.h (like vcmi_debug_force): the group radius of a joint model on the host
+// alone -- no device, no handle.  c (M * M * J, may be NULL): the table, NaN where there is no bound; R, lmin (M each): the
+// radii less their rounding margin and lc_g - R_g / 2 for `prune` (any value: vcmi_gmmmap_set_prune's floor of 40 is not this
+// function's business); *pass_frac (may be NULL): the share of the model's 256 profile frames inside their mixture's radius.
+extern "C" int vcmi_debug_screen_radius(const double *w, const double *mu, const double *sigma, int Dj, int M, int swap, double prune,
+                                        double *c, double *R, double *lmin, double *pass_frac) {
+  using namespace vcmi;
+  if (!w || !mu || !sigma || !R || !lmin) return fail(VCMI_ERR_ARG, "vcmi_debug_screen_radius: NULL argument");
+  if (Dj < 2 || (Dj & 1) || M < 1) return fail(VCMI_ERR_DIM, "vcmi_debug_screen_radius: joint dimension %d / mixtures %d invalid", Dj, M);
+  vcmi_gmmmap g;
+  HostModel hm;
+  VCMI_TRY(factor_model(&g, hm, w, mu, sigma, Dj, M, swap, false));
+  if (hm.Sxx.empty()) return fail(VCMI_ERR_ARG, "vcmi_debug_screen_radius: no group radius for dimension %d, %d mixtures", Dj / 2, M);
+  const ScreenRadius rt = screen_radius_table(hm, g.h_mux);
+  std::vector<double> Rv, lv;
+  screen_radius_lmin(rt, prune, Rv, lv);
+  if (c) memcpy(c, rt.c.data(), rt.c.size() * sizeof(double));
+  memcpy(R, Rv.data(), (size_t)M * sizeof(double));
+  memcpy(lmin, lv.data(), (size_t)M * sizeof(double));
+  if (pass_frac) *pass_frac = screen_radius_pass_frac(profile_model(hm, g.h_mux, w), rt, lv);
+  return VCMI_OK;
+}
 
 // diffgmm(params) -- src/diffgmm.jl:9-25, on the joint parameters mu (2D,M), sigma (2D,2D,M) (host arithmetic: a
 // one-time parameter transform).  Feed the result to vcmi_gmmmap_create for the differential converter.

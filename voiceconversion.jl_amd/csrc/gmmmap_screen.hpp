@@ -13,6 +13,9 @@
 //   1. the mixtures of the workgroup's groups (from gbase: one, or two or three where the workgroup straddles group
 //      boundaries) are evaluated in full -- whitening, regression, softmax -- which makes the running maximum tight for
 //      (almost) all of its frames;
+//   1b. a workgroup with ONE group g whose frames all lie inside the radius the host certified for g (l_g >= lmin[g]: ScreenRadius,
+//      gmmmap_handle.hpp -- a bound from both covariances, made once per model) has nothing to find in steps 2 and 3 and goes
+//      straight to the stores; handles whose own frames do not stay inside their radii pass no lmin and never ask;
 //   2. every quad of mixtures is screened against (running maximum - prune); a mixture that no frame of the workgroup lets
 //      through contributes less than e^-prune to every frame: exactly the terms the other shapes skip.  On the BF16 pipe a
 //      mixture that the four rows leave open for some frame of a wave gets a SECOND LOOK in that wave before it counts: the
@@ -65,7 +68,7 @@ __global__ void __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu
 gmmmap_screen_kernel(const double *__restrict__ packed, const double *__restrict__ packedQ, int rpm, int M, int D,
                      const double *__restrict__ X, int64_t ldx, int64_t T, double *__restrict__ Y, int64_t ldy, double prune,
                      unsigned long long *__restrict__ nreg, const int *__restrict__ perm, const int *__restrict__ gbase,
-                     const double *__restrict__ packedQ2) {
+                     const double *__restrict__ packedQ2, const double *__restrict__ lmin) {
   using TL = Tiling<DP, false>;
   constexpr int KS = TL::KS, NT = TL::NT, NU = TL::NU, BLK = TL::BLK;
   constexpr int QS = screen_quads(DP), QFR = screen_frag_doubles(DP), STG = B16 ? screen16_stage_doubles(DP) : screen_stage_doubles(DP);
@@ -75,7 +78,7 @@ gmmmap_screen_kernel(const double *__restrict__ packed, const double *__restrict
   static_assert(!B16 || (screen16_has(DP) && STG % 128 == 0), "the bf16 screen covers up to ten k-steps");
   extern __shared__ double smem[];                              // 2 * BUF doubles
   __shared__ double etab[64];
-  __shared__ unsigned survivors[32];                            // bit m: mixture m passed the screen on some frame of the workgroup (M <= 1024)
+  __shared__ unsigned survivors[33];                            // bit m: mixture m passed the screen on some frame of the workgroup (M <= 1024); [32]: some wave has a frame outside the group's radius
   __shared__ unsigned keys[32];                                 // bit m: m is the group of some frame of the workgroup (evaluated in step 1)
   __shared__ unsigned wsurv[PAIRED ? WAVES : 1][32];            // two tiles: bit m of row w: m passed the screen on some frame of wave w
 
@@ -85,6 +88,8 @@ gmmmap_screen_kernel(const double *__restrict__ packed, const double *__restrict
   const int lcol = lane & 15, lgrp = lane >> 4;
   const int64_t frame0 = ((int64_t)blockIdx.x * WAVES + wave) * (16 * FT);
   const unsigned lds0 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char *)(reinterpret_cast<char *>(smem));
+  // the group radius (step 1b) is taken where the handle has one: stage 0 is then fetched behind the test, not here
+  const bool radius = lmin != nullptr;
 
   // block m -> a buffer, stage s -> a buffer (each wave issues every WAVES-th KB)
   auto dma_block = [&](int m, int buf) {
@@ -152,7 +157,7 @@ gmmmap_screen_kernel(const double *__restrict__ packed, const double *__restrict
     //   one batch: perm of both tiles, the table of vc_exp_tab, the gbase words of groups_in_range -- one wait;
     //   the rows of both tiles, then block mg -> buffer 0; the transposes, vmcnt(0), the barrier.
     // Positions beyond T read position T - 1 (clamped, selected afterwards: a load under an exec branch is not batched).
-    dma_stage(0, 1);
+    if (!radius) dma_stage(0, 1);
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
     for (int f = 0; f < FT; ++f) {
@@ -163,7 +168,7 @@ gmmmap_screen_kernel(const double *__restrict__ packed, const double *__restrict
     const double etv = kExp2Tab[lane];
     mg = find_groups();
     if (tid < 64) etab[tid] = etv;
-    if (tid < 32) survivors[tid] = 0u;
+    if (tid < 33) survivors[tid] = 0u;
     if (tid < 32 * WAVES) (&wsurv[0][0])[tid] = 0u;
     load_x2([&]() {
       dma_block(mg, 0);
@@ -176,9 +181,9 @@ gmmmap_screen_kernel(const double *__restrict__ packed, const double *__restrict
     const double etv = (tid < 64) ? kExp2Tab[tid] : 0.0;
     mg = find_groups();
     if (tid < 64) etab[tid] = etv;
-    if (tid < 32) survivors[tid] = 0u;
+    if (tid < 33) survivors[tid] = 0u;
     dma_block(mg, 0);
-    dma_stage(0, 1);
+    if (!radius) dma_stage(0, 1);
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
     for (int f = 0; f < FT; ++f) {
@@ -357,6 +362,7 @@ gmmmap_screen_kernel(const double *__restrict__ packed, const double *__restrict
 
   // ---- 1. the group's own mixture
   const double lc_g = packed_c[(size_t)mg * BLK + TL::LC_OFF];
+  const double lmin_g = radius ? ((const __attribute__((address_space(4))) double *)lmin)[mg] : 0.0;
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
   full_mixture(smem, lc_g, false);
@@ -373,12 +379,30 @@ gmmmap_screen_kernel(const double *__restrict__ packed, const double *__restrict
   } else {
     thr[0] = runmax[0] - prune;
   }
+  const int64_t left = T - ((int64_t)blockIdx.x * WAVES + wave_u) * (16 * FT);       // (scalar: the wave's columns that are frames)
+  const int live_cols = left < 16 * FT ? (int)left : 16 * FT;
+  // ---- 1b. the group radius.  A workgroup of ONE group g: a frame with l_g >= lmin[g] = lc_g - R_g / 2 lies inside the radius
+  // that the host certified for g (ScreenRadius, gmmmap_handle.hpp) -- every other mixture is more than prune under l_g there,
+  // which is all that steps 2 and 3 could find out.  The running maximum IS l_g (two tiles: tile 0's in the even lane groups,
+  // tile 1's in the odd ones); a NaN, or the -inf of a zero-weight group, fails the test; a column beyond T has no say.  One
+  // ballot per wave, one word in LDS, visible behind the barrier that stands in front of step 2 anyway.
+  if (radius && nkeys == 0) {
+    const int col = PAIRED ? 16 * (lgrp & 1) + lcol : lcol;
+    const bool inside = col >= live_cols || runmax[0] >= lmin_g;
+    if (__builtin_amdgcn_ballot_w64(!inside) != 0 && lane == 0) atomicOr(&survivors[32], 1u);
+  }
+  bool screen = true;                                            // (workgroup-uniform)
+  if (radius) {
+    __syncthreads();                                             // everyone is done with the block buffers; the word is complete
+    screen = nkeys != 0 || __builtin_amdgcn_readfirstlane(survivors[32]) != 0u;
+    if (screen) dma_stage(0, 1);                                 // one more L2 round trip, as the workgroups of several groups pay
+    else if (nreg && tid == 0) atomicAdd(nreg + 3, 1ull);        // workgroups that skipped the screen
+  }
+  if (screen) {                                                  // (steps 2 and 3, down to the counters: not indented)
   // a tile beyond T: no mixture passes on its account.  B16: nor on account of a COLUMN beyond T in the call's last, partly
   // filled tile -- its x is zero, no frame at all, and as far from the group's mean as from anyone's: half of the mixtures would
   // pass every look for it and be whitened by the workgroup
   if constexpr (B16) {
-    const int64_t left = T - ((int64_t)blockIdx.x * WAVES + wave_u) * (16 * FT);       // (scalar: the wave's columns that are frames)
-    const int live_cols = left < 16 * FT ? (int)left : 16 * FT;
 #pragma unroll
     for (int f = 0; f < FT; ++f)
       if (16 * f + lcol >= live_cols) thr[f] = INFINITY;
@@ -426,9 +450,9 @@ gmmmap_screen_kernel(const double *__restrict__ packed, const double *__restrict
       bt[f][3] = 0u;
     }
   }
-  __syncthreads();                                               // everyone is done with the block buffers
-  if (nkeys >= 2) {
-    dma_stage(0, 1);
+  if (!radius) __syncthreads();                                  // everyone is done with the block buffers
+  if (radius || nkeys >= 2) {
+    if (!radius) dma_stage(0, 1);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
   }
@@ -610,6 +634,7 @@ gmmmap_screen_kernel(const double *__restrict__ packed, const double *__restrict
 
   // ---- 3. the survivors in full, in index order (the bitmap is complete and visible: the loop above ended with a barrier)
   eval_bitmap(survivors, PAIRED ? wsurv[wave] : nullptr, 0, -1, B16);
+  }                                                              // (screen)
 
   if (nreg && lane == 0) {
     atomicAdd(nreg, (unsigned long long)nreg_wave);

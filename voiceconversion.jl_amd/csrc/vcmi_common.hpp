@@ -149,6 +149,7 @@ enum : unsigned {
   kDbgEstepNoHard = 134217728u,      // diagonal E-step: every frame through estep_mfma_kernel (no hard-assignment path, estep_hard.hpp)
   kDbgConvertWideTiles = 131072u, // fvconvert: two frame tiles per wave (128-frame workgroups) also for calls of a few thousand frames
   kDbgMc2eTwoWaves = 268435456u, kDbgMc2eOneWave = 536870912u,   // mc2e: two / one frames per workgroup also where four fit (the paths of fft lengths above 2400 / 4800)
+  kDbgScreenNoRadius = 1073741824u, // fvconvert shape 3: every workgroup runs the screen (no group radius test) -- the A/B partner of the certificate
   kDbgPredictNoEarlyExit = 64u   // predict / trajectory argmax: every whitening tile of every mixture (MODE 2) instead of the early exit (MODE 3)
 };
 bool debug_flag(unsigned which);

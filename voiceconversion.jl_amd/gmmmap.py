@@ -74,6 +74,14 @@ class GMMMap(FrameByFrameConverter):
         _lib.check(_lib.lib.vcmi_gmmmap_convert_plan(self._h, C.byref(n), C.byref(shape), C.byref(frac), C.byref(und)))
         return int(n.value), int(shape.value), float(frac.value), float(und.value)
 
+    def screen_radius_stats(self):
+        """(workgroups of the screened shape that skipped the screen since prune_stats(True), whether the kernel takes the
+        group-radius test for this model, the share of the model's own profile frames inside their mixture's radius)
+        -- include/vcmi.h: vcmi_gmmmap_screen_radius_stats."""
+        n, on, frac = C.c_int64(0), C.c_int(0), C.c_double(0.0)
+        _lib.check(_lib.lib.vcmi_gmmmap_screen_radius_stats(self._h, C.byref(n), C.byref(on), C.byref(frac)))
+        return int(n.value), bool(on.value), float(frac.value)
+
     def _fvconvert(self, x, out=None):
         if is_torch(x):
             import torch
