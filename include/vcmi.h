@@ -28,7 +28,7 @@
  *     vcmi_dtw_fit_batch_dev per thread), or it has finished when it returns because it ends with a status read on its
  *     stream (vcmi_estep_full_dev, vcmi_traj_convert_batch_dev, vcmi_trajgv_convert_batch_dev, vcmi_vc_traj_dev,
  *     vcmi_vc_trajgv_dev), or it touches the caller's buffers only (vcmi_gmmmap_posterior_dev, vcmi_push_delta_dev,
- *     vcmi_mc2b_dev).  The exception is vcmi_kmeans: see there.
+ *     vcmi_push_delta2_dev, vcmi_mc2b_dev).  The exception is vcmi_kmeans: see there.
  *     None of this holds for a stream that is being CAPTURED into a graph: the entries are not supported under stream
  *     capture ("State that outlives a call").
  */
@@ -458,6 +458,26 @@ int vcmi_traj_create(vcmi_gmmmap *g, int64_t T, vcmi_traj **out);
  * vcmi_traj_cond_loglik[_dev], and every convert entry of a vcmi_trajgv of vcmi_trajgv_create over t (the GV ascent over such a
  * converter: vcmi_trajgv_create_diag). */
 int vcmi_traj_create_bdiag(vcmi_bdmap *b, int64_t T, vcmi_traj **out);
+/* ... with the window count of the features.  windows = 2: vcmi_traj_create_bdiag exactly.  windows = 3: b is a model over
+ * static + delta + delta-delta features, rows [static (D); delta (D); delta-delta (D)], dim(b) = 3D (the joint model has Dj = 6D,
+ * joint row k is coupled with row k + 3D only; vcmi_gmm_em_bdiag_* trains it as it is).  W then has three rows per frame and
+ * static dimension: the static row, the delta row (-1/2 at t-1, +1/2 at t+1) and the delta-delta row (1 at t-1, -2 at t, 1 at
+ * t+1), entries outside the utterance dropped, the -2 always there -- the rows vcmi_push_delta2 makes of a static track.  The
+ * normal equations are one symmetric positive definite PENTADIAGONAL system per static dimension over all frames (the frame
+ * parities no longer decouple, and the system is not diagonally dominant), solved by L D L' without pivoting in
+ * traj_penta_solve_kernel (csrc/traj_penta.hip; statement: csrc/traj_penta_step.hpp): O(T D) work, two D T workspace arrays, no
+ * LDS.  The arg-max + g_t pass is vcmi_traj_create_bdiag's, over 3D rows (dim(b) <= 128 as for vcmi_bdmap).  dim(t) = 3D.
+ * VCMI_ERR_DIM: windows = 3 with dim(b) % 3 != 0 (the message names static + delta + delta-delta); any other window count:
+ * VCMI_ERR_ARG.  VCMI_ERR_NOT_PD and the device rule: vcmi_traj_create_bdiag's.
+ * A handle with three windows converts through vcmi_traj_convert, _batch and _batch_dev (X (3D,T)), vcmi_vc_traj,
+ * vcmi_vc_traj_postf and vcmi_vc_traj_dev with is_static = 0 (fm (3D+1,T), chunks of length(t), the power row passed through bit
+ * for bit).  Follow-ups, not provided yet -- VCMI_ERR_ARG with a message that says three windows, before any launch, the handle
+ * usable afterwards: vcmi_vc_traj_static and is_static = 1 of vcmi_vc_traj_dev; the vcmi_vc_traj_batch family;
+ * vcmi_traj_set_em_bdiag(t, n > 0); vcmi_traj_cond_loglik_bdiag[_dev]; vcmi_trajgv_create_diag over such a handle (refused when
+ * the GV handle is made).  What vcmi_traj_create_bdiag refuses, a handle with three windows refuses too. */
+int vcmi_traj_create_bdiag_windows(vcmi_bdmap *b, int64_t T, int windows, vcmi_traj **out);
+/* 2, or 3 for a handle of vcmi_traj_create_bdiag_windows(b, T, 3); -1 for NULL */
+int vcmi_traj_get_windows(const vcmi_traj *t);
 int vcmi_traj_destroy(vcmi_traj *t);
 /* length(t).  As in the reference, fvconvert rebuilds W when the sequence length differs (src/trajectory_gmmmap.jl:70-72),
  * so after vcmi_traj_convert(t, X, T, Y) the length is T, and after vcmi_vc_traj it is the length of the last chunk --
@@ -543,6 +563,14 @@ int vcmi_push_delta(const double *src, int D, int64_t T, double *out);
 /* ... and on DEVICE-RESIDENT matrices with leading dimensions (lds >= D, ldo >= 2D), asynchronous on `stream`: the input of
  * the trajectory conversion is built where the features already are (bin/vc.jl:75-78 builds it in front of vc). */
 int vcmi_push_delta_dev(const double *dsrc, int64_t lds, int D, int64_t T, double *dout, int64_t ldo, void *stream);
+/* push_delta with a delta-delta block: src (D,T) -> out (3D,T).  Rows 1 .. 2D are vcmi_push_delta's bit for bit (the first and
+ * the last frame keep the reference's static copy in the delta rows).  Rows 2D+1 .. 3D are x_{t-1} - 2 x_t + x_{t+1} with a
+ * neighbour outside the matrix dropped: a_1 = -2 x_1 + x_2, a_T = x_{T-1} - 2 x_T, T = 1 gives -2 x_1 -- the convention of W
+ * (vcmi_traj_create_bdiag_windows), so the delta-delta rows of a training matrix are exactly the delta-delta rows of W x.  Host
+ * arithmetic; the _dev form (lds >= D, ldo >= 3D) is one streaming kernel on `stream`, touches the caller's buffers only, and
+ * gives the host routine's values bit for bit. */
+int vcmi_push_delta2(const double *src, int D, int64_t T, double *out);
+int vcmi_push_delta2_dev(const double *dsrc, int64_t lds, int D, int64_t T, double *dout, int64_t ldo, void *stream);
 /* vc(c::TrajectoryConverter, fm) with the VarianceScaling post-filter (src/gv.jl:10-15) applied to the converted rows
  * 2..D+1 BEFORE the download: out[2:end,:] = fvpostf(VarianceScaling(sigma2), vc(t, fm)[2:end,:]); sigma2 (D) host vector,
  * NULL = plain vcmi_vc_traj.  One upload, one download; everything in between stays in HBM.  With sigma2 this is

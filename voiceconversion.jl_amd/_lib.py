@@ -141,6 +141,8 @@ SIGNATURES = {
     "vcmi_kmeans_mind2_dev": (_int, [_vp, _i64, _vp, _vp]),
     "vcmi_traj_create": (_int, [_vp, _i64, C.POINTER(_vp)]),
     "vcmi_traj_create_bdiag": (_int, [_vp, _i64, C.POINTER(_vp)]),
+    "vcmi_traj_create_bdiag_windows": (_int, [_vp, _i64, _int, C.POINTER(_vp)]),
+    "vcmi_traj_get_windows": (_int, [_vp]),
     "vcmi_traj_destroy": (_int, [_vp]),
     "vcmi_traj_length": (_i64, [_vp]),
     "vcmi_traj_convert": (_int, [_vp, _dp, _i64, _dp]),
@@ -159,6 +161,8 @@ SIGNATURES = {
     "vcmi_vc_traj": (_int, [_vp, _dp, _i64, _dp]),
     "vcmi_push_delta": (_int, [_dp, _int, _i64, _dp]),
     "vcmi_push_delta_dev": (_int, [_vp, _i64, _int, _i64, _vp, _i64, _vp]),
+    "vcmi_push_delta2": (_int, [_dp, _int, _i64, _dp]),
+    "vcmi_push_delta2_dev": (_int, [_vp, _i64, _int, _i64, _vp, _i64, _vp]),
     "vcmi_vc_traj_postf": (_int, [_vp, _dp, _i64, _dp, _dp]),
     "vcmi_vc_traj_static": (_int, [_vp, _dp, _i64, _dp, _dp]),
     "vcmi_vc_traj_dev": (_int, [_vp, _vp, _i64, _i64, _int, _dp, _vp, _i64, _vp]),

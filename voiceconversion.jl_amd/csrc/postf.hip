@@ -2,6 +2,7 @@
 //   src -> push_delta -> vc -> fvpostf!    (bin/vc.jl:75-82, src/datasets.jl:6-13, src/common.jl:7-63, src/gv.jl:10-15)
 // is one upload and one download (round 5 had them as separate host-pointer calls: two more PCIe round trips).
 //   vcmi_push_delta / _dev           [src; delta]: delta_t = (x_{t+1} - x_{t-1}) / 2 for 2 <= t <= T-1, the static value at t = 1, T
+//   vcmi_push_delta2 / _dev          ... with a third block, delta-delta_t = x_{t-1} - 2 x_t + x_{t+1}, absent neighbours dropped
 //   vcmi_variance_scaling / _dev     per row sqrt(sigma2 / var) (x - mean) + mean, Julia's corrected variance, in place allowed
 //   vcmi_vc_frames_postf             vc(g::GMMMap, fm) with fvpostf! applied to the converted rows before the download
 //   vc_traj_pre_device / vc_traj_post_device   the two ends of vc(c::TrajectoryConverter, fm) around the chunk conversions
@@ -15,6 +16,16 @@
 #include "hostpipe.hpp"
 
 namespace vcmi {
+
+// the delta-delta value of a frame, one expression for the kernel and the host routine: neighbours that exist only (lo: t-1,
+// hi: t+1), left to right, no contraction -- the two agree bit for bit
+__host__ __device__ static inline double push_delta2_value(bool lo, bool hi, double xm, double x, double xp) {
+#pragma clang fp contract(off)
+  double a = -2.0 * x;
+  if (lo) a = xm + a;
+  if (hi) a = a + xp;
+  return a;
+}
 
 // ---- push_delta, src/datasets.jl:6-13 ------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(256)
@@ -35,6 +46,34 @@ int push_delta_device(const double *dsrc, int64_t lds, int D, int64_t T, double 
   const int64_t n = (int64_t)D * T;
   const unsigned grid = (unsigned)std::min<int64_t>((n + 255) / 256, 8192);
   hipLaunchKernelGGL(push_delta_kernel, dim3(grid), dim3(256), 0, st, dsrc, lds, D, T, dout, ldo);
+  VCMI_HIP(hipGetLastError());
+  return VCMI_OK;
+}
+
+// ---- push_delta with a delta-delta block: out (3D,T) = [src; delta; delta-delta].  Rows 0 .. 2D-1 are push_delta_kernel's, by the
+// same expressions; rows 2D .. 3D-1 are x_{t-1} - 2 x_t + x_{t+1} with a neighbour outside the matrix DROPPED (the convention of
+// the trajectory solver's W, traj_penta_step.hpp: a_1 = -2 x_1 + x_2, a_T = x_{T-1} - 2 x_T, T = 1: -2 x_1), summed left to right.
+__global__ void __launch_bounds__(256)
+push_delta2_kernel(const double *__restrict__ src, int64_t lds, int D, int64_t T, double *__restrict__ out, int64_t ldo) {
+#pragma clang fp contract(off)
+  const int64_t n = (int64_t)D * T;
+  for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < n; e += (int64_t)gridDim.x * 256) {
+    const int64_t t = e / D;
+    const int d = (int)(e - t * D);
+    const double x = src[t * lds + d];
+    const bool lo = t >= 1, hi = t + 1 < T;
+    const double xm = lo ? src[(t - 1) * lds + d] : 0.0, xp = hi ? src[(t + 1) * lds + d] : 0.0;
+    out[t * ldo + d] = x;
+    out[t * ldo + D + d] = (lo && hi) ? -0.5 * xm + 0.5 * xp : x;
+    out[t * ldo + 2 * D + d] = push_delta2_value(lo, hi, xm, x, xp);
+  }
+}
+
+int push_delta2_device(const double *dsrc, int64_t lds, int D, int64_t T, double *dout, int64_t ldo, hipStream_t st) {
+  if (T == 0) return VCMI_OK;
+  const int64_t n = (int64_t)D * T;
+  const unsigned grid = (unsigned)std::min<int64_t>((n + 255) / 256, 8192);
+  hipLaunchKernelGGL(push_delta2_kernel, dim3(grid), dim3(256), 0, st, dsrc, lds, D, T, dout, ldo);
   VCMI_HIP(hipGetLastError());
   return VCMI_OK;
 }
@@ -140,12 +179,12 @@ int variance_scaling_device(const double *dsrc, int64_t lds, int D, int64_t T, c
 // into `out` (skipped when out is NULL: the caller assembles the result in place in fm, the row is already there).
 //   STATIC: rows = D+1; x = [fm[2:end,:]; delta], the delta over the WHOLE matrix with push_delta_kernel's arithmetic (the
 //           first and the last frame of the matrix -- not of a chunk -- keep the copy), bin/vc.jl:77-78, src/datasets.jl:6-13
-//   else:   rows = 2D+1; x = fm[2:end,:]
+//   else:   rows = D2+1, D2 = dim(t) (2D; 3D for a converter with three windows); x = fm[2:end,:] (D2,T)
 template <bool STATIC>
 __global__ void __launch_bounds__(256)
-vc_traj_pre_kernel(const double *__restrict__ fm, int64_t ldf, int D, int64_t T, double *__restrict__ x, double *__restrict__ out,
+vc_traj_pre_kernel(const double *__restrict__ fm, int64_t ldf, int D, int D2, int64_t T, double *__restrict__ x, double *__restrict__ out,
                    int64_t ldo) {
-  const int R = STATIC ? D : 2 * D;                                  // feature rows read per frame
+  const int R = STATIC ? D : D2;                                     // feature rows read per frame
   const int64_t n = (int64_t)R * T;
   for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < n; e += (int64_t)gridDim.x * 256) {
     const int64_t t = e / R;
@@ -162,13 +201,13 @@ vc_traj_pre_kernel(const double *__restrict__ fm, int64_t ldf, int D, int64_t T,
   }
 }
 
-int vc_traj_pre_device(const double *dfm, int64_t ldf, int D, int64_t T, bool is_static, double *dx, double *dout, int64_t ldo,
+int vc_traj_pre_device(const double *dfm, int64_t ldf, int D, int D2, int64_t T, bool is_static, double *dx, double *dout, int64_t ldo,
                        hipStream_t st) {
   if (T == 0) return VCMI_OK;
-  const int64_t n = (int64_t)(is_static ? D : 2 * D) * T;
+  const int64_t n = (int64_t)(is_static ? D : D2) * T;
   const dim3 grid((unsigned)std::min<int64_t>((n + 255) / 256, 8192));
-  if (is_static) hipLaunchKernelGGL(vc_traj_pre_kernel<true>, grid, dim3(256), 0, st, dfm, ldf, D, T, dx, dout, ldo);
-  else hipLaunchKernelGGL(vc_traj_pre_kernel<false>, grid, dim3(256), 0, st, dfm, ldf, D, T, dx, dout, ldo);
+  if (is_static) hipLaunchKernelGGL(vc_traj_pre_kernel<true>, grid, dim3(256), 0, st, dfm, ldf, D, D2, T, dx, dout, ldo);
+  else hipLaunchKernelGGL(vc_traj_pre_kernel<false>, grid, dim3(256), 0, st, dfm, ldf, D, D2, T, dx, dout, ldo);
   VCMI_HIP(hipGetLastError());
   return VCMI_OK;
 }
@@ -203,17 +242,43 @@ extern "C" int vcmi_push_delta_dev(const double *dsrc, int64_t lds, int D, int64
 // push_delta(src (D,T)) -> out (2D,T) on HOST matrices: host arithmetic -- three streaming passes over memory the caller already
 // holds cost less than moving the matrix over PCIe and back (and the helper works without a device); the device-resident
 // form above is the one the vc pipeline uses
-extern "C" int vcmi_push_delta(const double *src, int D, int64_t T, double *out) {
-  if (!src || !out || D < 1 || T < 0) return fail(VCMI_ERR_ARG, "vcmi_push_delta: bad argument");
+// (ldo: the rows of out, 2D here and 3D under vcmi_push_delta2)
+static void push_delta_host(const double *src, int D, int64_t T, double *out, size_t ldo) {
   for (int64_t t = 0; t < T; ++t)
     for (int d = 0; d < D; ++d) {   // repmat(src, 2), src/datasets.jl:8
-      out[d + (size_t)2 * D * t] = src[d + (size_t)D * t];
-      out[D + d + (size_t)2 * D * t] = src[d + (size_t)D * t];
+      out[d + ldo * t] = src[d + (size_t)D * t];
+      out[D + d + ldo * t] = src[d + (size_t)D * t];
     }
   for (int64_t t = 1; t + 1 < T; ++t)   // t = 2:T-1, src/datasets.jl:9-11
     for (int d = 0; d < D; ++d)
-      out[D + d + (size_t)2 * D * t] = -0.5 * src[d + (size_t)D * (t - 1)] + 0.5 * src[d + (size_t)D * (t + 1)];
+      out[D + d + ldo * t] = -0.5 * src[d + (size_t)D * (t - 1)] + 0.5 * src[d + (size_t)D * (t + 1)];
+}
+
+extern "C" int vcmi_push_delta(const double *src, int D, int64_t T, double *out) {
+  if (!src || !out || D < 1 || T < 0) return fail(VCMI_ERR_ARG, "vcmi_push_delta: bad argument");
+  push_delta_host(src, D, T, out, (size_t)2 * D);
   return VCMI_OK;
+}
+
+// push_delta(src (D,T), order = 2) -> out (3D,T): rows 0 .. 2D-1 as vcmi_push_delta makes them, rows 2D .. 3D-1 the delta-delta
+// rows of push_delta2_kernel.  Host arithmetic, like vcmi_push_delta.
+extern "C" int vcmi_push_delta2(const double *src, int D, int64_t T, double *out) {
+  if (!src || !out || D < 1 || T < 0) return fail(VCMI_ERR_ARG, "vcmi_push_delta2: bad argument");
+  push_delta_host(src, D, T, out, (size_t)3 * D);
+  for (int64_t t = 0; t < T; ++t)
+    for (int d = 0; d < D; ++d) {
+      const bool lo = t >= 1, hi = t + 1 < T;
+      out[2 * D + d + (size_t)3 * D * t] = push_delta2_value(lo, hi, lo ? src[d + (size_t)D * (t - 1)] : 0.0, src[d + (size_t)D * t],
+                                                             hi ? src[d + (size_t)D * (t + 1)] : 0.0);
+    }
+  return VCMI_OK;
+}
+
+extern "C" int vcmi_push_delta2_dev(const double *dsrc, int64_t lds, int D, int64_t T, double *dout, int64_t ldo, void *stream) {
+  if (D < 1 || T < 0 || lds < D || ldo < 3 * (int64_t)D) return fail(VCMI_ERR_ARG, "vcmi_push_delta2_dev: bad argument");
+  if (T > 0 && (!dsrc || !dout)) return fail(VCMI_ERR_ARG, "vcmi_push_delta2_dev: NULL argument");
+  VCMI_TRY(check_device());
+  return push_delta2_device(dsrc, lds, D, T, dout, ldo, as_stream(stream));
 }
 
 extern "C" int vcmi_variance_scaling_dev(const double *dsrc, int64_t lds, int D, int64_t T, const double *sigma2, double *dout,

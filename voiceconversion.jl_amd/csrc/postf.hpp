@@ -9,6 +9,8 @@
 namespace vcmi {
 // out (2D,T) with leading dimension ldo  <-  [src; delta(src)], src (D,T) with leading dimension lds; asynchronous on st
 int push_delta_device(const double *dsrc, int64_t lds, int D, int64_t T, double *dout, int64_t ldo, hipStream_t st);
+// out (3D,T)  <-  [src; delta(src); delta-delta(src)]: the first 2D rows as above, then x_{t-1} - 2 x_t + x_{t+1} with absent neighbours dropped
+int push_delta2_device(const double *dsrc, int64_t lds, int D, int64_t T, double *dout, int64_t ldo, hipStream_t st);
 // fvpostf!: out[d,t] = sqrt(sigma2[d] / var_d) (src[d,t] - mean_d) + mean_d, mean / corrected variance per row over the T
 // frames; sigma2 is a HOST vector (D).  dout may be dsrc (in place).  Asynchronous on st; deterministic (fixed-order sums).
 int variance_scaling_device(const double *dsrc, int64_t lds, int D, int64_t T, const double *sigma2_host, double *dout,
@@ -23,10 +25,11 @@ int variance_scaling_stats_device(const double *dsrc, int64_t lds, int D, int64_
 int variance_scaling_stats_leave(hipStream_t st);
 
 // The two ends of vc(c::TrajectoryConverter, fm) around the chunk conversions, one streaming pass each.
-// pre:  dfm (D+1,T) static features (is_static) or (2D+1,T) -> dx (2D,T) dense, the converter's input.  Static input:
+// pre:  dfm (D+1,T) static features (is_static) or (D2+1,T) -> dx (D2,T) dense, the converter's input; D2 = dim(t): 2D, or 3D
+//       for a converter with three windows (never with is_static).  Static input:
 //       dx = [fm[2:end,:]; delta] with the delta of push_delta over ALL T frames (bin/vc.jl:77-78).  The power row goes to
 //       row 1 of dout (leading dimension ldo) unless dout is NULL (the caller assembles in place in dfm: the row is there).
-int vc_traj_pre_device(const double *dfm, int64_t ldf, int D, int64_t T, bool is_static, double *dx, double *dout, int64_t ldo,
+int vc_traj_pre_device(const double *dfm, int64_t ldf, int D, int D2, int64_t T, bool is_static, double *dx, double *dout, int64_t ldo,
                        hipStream_t st);
 // post: dy (D,T) dense -> rows 2..D+1 of dout; with dstat (variance_scaling_stats_device) the rows are scaled on the way.
 int vc_traj_post_device(const double *dy, int D, int64_t T, const double *dstat, double *dout, int64_t ldo, hipStream_t st);

@@ -249,6 +249,7 @@ int traj_run(vcmi_traj *t, std::vector<TrajUtt> &utts, int64_t nframes, bool con
   VCMI_TRY(traj_solve_plan(t, utts, nframes, Tmax, gv != nullptr, &plan));
   t->em_run_iters = 0;
   if (diag) {     // (EM: over a cross-diagonal handle only, vcmi_traj_set_em_bdiag; GV: a handle of vcmi_trajgv_create_diag)
+    if (t->windows == 3) return traj_penta_launch(t, plan, t->dg_q.p, t->mhat.p, st);     // (no EM, no GV over such a handle)
     VCMI_TRY(traj_diag_launch(t, plan, t->dg_q.p, t->mhat.p, st));
     if (t->b && t->em_iters > 0) VCMI_TRY(traj_em_bdiag_run(t, utts, plan, st));
     if (gv && gv->epochs >= 0) VCMI_TRY(traj_gvd_launch(t, plan, *gv, st));
@@ -259,6 +260,12 @@ int traj_run(vcmi_traj *t, std::vector<TrajUtt> &utts, int64_t nframes, bool con
   // (3) global-variance ascent on the solved trajectories, in place
   if (gv && gv->epochs >= 0) VCMI_TRY(traj_gv_launch(t, plan, *gv, st));
   return VCMI_OK;
+}
+
+int traj_two_windows_only(const vcmi_traj *t, const char *who, const char *what) {
+  if (t->windows != 3) return VCMI_OK;
+  return fail(VCMI_ERR_ARG, "%s: the converter has three windows (static + delta + delta-delta, vcmi_traj_create_bdiag_windows): %s "
+                            "is provided for two windows only", who, what);
 }
 
 int traj_check_status(vcmi_traj *t, hipStream_t st) {
@@ -455,31 +462,47 @@ extern "C" int vcmi_traj_create(vcmi_gmmmap *g, int64_t T, vcmi_traj **out) {
 
 // TrajectoryGMMMap straight from a cross-diagonal model: the conditional covariance of every mixture is
 // diagonal exactly, so the converter IS a diagonal-precision one -- q from the pairs (gmmmap_bdiag_prepare.cpp), nothing dense.
-extern "C" int vcmi_traj_create_bdiag(vcmi_bdmap *b, int64_t T, vcmi_traj **out) {
-  if (!b || !out) return fail(VCMI_ERR_ARG, "vcmi_traj_create_bdiag: NULL argument");
+static int traj_create_bdiag(vcmi_bdmap *b, int64_t T, int windows, vcmi_traj **out, const char *who) {
+  if (!b || !out) return fail(VCMI_ERR_ARG, "%s: NULL argument", who);
   *out = nullptr;
-  if (b->D & 1) return fail(VCMI_ERR_DIM, "TrajectoryGMMMap: dim(g) = %d must be even (static + delta)", b->D);
+  if (windows != 2 && windows != 3) return fail(VCMI_ERR_ARG, "%s: %d windows: 2 (static + delta) or 3 (static + delta + delta-delta)", who, windows);
+  if (windows == 2 && (b->D & 1)) return fail(VCMI_ERR_DIM, "TrajectoryGMMMap: dim(g) = %d must be even (static + delta)", b->D);
+  if (windows == 3 && b->D % 3 != 0)
+    return fail(VCMI_ERR_DIM, "TrajectoryGMMMap: dim(g) = %d must be a multiple of 3 (static + delta + delta-delta)", b->D);
   if (T < 0) return fail(VCMI_ERR_ARG, "TrajectoryGMMMap: negative length");
   if (b->q_bad >= 0)
-    return fail(VCMI_ERR_NOT_PD, "vcmi_traj_create_bdiag: the conditional variance of pair (%d,%d) is not positive and finite",
+    return fail(VCMI_ERR_NOT_PD, "%s: the conditional variance of pair (%d,%d) is not positive and finite", who,
                 (int)(b->q_bad % b->D) + 1, (int)(b->q_bad / b->D) + 1);
   int dev = 0;
   VCMI_HIP(hipGetDevice(&dev));
   if (dev != b->device)
-    return fail(VCMI_ERR_ARG, "vcmi_traj_create_bdiag: the handle was created on device %d, the call runs on device %d", b->device, dev);
+    return fail(VCMI_ERR_ARG, "%s: the handle was created on device %d, the call runs on device %d", who, b->device, dev);
   std::unique_ptr<vcmi_traj> t(new (std::nothrow) vcmi_traj());
   if (!t) return fail(VCMI_ERR_OOM, "out of host memory");
   t->b = b;
   t->D2 = b->D;
-  t->D = b->D / 2;
+  t->windows = windows;
+  t->D = b->D / windows;
   t->M = b->M;
   t->length = T;
   t->precision = VCMI_TRAJ_PRECISION_DIAG;
-  VCMI_TRY(upload_now(t->dg_q, b->h_q));       // [M][2D]: (D,M) dimension fastest is that layout
+  VCMI_TRY(upload_now(t->dg_q, b->h_q));       // [M][dim(b)]: (dim(b),M) dimension fastest is that layout
   t->diag_ready = true;
   *out = t.release();
   return VCMI_OK;
 }
+
+extern "C" int vcmi_traj_create_bdiag(vcmi_bdmap *b, int64_t T, vcmi_traj **out) {
+  return traj_create_bdiag(b, T, 2, out, "vcmi_traj_create_bdiag");
+}
+
+// ... over static + delta (windows = 2: vcmi_traj_create_bdiag exactly) or static + delta + delta-delta features (windows = 3,
+// dim(b) = 3D, the pentadiagonal solver of traj_penta.hip)
+extern "C" int vcmi_traj_create_bdiag_windows(vcmi_bdmap *b, int64_t T, int windows, vcmi_traj **out) {
+  if (windows == 2) return vcmi_traj_create_bdiag(b, T, out);
+  return traj_create_bdiag(b, T, windows, out, "vcmi_traj_create_bdiag_windows");
+}
+extern "C" int vcmi_traj_get_windows(const vcmi_traj *t) { return t ? t->windows : -1; }
 
 extern "C" int vcmi_traj_destroy(vcmi_traj *t) {
   delete t;

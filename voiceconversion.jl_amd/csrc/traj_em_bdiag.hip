@@ -318,6 +318,7 @@ using namespace vcmi;
 extern "C" int vcmi_traj_set_em_bdiag(vcmi_traj *t, int iters) {
   VCMI_TRY(em_bd_handle_check(t, "vcmi_traj_set_em_bdiag"));
   if (iters < 0) return fail(VCMI_ERR_ARG, "vcmi_traj_set_em_bdiag: negative iteration count");
+  if (iters > 0) VCMI_TRY(traj_two_windows_only(t, "vcmi_traj_set_em_bdiag", "EM re-estimation"));     // (the E-step's W is the two-window stencil)
   if (iters > 0) VCMI_TRY(em_bd_ensure(t));
   t->em_iters = iters;
   return VCMI_OK;
@@ -325,6 +326,7 @@ extern "C" int vcmi_traj_set_em_bdiag(vcmi_traj *t, int iters) {
 
 extern "C" int vcmi_traj_cond_loglik_bdiag_dev(vcmi_traj *t, const double *dX, const double *dY, int64_t T, double *dL, void *stream) {
   VCMI_TRY(em_bd_handle_check(t, "vcmi_traj_cond_loglik_bdiag_dev"));
+  VCMI_TRY(traj_two_windows_only(t, "vcmi_traj_cond_loglik_bdiag_dev", "L(y)"));
   if (!dL) return fail(VCMI_ERR_ARG, "vcmi_traj_cond_loglik_bdiag_dev: NULL argument");
   if (T < 0 || T > INT32_MAX || (T > 0 && (!dX || !dY))) return fail(VCMI_ERR_ARG, "vcmi_traj_cond_loglik_bdiag_dev: bad argument");
   hipStream_t st = as_stream(stream);
@@ -344,6 +346,7 @@ extern "C" int vcmi_traj_cond_loglik_bdiag_dev(vcmi_traj *t, const double *dX, c
 
 extern "C" int vcmi_traj_cond_loglik_bdiag(vcmi_traj *t, const double *X, const double *Y, int64_t T, double *L) {
   VCMI_TRY(em_bd_handle_check(t, "vcmi_traj_cond_loglik_bdiag"));
+  VCMI_TRY(traj_two_windows_only(t, "vcmi_traj_cond_loglik_bdiag", "L(y)"));
   if (!L) return fail(VCMI_ERR_ARG, "vcmi_traj_cond_loglik_bdiag: NULL argument");
   if (T < 0 || T > INT32_MAX || (T > 0 && (!X || !Y))) return fail(VCMI_ERR_ARG, "vcmi_traj_cond_loglik_bdiag: bad argument");
   *L = 0.0;
@@ -365,6 +368,7 @@ extern "C" int vcmi_traj_cond_loglik_bdiag(vcmi_traj *t, const double *X, const 
 extern "C" int vcmi_debug_traj_em_bdiag_estep(vcmi_traj *t, const double *X, const double *Y, int64_t T, double *lse, double *qbar,
                                               double *gbar) {
   VCMI_TRY(em_bd_handle_check(t, "vcmi_debug_traj_em_bdiag_estep"));
+  VCMI_TRY(traj_two_windows_only(t, "vcmi_debug_traj_em_bdiag_estep", "the E-step"));
   if (T < 0 || T > INT32_MAX - 1 || (T > 0 && (!X || !Y || !lse || !qbar || !gbar)))
     return fail(VCMI_ERR_ARG, "vcmi_debug_traj_em_bdiag_estep: bad argument");
   if (T == 0) return VCMI_OK;

@@ -791,6 +791,7 @@ static int trajgv_create(vcmi_traj *t, const double *muv, const double *sigmavv,
   const char *who = diag ? "vcmi_trajgv_create_diag" : "vcmi_trajgv_create";
   if (!t || !muv || !sigmavv || !out) return fail(VCMI_ERR_ARG, "%s: NULL argument", who);
   *out = nullptr;
+  if (diag) VCMI_TRY(traj_two_windows_only(t, who, "the GV ascent"));     // (traj_gvd_kernel's gradient is the two-window stencil)
   if (diag && t->precision != VCMI_TRAJ_PRECISION_DIAG)
     return fail(VCMI_ERR_ARG, "vcmi_trajgv_create_diag: the trajectory converter has full conditional precisions "
                               "(vcmi_traj_set_precision): vcmi_trajgv_create makes the handle for it");

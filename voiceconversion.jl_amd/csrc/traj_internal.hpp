@@ -19,7 +19,9 @@ struct vcmi_traj {
   // good, dg_q holds b's q, the arg-max and g_t of a call are one pass of b's kernel (bdmap_traj_device), and every dense
   // buffer below (AT .. Afrag, Qpad, cm, dg_QT, dg_Qfrag) stays empty.  No replicas: b converts on its own device.
   vcmi_bdmap *b = nullptr;
-  int D2 = 0;          // dim(t) = 2D (static + delta), src/trajectory_gmmmap.jl:35
+  int D2 = 0;          // dim(t) = 2D (static + delta), src/trajectory_gmmmap.jl:35; 3D for a handle with three windows
+  int windows = 2;     // 3: static + delta + delta-delta (vcmi_traj_create_bdiag_windows; a cross-diagonal handle only): the
+                       // pentadiagonal solver of traj_penta.hip in place of traj_diag.hip's
   int D = 0;           // static dimension
   int M = 0;
   int64_t length = 0;  // length(t), src/trajectory_gmmmap.jl:34
@@ -128,7 +130,7 @@ bool traj_solve_is_big(int D);
 // path), gpad / ypad / gwin where the solver needs them, and uploads the padded descriptors (synchronous).  A reserve that
 // grows a buffer frees the old one, which waits for the device.  A handle in diagonal mode gets n, Tmax, nframes, du, cus, grid and a
 // workspace of gvd_ws_doubles (traj_gvd_plan.hpp: nframes * D doubles, five times that with_gv), its size in ws_stride: no
-// padded copies, no window, no occupancy query.
+// padded copies, no window, no occupancy query.  A handle with three windows gets penta_ws_doubles instead (traj_penta_plan.hpp).
 int traj_solve_plan(vcmi_traj *t, const std::vector<TrajUtt> &utts, int64_t nframes, int Tmax, bool with_gv, TrajSolvePlan *plan);
 // Solve of the (sorted) utterances [b0, b0 + nb) with the precision table Qs (indexed by mh[t] - 1: t->Q / t->Qpad with t->mhat,
 // or the EM loop's table; in plan.Ds) and the right-hand sides in t->gbuf: gbuf -> gpad where padded, the solver the plan chose,
@@ -144,6 +146,14 @@ int traj_diag_ensure(vcmi_traj *t);
 // EM loop's per-frame table with its identity index); workspace t->ws, nframes * D doubles indexed by frame0 (a plan made in
 // diagonal mode).  Asynchronous on st; never writes t->status.
 int traj_diag_launch(vcmi_traj *t, const TrajSolvePlan &plan, const double *q, const int64_t *mh, hipStream_t st);
+
+// ---- traj_penta.hip ----
+// The same solve for a handle with three windows (t->windows == 3): right-hand sides t->gbuf [frame][3D], the precision table q
+// [.][3D] with its 1-based index as above; workspace t->ws, the two (nframes,D) arrays of traj_penta_plan.hpp (a plan made for
+// such a handle).  Asynchronous on st; never writes t->status.
+int traj_penta_launch(vcmi_traj *t, const TrajSolvePlan &plan, const double *q, const int64_t *mh, hipStream_t st);
+// VCMI_ERR_ARG for a handle with three windows at an entry that has no three-window form (`what` names it in the message)
+int traj_two_windows_only(const vcmi_traj *t, const char *who, const char *what);
 
 // ---- traj_gv.hip ----
 // The GV ascent on the solved trajectories of the plan's utterances, in place (two-team kernel where the frame permutation of

@@ -25,12 +25,13 @@ static int vc_traj_args(const vcmi_traj *t, const vcmi_trajgv *gvh, int epochs, 
   return VCMI_OK;
 }
 
-// The one routine behind the five entries.  dfm (D+1,T) static or (2D+1,T); dout (D+1,T); gvh != NULL: every chunk through
+// The one routine behind the five entries.  dfm (D+1,T) static or (dim(t)+1,T), dim(t) = 2D (3D with three windows); dout (D+1,T); gvh != NULL: every chunk through
 // fvconvert(tgv, X; epochs, alpha).  dout == dfm (static input only) assembles the result in place: the power row never
 // moves, rows 2..D+1 are overwritten after the pre kernel has read them.  Every argument is checked before the first launch.
 static int vc_traj_device(vcmi_traj *t, vcmi_trajgv *gvh, int epochs, double alpha, const double *dfm, int64_t ldf, int64_t T,
                           bool is_static, const double *sigma2, double *dout, int64_t ldo, hipStream_t st, const char *who) {
   if (T < 0 || (T > 0 && (!dfm || !dout))) return fail(VCMI_ERR_ARG, "%s: bad argument", who);
+  if (is_static) VCMI_TRY(traj_two_windows_only(t, who, "static input (the deltas taken by the library)"));
   if (T == 0) return VCMI_OK;
   const int D = t->D, D2 = t->D2, rows = (is_static ? D : D2) + 1;
   if (ldf < rows || ldo < D + 1) return fail(VCMI_ERR_ARG, "%s: leading dimension below the row count", who);
@@ -46,8 +47,8 @@ static int vc_traj_device(vcmi_traj *t, vcmi_trajgv *gvh, int epochs, double alp
   VCMI_TRY(sc.x.reserve((size_t)D2 * T));
   VCMI_TRY(sc.y.reserve((size_t)D * T));
   VCMI_TRY(sc.order.enter(st));
-  // X = [fm[1,:]; push_delta(fm[2:end,:])] over the whole matrix (bin/vc.jl:77-78), or rows 2..2D+1 as they are
-  VCMI_TRY(vc_traj_pre_device(dfm, ldf, D, T, is_static, sc.x.p, dout == dfm ? nullptr : dout, ldo, st));
+  // X = [fm[1,:]; push_delta(fm[2:end,:])] over the whole matrix (bin/vc.jl:77-78), or rows 2..dim(t)+1 as they are
+  VCMI_TRY(vc_traj_pre_device(dfm, ldf, D, D2, T, is_static, sc.x.p, dout == dfm ? nullptr : dout, ldo, st));
   for (int64_t k = 0; k < nch; ++k)
     utts[(size_t)k] = TrajUtt{sc.x.p + (size_t)k * L * D2, sc.y.p + (size_t)k * L * D, k * L, (int32_t)Ts[(size_t)k], (int32_t)k};
   VCMI_TRY(traj_run(t, utts, T, true, sc.x.p, st, gvh ? &gv : nullptr));
@@ -66,6 +67,7 @@ static int vc_traj_device(vcmi_traj *t, vcmi_trajgv *gvh, int epochs, double alp
 static int vc_traj_host(vcmi_traj *t, vcmi_trajgv *gvh, int epochs, double alpha, const double *fm, int64_t T, bool is_static,
                         const double *sigma2, double *out, const char *who) {
   if (T < 0 || (T > 0 && (!fm || !out))) return fail(VCMI_ERR_ARG, "%s: bad argument", who);
+  if (is_static) VCMI_TRY(traj_two_windows_only(t, who, "static input (the deltas taken by the library)"));
   if (T == 0) return VCMI_OK;
   {   // nothing is uploaded for a call that cannot run
     std::vector<int64_t> Ts;

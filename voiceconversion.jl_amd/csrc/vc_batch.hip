@@ -198,6 +198,7 @@ static int vcb_filter_and_post(const VcBatchPlan &p, const VcbLists &l, const do
 static int vcb_traj_check(const vcmi_traj *t, const vcmi_trajgv *gvh, int epochs, int64_t n, const int64_t *T, bool is_static,
                           const double *sigma2, const int64_t *in_off, const int64_t *out_off, VcBatchPlan *plan, TrajGV *gv,
                           const char *who) {
+  VCMI_TRY(traj_two_windows_only(t, who, "vc over a batch of utterances"));     // (vcb_pre_kernel reads 2D feature rows)
   const int D = t->D;
   if (sigma2 && (D < 1 || D > 256)) return fail(VCMI_ERR_DIM, "%s: variance scaling needs 1 <= D <= 256", who);
   *plan = vc_batch_plan(n, T, true, t->length, (is_static ? D : t->D2) + 1, D + 1, sigma2 != nullptr, gvh != nullptr, in_off,

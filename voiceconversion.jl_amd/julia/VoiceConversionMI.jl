@@ -440,10 +440,17 @@ function vc(t::TrajectoryGMMMap, fm::Matrix{Float64})
     out
 end
 
-function push_delta(src::Matrix{Float64})                              # src/datasets.jl:6-13
-    out = Matrix{Float64}(undef, 2size(src, 1), size(src, 2))
-    check(ccall((:vcmi_push_delta, libvcmi), Cint, (Ptr{Float64}, Cint, Int64, Ptr{Float64}),
-                src, size(src, 1), size(src, 2), out))
+# order=2: a third block of rows, the delta-delta x_{t-1} - 2x_t + x_{t+1} with absent neighbours dropped (vcmi_push_delta2)
+function push_delta(src::Matrix{Float64}; order::Int=1)                # src/datasets.jl:6-13
+    order in (1, 2) || throw(ArgumentError("push_delta: order must be 1 or 2"))
+    out = Matrix{Float64}(undef, (order + 1) * size(src, 1), size(src, 2))
+    if order == 1
+        check(ccall((:vcmi_push_delta, libvcmi), Cint, (Ptr{Float64}, Cint, Int64, Ptr{Float64}),
+                    src, size(src, 1), size(src, 2), out))
+    else
+        check(ccall((:vcmi_push_delta2, libvcmi), Cint, (Ptr{Float64}, Cint, Int64, Ptr{Float64}),
+                    src, size(src, 1), size(src, 2), out))
+    end
     out
 end
 
@@ -791,10 +798,16 @@ struct DeviceMatrix
     cols::Int
     ld::Int
 end
-function push_delta(src::DeviceMatrix, out::DeviceMatrix; stream::Ptr{Cvoid}=C_NULL)      # src/datasets.jl:6-13
-    (out.rows == 2src.rows && out.cols == src.cols) || throw(DimensionMismatch("out must be (2D,T)"))
-    check(ccall((:vcmi_push_delta_dev, libvcmi), Cint, (Ptr{Float64}, Int64, Cint, Int64, Ptr{Float64}, Int64, Ptr{Cvoid}),
-                src.ptr, src.ld, src.rows, src.cols, out.ptr, out.ld, stream))
+function push_delta(src::DeviceMatrix, out::DeviceMatrix; order::Int=1, stream::Ptr{Cvoid}=C_NULL)      # src/datasets.jl:6-13
+    order in (1, 2) || throw(ArgumentError("push_delta: order must be 1 or 2"))
+    (out.rows == (order + 1) * src.rows && out.cols == src.cols) || throw(DimensionMismatch("out must be (2D,T), (3D,T) with order=2"))
+    if order == 1
+        check(ccall((:vcmi_push_delta_dev, libvcmi), Cint, (Ptr{Float64}, Int64, Cint, Int64, Ptr{Float64}, Int64, Ptr{Cvoid}),
+                    src.ptr, src.ld, src.rows, src.cols, out.ptr, out.ld, stream))
+    else
+        check(ccall((:vcmi_push_delta2_dev, libvcmi), Cint, (Ptr{Float64}, Int64, Cint, Int64, Ptr{Float64}, Int64, Ptr{Cvoid}),
+                    src.ptr, src.ld, src.rows, src.cols, out.ptr, out.ld, stream))
+    end
     out
 end
 # vc of a trajectory converter on a matrix in HBM: fm (D+1,T) static (delta=true) or (2D+1,T) -> out (D+1,T), out must not
@@ -841,9 +854,13 @@ end
 mutable struct TrajectoryGMMMapBlockDiag <: TrajectoryConverter
     gmmmap::GMMMapBlockDiag
     h::Ptr{Cvoid}
-    function TrajectoryGMMMapBlockDiag(g::GMMMapBlockDiag, T::Int)
+    function TrajectoryGMMMapBlockDiag(g::GMMMapBlockDiag, T::Int; windows::Int=2)
         h = Ref{Ptr{Cvoid}}(C_NULL)
-        check(ccall((:vcmi_traj_create_bdiag, libvcmi), Cint, (Ptr{Cvoid}, Int64, Ref{Ptr{Cvoid}}), g.h, T, h))
+        if windows == 2
+            check(ccall((:vcmi_traj_create_bdiag, libvcmi), Cint, (Ptr{Cvoid}, Int64, Ref{Ptr{Cvoid}}), g.h, T, h))
+        else    # 3: g over static + delta + delta-delta features (dim(g) = 3D): the pentadiagonal solver, csrc/traj_penta.hip
+            check(ccall((:vcmi_traj_create_bdiag_windows, libvcmi), Cint, (Ptr{Cvoid}, Int64, Cint, Ref{Ptr{Cvoid}}), g.h, T, windows, h))
+        end
         t = new(g, h[])
         finalizer(x -> ccall((:vcmi_traj_destroy, libvcmi), Cint, (Ptr{Cvoid},), x.h), t)
         t
@@ -870,7 +887,7 @@ function em_iters!(t::TrajectoryGMMMapBlockDiag, n::Integer)
     t
 end
 function cond_loglik(t::TrajectoryGMMMapBlockDiag, X::Matrix{Float64}, Y::Matrix{Float64})
-    (size(X, 1) == dim(t) && 2 * size(Y, 1) == size(X, 1) && size(X, 2) == size(Y, 2)) || throw(DimensionMismatch("Inconsistent dimentions."))
+    (size(X, 1) == dim(t) && size(Y, 1) == static_dim(t) && size(X, 2) == size(Y, 2)) || throw(DimensionMismatch("Inconsistent dimentions."))
     L = Ref{Float64}(0.0)
     check(ccall((:vcmi_traj_cond_loglik_bdiag, libvcmi), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Int64, Ref{Float64}),
                 t.h, X, Y, size(X, 2), L))
@@ -887,11 +904,15 @@ traj_precision(t::TrajectoryGMMMapBlockDiag) = TRAJ_PRECISIONS[Int(ccall((:vcmi_
 em_iters(t::TrajectoryGMMMapBlockDiag) = Int(ccall((:vcmi_traj_get_em, libvcmi), Cint, (Ptr{Cvoid},), t.h))
 Base.length(t::TrajectoryGMMMapBlockDiag) = Int(ccall((:vcmi_traj_length, libvcmi), Int64, (Ptr{Cvoid},), t.h))
 dim(t::TrajectoryGMMMapBlockDiag) = dim(t.gmmmap)
+# rows of W per frame and static dimension: 2, or 3 for TrajectoryGMMMapBlockDiag(g, T; windows=3), whose vc takes fm (3D+1,T) and
+# whose vc(...; delta=true), batch vc, em_iters!(t, n > 0), cond_loglik and TrajectoryGVGMMMapDiag the library refuses
+windows(t::TrajectoryGMMMapBlockDiag) = Int(ccall((:vcmi_traj_get_windows, libvcmi), Cint, (Ptr{Cvoid},), t.h))
+static_dim(t::TrajectoryGMMMapBlockDiag) = div(dim(t), windows(t))
 ncomponents(t::TrajectoryGMMMapBlockDiag) = ncomponents(t.gmmmap)
 Base.size(t::TrajectoryGMMMapBlockDiag) = (dim(t), length(t))
 function fvconvert(t::TrajectoryGMMMapBlockDiag, X::Matrix{Float64})
     size(X, 1) == dim(t) || throw(DimensionMismatch("Inconsistent dimentions."))
-    Y = Matrix{Float64}(undef, size(X, 1) >> 1, size(X, 2))
+    Y = Matrix{Float64}(undef, static_dim(t), size(X, 2))
     check(ccall((:vcmi_traj_convert, libvcmi), Cint, (Ptr{Cvoid}, Ptr{Float64}, Int64, Ptr{Float64}),
                 t.h, X, size(X, 2), Y))
     Y
@@ -899,7 +920,7 @@ end
 function fvconvert(t::TrajectoryGMMMapBlockDiag, Xs::Vector{Matrix{Float64}})
     all(size(x, 1) == dim(t) for x in Xs) || throw(DimensionMismatch("Inconsistent dimentions."))
     T = Int64[size(x, 2) for x in Xs]
-    Ys = [Matrix{Float64}(undef, dim(t) >> 1, k) for k in T]
+    Ys = [Matrix{Float64}(undef, static_dim(t), k) for k in T]
     GC.@preserve Xs Ys begin
         check(ccall((:vcmi_traj_convert_batch, libvcmi), Cint,
                     (Ptr{Cvoid}, Int64, Ptr{Ptr{Float64}}, Ptr{Int64}, Ptr{Ptr{Float64}}),
@@ -908,8 +929,8 @@ function fvconvert(t::TrajectoryGMMMapBlockDiag, Xs::Vector{Matrix{Float64}})
     Ys
 end
 function vc(t::TrajectoryGMMMapBlockDiag, fm::Matrix{Float64}, vs::Union{VarianceScaling,Nothing}=nothing; delta::Bool=false)
-    D = dim(t) >> 1
-    size(fm, 1) == (delta ? D : 2D) + 1 || throw(DimensionMismatch("Inconsistent dimentions."))
+    D = static_dim(t)
+    size(fm, 1) == (delta ? D : dim(t)) + 1 || throw(DimensionMismatch("Inconsistent dimentions."))
     σ² = σ²vector(vs, D)
     out = Matrix{Float64}(undef, D + 1, size(fm, 2))
     GC.@preserve σ² begin
@@ -924,8 +945,8 @@ function vc(t::TrajectoryGMMMapBlockDiag, fm::Matrix{Float64}, vs::Union{Varianc
     out
 end
 function vc(t::TrajectoryGMMMapBlockDiag, fms::Vector{Matrix{Float64}}, vs::Union{VarianceScaling,Nothing}=nothing; delta::Bool=false)
-    D = dim(t) >> 1
-    all(size(fm, 1) == (delta ? D : 2D) + 1 for fm in fms) || throw(DimensionMismatch("Inconsistent dimentions."))
+    D = static_dim(t)
+    all(size(fm, 1) == (delta ? D : dim(t)) + 1 for fm in fms) || throw(DimensionMismatch("Inconsistent dimentions."))
     σ² = σ²vector(vs, D)
     T = Int64[size(fm, 2) for fm in fms]
     outs = [Matrix{Float64}(undef, D + 1, k) for k in T]
@@ -938,8 +959,8 @@ function vc(t::TrajectoryGMMMapBlockDiag, fms::Vector{Matrix{Float64}}, vs::Unio
 end
 function vc(t::TrajectoryGMMMapBlockDiag, fm::DeviceMatrix, out::DeviceMatrix, vs::Union{VarianceScaling,Nothing}=nothing;
             delta::Bool=false, stream::Ptr{Cvoid}=C_NULL)
-    D = dim(t) >> 1
-    fm.rows == (delta ? D : 2D) + 1 || throw(DimensionMismatch("Inconsistent dimentions."))
+    D = static_dim(t)
+    fm.rows == (delta ? D : dim(t)) + 1 || throw(DimensionMismatch("Inconsistent dimentions."))
     (out.rows == D + 1 && out.cols == fm.cols) || throw(DimensionMismatch("out must be (D+1,T)"))
     σ² = σ²vector(vs, D)
     GC.@preserve σ² begin

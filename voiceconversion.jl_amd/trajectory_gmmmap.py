@@ -9,13 +9,18 @@ from .common import TrajectoryConverter
 from .gmmmap_bdiag import BlockDiagGMMMap
 
 
-def constructW(D, T):
+def constructW(D, T, windows=2):
     """constructW(D, T): the (2DT x DT) sparse window matrix of src/trajectory_gmmmap.jl:39-61 -- identity for the
     static rows, -1/2 / +1/2 on the neighbouring frames for the delta rows (missing neighbours dropped).
     Host-side helper for API parity (test/trajectory_gmmmap.jl:1-34); the GPU solver applies W as a stencil and
-    never materialises it."""
+    never materialises it.  windows=3: (3DT x DT), rows [static; delta; delta-delta] per frame, the delta-delta rows 1 / -2 / 1
+    on frames t-1, t, t+1 (missing neighbours dropped, the -2 always there): W of BlockDiagTrajectoryGMMMap(g, T, windows=3)."""
     import scipy.sparse as sp
 
+    if windows == 3:
+        return _constructW3(D, T)
+    if windows != 2:
+        raise ValueError("constructW: windows must be 2 (static + delta) or 3 (static + delta + delta-delta)")
     t = np.arange(T)
     d = np.arange(D)
     rows = [(2 * D * t[:, None] + d[None, :]).ravel()]
@@ -33,22 +38,52 @@ def constructW(D, T):
     return sp.csc_matrix((np.concatenate(vals), (np.concatenate(rows), np.concatenate(cols))), shape=(2 * D * T, D * T))
 
 
-def push_delta(src):
+def _constructW3(D, T):
+    import scipy.sparse as sp
+
+    t = np.arange(T)
+    d = np.arange(D)
+    rows, cols, vals = [], [], []
+
+    def put(block, tt, shift, v):           # value v in the rows of `block` of frames tt, on the columns of frame tt + shift
+        rows.append((3 * D * tt[:, None] + block * D + d[None, :]).ravel())
+        cols.append((D * (tt[:, None] + shift) + d[None, :]).ravel())
+        vals.append(np.full(D * len(tt), v))
+
+    put(0, t, 0, 1.0)
+    put(2, t, 0, -2.0)
+    if T >= 2:
+        put(1, t[1:], -1, -0.5)
+        put(1, t[:-1], 1, 0.5)
+        put(2, t[1:], -1, 1.0)
+        put(2, t[:-1], 1, 1.0)
+    return sp.csc_matrix((np.concatenate(vals), (np.concatenate(rows), np.concatenate(cols))), shape=(3 * D * T, D * T))
+
+
+def push_delta(src, order=1):
     """push_delta(src (D,T)) -> (2D,T), src/datasets.jl:6-13: delta_t = (x_{t+1} - x_{t-1})/2 for 2 <= t <= T-1;
     the first and last frame keep a copy of the static features in the delta rows (repmat artefact).
     A torch tensor on the device gives a device tensor (vcmi_push_delta_dev on the current stream): the trajectory
-    converter's input is built where the features are."""
+    converter's input is built where the features are.
+    order=2 -> (3D,T): rows 0 .. 2D-1 as above, bit for bit; rows 2D .. 3D-1 the delta-delta x_{t-1} - 2 x_t + x_{t+1} with a
+    neighbour outside the matrix dropped (a_1 = -2 x_1 + x_2, a_T = x_{T-1} - 2 x_T) -- the rows of constructW(D, T, windows=3),
+    the input of BlockDiagTrajectoryGMMMap(g, T, windows=3) and of its model's training (vcmi_push_delta2[_dev])."""
+    if order not in (1, 2):
+        raise ValueError("push_delta: order must be 1 (static + delta) or 2 (static + delta + delta-delta)")
+    host, dev = ((_lib.lib.vcmi_push_delta, _lib.lib.vcmi_push_delta_dev) if order == 1 else
+                 (_lib.lib.vcmi_push_delta2, _lib.lib.vcmi_push_delta2_dev))
+    blocks = order + 1
     if is_torch(src):
         import torch
 
         ptr, D, T, ld = dev_matrix(src, "src")
-        buf = torch.empty((T, 2 * D), dtype=torch.float64, device=src.device)
-        _lib.check(_lib.lib.vcmi_push_delta_dev(ptr, ld, D, T, buf.data_ptr(), 2 * D, current_stream_ptr()))
+        buf = torch.empty((T, blocks * D), dtype=torch.float64, device=src.device)
+        _lib.check(dev(ptr, ld, D, T, buf.data_ptr(), blocks * D, current_stream_ptr()))
         return buf.t()
     src = jl_matrix(src, "src")
     D, T = src.shape
-    out = np.empty((2 * D, T), order="F")
-    _lib.check(_lib.lib.vcmi_push_delta(_lib.dptr(src), D, T, _lib.dptr(out)))
+    out = np.empty((blocks * D, T), order="F")
+    _lib.check(host(_lib.dptr(src), D, T, _lib.dptr(out)))
     return out
 
 
@@ -56,8 +91,8 @@ def _vc_host_args(c, fm, postfilter, delta):
     """fm of vc(c, fm; delta) on the host, (D+1,T) STATIC features if delta else (2D+1,T) -> (fm as a Julia matrix, D, sigma2
     argument)"""
     fm = jl_matrix(fm, "fm")
-    D = c._dim() // 2
-    if fm.shape[0] != (D if delta else 2 * D) + 1:
+    D = c._static_dim()
+    if fm.shape[0] != (D if delta else c._dim()) + 1:
         raise _lib.DimensionMismatch("Inconsistent dimentions.")
     return fm, D, sigma2_arg(postfilter, D)
 
@@ -69,8 +104,8 @@ def _vc_dev(c, fm, postfilter, delta, call):
     import torch
 
     ptr, rows, T, ld = dev_matrix(fm, "fm")
-    D = c._dim() // 2
-    if rows != (D if delta else 2 * D) + 1:
+    D = c._static_dim()
+    if rows != (D if delta else c._dim()) + 1:
         raise _lib.DimensionMismatch("Inconsistent dimentions.")
     s2 = sigma2_arg(postfilter, D)
     buf = torch.empty((T, D + 1), dtype=torch.float64, device=fm.device)
@@ -87,8 +122,8 @@ def _vc_batch(c, fms, postfilter, delta, host_call, dev_call):
     n = len(fms)
     if n == 0:
         return []
-    D = c._dim() // 2
-    rows = (D if delta else 2 * D) + 1
+    D = c._static_dim()
+    rows = (D if delta else c._dim()) + 1
     on_dev = [is_torch(f) and f.is_cuda for f in fms]
     if any(on_dev) and not all(on_dev):
         raise TypeError("vc_batch: device tensors and host matrices in one list")
@@ -184,7 +219,7 @@ class TrajectoryGMMMap(TrajectoryConverter):
 
             xp, D2, T, ldx = dev_matrix(X, "X")
             yp, D, Ty, ldy = dev_matrix(Y, "Y")
-            if D2 != self._dim() or 2 * D != D2 or Ty != T:
+            if D2 != self._dim() or D != self._static_dim() or Ty != T:
                 raise _lib.DimensionMismatch("Inconsistent dimentions.")
             if T > 1 and (ldx != D2 or ldy != D):
                 raise ValueError("cond_loglik: X and Y must be dense")
@@ -192,7 +227,7 @@ class TrajectoryGMMMap(TrajectoryConverter):
             _lib.check(self._cond_loglik_dev(self._h, xp, yp, T, out.data_ptr(), current_stream_ptr()))
             return out
         X, Y = jl_matrix(X, "X"), jl_matrix(Y, "Y")
-        if X.shape[0] != self._dim() or 2 * Y.shape[0] != X.shape[0] or X.shape[1] != Y.shape[1]:
+        if X.shape[0] != self._dim() or Y.shape[0] != self._static_dim() or X.shape[1] != Y.shape[1]:
             raise _lib.DimensionMismatch("Inconsistent dimentions.")
         L = C.c_double(0.0)
         _lib.check(self._cond_loglik(self._h, _lib.dptr(X), _lib.dptr(Y), X.shape[1], C.byref(L)))
@@ -219,35 +254,78 @@ class TrajectoryGMMMap(TrajectoryConverter):
     def _dim(self):                         # src/trajectory_gmmmap.jl:35
         return self.gmmmap._dim()
 
+    @property
+    def windows(self):
+        """rows of W per frame and static dimension: 2 (static + delta, the reference's), or 3 (static + delta + delta-delta)
+        for a BlockDiagTrajectoryGMMMap(g, T, windows=3)"""
+        return int(_lib.lib.vcmi_traj_get_windows(self._h))
+
+    def _static_dim(self):                  # D: dim(t) / windows
+        return self._dim() // self.windows
+
     def _ncomponents(self):                 # src/trajectory_gmmmap.jl:36
         return self.gmmmap._ncomponents()
 
     def _fvconvert(self, X):
-        """fvconvert(tgmm, X (2D,T)) -> (D,T); src/trajectory_gmmmap.jl:65-110"""
+        """fvconvert(tgmm, X (2D,T)) -> (D,T); src/trajectory_gmmmap.jl:65-110.  A torch tensor on the device is converted where it
+        is and a device tensor comes back (through the batch entry, which leaves len(t) as it is)."""
+        if is_torch(X) and X.is_cuda:
+            return self.fvconvert_batch([X])[0]
         X = jl_matrix(X, "X")
         D2, T = X.shape
         if D2 != self._dim():               # src/trajectory_gmmmap.jl:68
             raise _lib.DimensionMismatch("Inconsistent dimentions.")
-        Y = np.empty((D2 // 2, T), order="F")
+        Y = np.empty((self._static_dim(), T), order="F")
         _lib.check(_lib.lib.vcmi_traj_convert(self._h, _lib.dptr(X), T, _lib.dptr(Y)))
         return Y
 
     def fvconvert_batch(self, Xs):
-        """Batch extension: independent utterances in one launch (one workgroup per utterance)."""
+        """Batch extension: independent utterances in one launch (one workgroup per utterance).  A list of device tensors (each
+        with unit stride along its rows; one that is not dense is copied) is converted where it is, on the current stream
+        (vcmi_traj_convert_batch_dev): the results are device tensors, views of one new (sum T, D) buffer."""
         n = len(Xs)
         if n == 0:
             return []
+        on_dev = [is_torch(x) and x.is_cuda for x in Xs]
+        if any(on_dev):
+            if not all(on_dev):
+                raise TypeError("fvconvert_batch: device tensors and host matrices in one list")
+            return self._fvconvert_batch_dev(list(Xs))
         Xs = [jl_matrix(x, "X") for x in Xs]
         D2 = self._dim()
         for x in Xs:
             if x.shape[0] != D2:
                 raise _lib.DimensionMismatch("Inconsistent dimentions.")
         T = np.array([x.shape[1] for x in Xs], dtype=np.int64)
-        Ys = [np.empty((D2 // 2, int(t)), order="F") for t in T]
+        Ys = [np.empty((self._static_dim(), int(t)), order="F") for t in T]
         dpp = C.POINTER(C.c_double) * n
         _lib.check(_lib.lib.vcmi_traj_convert_batch(self._h, n, dpp(*[_lib.dptr(x) for x in Xs]), _lib.iptr(T),
                                                     dpp(*[_lib.dptr(y) for y in Ys])))
         return Ys
+
+    def _fvconvert_batch_dev(self, Xs):
+        import torch
+
+        D2, D = self._dim(), self._static_dim()
+        dense = []                                   # (kept alive until the call returns: it ends with a status read)
+        for x in Xs:
+            if x.dim() != 2 or x.shape[0] != D2:
+                raise _lib.DimensionMismatch("Inconsistent dimentions.")
+            if x.shape[1] > 0:                       # (an empty tensor has no strides to speak of, and is never read)
+                _, _, t, ld = dev_matrix(x, "X")
+                if t > 1 and ld != D2:
+                    x = x.t().contiguous().t()
+            dense.append(x)
+        T = np.array([x.shape[1] for x in dense], dtype=np.int64)
+        ptrs = [x.data_ptr() for x in dense]
+        base = next((p for p, t in zip(ptrs, T) if t > 0), 0)
+        x_off = np.array([(p - base) // 8 if t > 0 else 0 for p, t in zip(ptrs, T)], dtype=np.int64)
+        first = np.concatenate([[0], np.cumsum(T)])
+        buf = torch.empty((int(first[-1]), D), dtype=torch.float64, device=Xs[0].device)
+        y_off = np.ascontiguousarray(first[:-1] * D, dtype=np.int64)
+        _lib.check(_lib.lib.vcmi_traj_convert_batch_dev(self._h, len(dense), base, _lib.iptr(x_off), _lib.iptr(T), buf.data_ptr(),
+                                                        _lib.iptr(y_off), current_stream_ptr()))
+        return [buf[int(first[u]):int(first[u + 1])].t() for u in range(len(dense))]
 
     def _vc(self, fm, postfilter=None, delta=False):
         """vc(c::TrajectoryConverter, fm (2D+1,T)) -> (D+1,T) in chunks of length(c) frames; src/common.jl:31-63.
@@ -284,14 +362,25 @@ class BlockDiagTrajectoryGMMMap(TrajectoryGMMMap):
     TrajectoryGMMMap(GMMMap(weights, mu, expand_block_diag(covars)), T, precision="diag") to rounding.  fvconvert,
     fvconvert_batch, vc and vc_batch are TrajectoryGMMMap's; precision is "diag" for good, and em_iters > 0, precision = "full",
     cond_loglik and a TrajectoryGVGMMMap over it are refused (VCMIError); global variance: DiagTrajectoryGVGMMMap.  Converts on the
-    device g was created on.  EM re-estimation over all mixtures and cond_loglik for such a model: BlockDiagTrajectoryEMGMMMap."""
+    device g was created on.  EM re-estimation over all mixtures and cond_loglik for such a model: BlockDiagTrajectoryEMGMMMap.
+    windows=3: g is a model over static + delta + delta-delta features (dim(g) = 3D, the rows push_delta(src, order=2) makes;
+    DimensionMismatch otherwise; VCMIError for any other count).  W = constructW(D, T, windows=3), and the normal
+    equations are one pentadiagonal system per static dimension (csrc/traj_penta.hip; include/vcmi.h:
+    vcmi_traj_create_bdiag_windows).  fvconvert, fvconvert_batch and vc(c, fm (3D+1,T)) with or without a postfilter, on host
+    matrices and (vc) device tensors, convert with it; vc(..., delta=True), vc_batch, BlockDiagTrajectoryEMGMMMap's em_iters > 0 and
+    cond_loglik, and a DiagTrajectoryGVGMMMap over it are refused (VCMIError naming three windows): follow-ups."""
 
-    def __init__(self, g, T):
+    def __init__(self, g, T, windows=2):
         if not isinstance(g, BlockDiagGMMMap):
             raise TypeError(f"BlockDiagTrajectoryGMMMap takes a BlockDiagGMMMap, not a {type(g).__name__}")
+        if isinstance(windows, bool) or not isinstance(windows, (int, np.integer)):
+            raise TypeError(f"BlockDiagTrajectoryGMMMap: windows must be an integer, not a {type(windows).__name__}")
         self.gmmmap = g                     # (kept alive: the library's handle reads g's tables in every call)
         h = C.c_void_p()
-        _lib.check(_lib.lib.vcmi_traj_create_bdiag(g._h, int(T), C.byref(h)))
+        if windows == 2:                    # (the entry the converter has always used)
+            _lib.check(_lib.lib.vcmi_traj_create_bdiag(g._h, int(T), C.byref(h)))
+        else:
+            _lib.check(_lib.lib.vcmi_traj_create_bdiag_windows(g._h, int(T), int(windows), C.byref(h)))
         self._h = h
 
 
@@ -331,7 +420,7 @@ class TrajectoryGVGMMMap(TrajectoryConverter):
     def __init__(self, tgmm, muv, sigmavv):
         muv = np.ascontiguousarray(np.asarray(muv, dtype=np.float64).reshape(-1))
         sigmavv = jl_matrix(sigmavv, "sigmavv")
-        D = tgmm._dim() // 2
+        D = tgmm._static_dim()
         if muv.shape != (D,) or sigmavv.shape != (D, D):
             raise _lib.DimensionMismatch("the GV statistics must have the static feature dimension")
         if np.any(muv < 0):                 # @assert sum(mu^v .< 0) == 0, src/trajectory_gmmmap.jl:124
@@ -353,6 +442,9 @@ class TrajectoryGVGMMMap(TrajectoryConverter):
     def _dim(self):                         # :133
         return self.tgmm._dim()
 
+    def _static_dim(self):
+        return self.tgmm._static_dim()
+
     def _ncomponents(self):                 # :134
         return self.tgmm._ncomponents()
 
@@ -370,7 +462,7 @@ class TrajectoryGVGMMMap(TrajectoryConverter):
             if x.shape[0] != D2:
                 raise _lib.DimensionMismatch("Inconsistent dimentions.")
         T = np.array([x.shape[1] for x in Xs], dtype=np.int64)
-        Ys = [np.empty((D2 // 2, int(t)), order="F") for t in T]
+        Ys = [np.empty((self._static_dim(), int(t)), order="F") for t in T]
         dpp = C.POINTER(C.c_double) * n
         _lib.check(_lib.lib.vcmi_trajgv_convert_batch(self._h, n, dpp(*[_lib.dptr(x) for x in Xs]), _lib.iptr(T), int(epochs),
                                                       float(alpha), dpp(*[_lib.dptr(y) for y in Ys])))
