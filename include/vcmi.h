@@ -474,7 +474,7 @@ int vcmi_traj_create_bdiag(vcmi_bdmap *b, int64_t T, vcmi_traj **out);
  * for bit).  Follow-ups, not provided yet -- VCMI_ERR_ARG with a message that says three windows, before any launch, the handle
  * usable afterwards: vcmi_vc_traj_static and is_static = 1 of vcmi_vc_traj_dev; the vcmi_vc_traj_batch family;
  * vcmi_traj_set_em_bdiag(t, n > 0); vcmi_traj_cond_loglik_bdiag[_dev]; vcmi_trajgv_create_diag over such a handle (refused when
- * the GV handle is made).  What vcmi_traj_create_bdiag refuses, a handle with three windows refuses too. */
+ * the GV handle is made; the GV ascent over three windows: vcmi_trajgv_create_bdiag).  What vcmi_traj_create_bdiag refuses, a handle with three windows refuses too. */
 int vcmi_traj_create_bdiag_windows(vcmi_bdmap *b, int64_t T, int windows, vcmi_traj **out);
 /* 2, or 3 for a handle of vcmi_traj_create_bdiag_windows(b, T, 3); -1 for NULL */
 int vcmi_traj_get_windows(const vcmi_traj *t);
@@ -631,6 +631,21 @@ int vcmi_trajgv_create(vcmi_traj *t, const double *muv, const double *sigmavv, v
  * D > 512: VCMI_ERR_ARG.  Device groups: an ordinary DIAG converter shards as vcmi_trajgv_create's does; one of
  * vcmi_traj_create_bdiag converts on its own device. */
 int vcmi_trajgv_create_diag(vcmi_traj *t, const double *muv, const double *sigmavv, vcmi_trajgv **out);
+/* The same converter over a handle of vcmi_traj_create_bdiag[_windows] ONLY; any other t: VCMI_ERR_ARG naming vcmi_trajgv_create
+ * and vcmi_trajgv_create_diag.  Arguments and checks of vcmi_trajgv_create_diag (a negative mu^v: VCMI_ERR_ARG; a singular
+ * Sigma^vv: VCMI_ERR_NOT_PD).  Two windows: the handle is the one vcmi_trajgv_create_diag makes, every result bit for bit that
+ * one's.  Three windows (vcmi_traj_create_bdiag_windows(b, T, 3), which vcmi_trajgv_create_diag keeps refusing): the likelihood
+ * gradient is the five-point stencil of the pentadiagonal system the solver factorises,
+ *   (P y)_t = c0_t y_t + c1_t y_{t-1} + c1_{t+1} y_{t+1} + c2_t y_{t-2} + c2_{t+2} y_{t+2}      (csrc/traj_gvp_step.hpp),
+ * a Jacobi step on two y buffers in traj_gvp_kernel (csrc/traj_gv_penta.hip): one workgroup per utterance with all epochs
+ * inside; as many of its six (T,D) arrays (y, second y, c1, c2, c0, r) as fit the 160 KB of LDS stay there across the epochs,
+ * chosen from D and the longest utterance of the call (csrc/traj_gvp_plan.hpp), the rest is streamed: every T >= 2 converts, and
+ * an utterance's result does not depend on the batch it came in.  Scratch on the trajectory handle: 5 D N doubles for the N
+ * frames of a call, the first two on the solver's l1 and l2 (dead once the solve has run).  The three-window handle goes to
+ * vcmi_trajgv_convert, _batch, _batch_dev (X (3D,T)) and to vcmi_vc_trajgv / vcmi_vc_trajgv_dev with is_static = 0 (fm (3D+1,T)),
+ * with or without sigma2; is_static = 1 and vcmi_vc_trajgv_batch[_dev] stay VCMI_ERR_ARG ("three windows"), as for the plain
+ * converter.  Converts on the device b was created on. */
+int vcmi_trajgv_create_bdiag(vcmi_traj *t, const double *muv, const double *sigmavv, vcmi_trajgv **out);
 int vcmi_trajgv_destroy(vcmi_trajgv *h);
 /* fvconvert(tgv, X; epochs=100, alpha=1.0e-5) :139-168: trajectory solve, eq.(58) rescaling, then `epochs` steps of
  * y += alpha (omega (W'D^-1E - W'D^-1W y) + gvgrad(y)), all on the device.  X (2D,T) -> Y (D,T). */

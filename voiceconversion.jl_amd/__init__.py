@@ -17,7 +17,7 @@ from .estep import (ESTEP_AUTO, ESTEP_HARD, ESTEP_SOFT, estep_diag, estep_diag_a
                     estep_full, estep_full_allreduce, estep_full_dev, fit_full, full_stats_len, mstep_full,
                     unpack_full_stats,
                     bdiag_stats_len, estep_bdiag_dev, mstep_bdiag, unpack_bdiag_stats)
-from .trajectory_gmmmap import BlockDiagTrajectoryEMGMMMap, BlockDiagTrajectoryGMMMap, DiagTrajectoryGVGMMMap, TrajectoryGVGMMMap, TrajectoryGMMMap, constructW, push_delta  # noqa: F401,E402
+from .trajectory_gmmmap import BlockDiagTrajectoryEMGMMMap, BlockDiagTrajectoryGMMMap, BlockDiagTrajectoryGVGMMMap, DiagTrajectoryGVGMMMap, TrajectoryGVGMMMap, TrajectoryGMMMap, constructW, push_delta  # noqa: F401,E402
 from . import dist  # noqa: F401,E402
 from .train import (BlockDiagEMState, DiagEMState, EMState, data_block_covariance, expand_block_diag, expand_diag,  # noqa: F401,E402
                     train_gmm)

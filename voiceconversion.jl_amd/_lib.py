@@ -174,6 +174,7 @@ SIGNATURES = {
     "vcmi_vc_trajgv_batch_dev": (_int, [_vp, _i64, _vp, _ip, _ip, _int, _int, C.c_double, _dp, _vp, _ip, _vp]),
     "vcmi_trajgv_create": (_int, [_vp, _dp, _dp, C.POINTER(_vp)]),
     "vcmi_trajgv_create_diag": (_int, [_vp, _dp, _dp, C.POINTER(_vp)]),
+    "vcmi_trajgv_create_bdiag": (_int, [_vp, _dp, _dp, C.POINTER(_vp)]),
     "vcmi_trajgv_destroy": (_int, [_vp]),
     "vcmi_trajgv_convert": (_int, [_vp, _dp, _i64, _int, C.c_double, _dp]),
     "vcmi_trajgv_convert_batch": (_int, [_vp, _i64, _dpp, _ip, _int, C.c_double, _dpp]),

@@ -249,7 +249,11 @@ int traj_run(vcmi_traj *t, std::vector<TrajUtt> &utts, int64_t nframes, bool con
   VCMI_TRY(traj_solve_plan(t, utts, nframes, Tmax, gv != nullptr, &plan));
   t->em_run_iters = 0;
   if (diag) {     // (EM: over a cross-diagonal handle only, vcmi_traj_set_em_bdiag; GV: a handle of vcmi_trajgv_create_diag)
-    if (t->windows == 3) return traj_penta_launch(t, plan, t->dg_q.p, t->mhat.p, st);     // (no EM, no GV over such a handle)
+    if (t->windows == 3) {     // (no EM over such a handle; GV: a handle of vcmi_trajgv_create_bdiag)
+      VCMI_TRY(traj_penta_launch(t, plan, t->dg_q.p, t->mhat.p, st));
+      if (gv && gv->epochs >= 0) VCMI_TRY(traj_gvp_launch(t, plan, *gv, st));
+      return VCMI_OK;
+    }
     VCMI_TRY(traj_diag_launch(t, plan, t->dg_q.p, t->mhat.p, st));
     if (t->b && t->em_iters > 0) VCMI_TRY(traj_em_bdiag_run(t, utts, plan, st));
     if (gv && gv->epochs >= 0) VCMI_TRY(traj_gvd_launch(t, plan, *gv, st));

@@ -787,11 +787,16 @@ int trajgv_args(const vcmi_trajgv *h, int64_t n, const int64_t *T, int epochs, T
 using namespace vcmi;
 
 // ---- TrajectoryGVGMMMap, src/trajectory_gmmmap.jl:114-189 ----------------------------------------
-static int trajgv_create(vcmi_traj *t, const double *muv, const double *sigmavv, bool diag, vcmi_trajgv **out) {
-  const char *who = diag ? "vcmi_trajgv_create_diag" : "vcmi_trajgv_create";
+// bdiag: vcmi_trajgv_create_bdiag -- a cross-diagonal converter only, with two windows (the handle of vcmi_trajgv_create_diag) or
+// three (traj_gv_penta.hip)
+static int trajgv_create(vcmi_traj *t, const double *muv, const double *sigmavv, bool diag, vcmi_trajgv **out, bool bdiag = false) {
+  const char *who = bdiag ? "vcmi_trajgv_create_bdiag" : diag ? "vcmi_trajgv_create_diag" : "vcmi_trajgv_create";
   if (!t || !muv || !sigmavv || !out) return fail(VCMI_ERR_ARG, "%s: NULL argument", who);
   *out = nullptr;
-  if (diag) VCMI_TRY(traj_two_windows_only(t, who, "the GV ascent"));     // (traj_gvd_kernel's gradient is the two-window stencil)
+  if (bdiag && !t->b)
+    return fail(VCMI_ERR_ARG, "vcmi_trajgv_create_bdiag: the trajectory converter is not one of vcmi_traj_create_bdiag[_windows]: "
+                              "vcmi_trajgv_create or vcmi_trajgv_create_diag makes the handle for it");
+  if (diag && !bdiag) VCMI_TRY(traj_two_windows_only(t, who, "the GV ascent"));     // (traj_gvd_kernel's gradient is the two-window stencil)
   if (diag && t->precision != VCMI_TRAJ_PRECISION_DIAG)
     return fail(VCMI_ERR_ARG, "vcmi_trajgv_create_diag: the trajectory converter has full conditional precisions "
                               "(vcmi_traj_set_precision): vcmi_trajgv_create makes the handle for it");
@@ -834,6 +839,12 @@ extern "C" int vcmi_trajgv_create(vcmi_traj *t, const double *muv, const double 
 // ... over a converter with diagonal conditional precisions (vcmi_traj_set_precision, vcmi_traj_create_bdiag): traj_gv_diag.hip
 extern "C" int vcmi_trajgv_create_diag(vcmi_traj *t, const double *muv, const double *sigmavv, vcmi_trajgv **out) {
   return trajgv_create(t, muv, sigmavv, true, out);
+}
+
+// ... over a converter made straight from a cross-diagonal model, with two windows (the handle above, bit for bit) or three
+// (traj_gv_penta.hip: traj_gvp_kernel)
+extern "C" int vcmi_trajgv_create_bdiag(vcmi_traj *t, const double *muv, const double *sigmavv, vcmi_trajgv **out) {
+  return trajgv_create(t, muv, sigmavv, true, out, true);
 }
 
 extern "C" int vcmi_trajgv_destroy(vcmi_trajgv *h) {

@@ -14,24 +14,9 @@
 #include "traj_internal.hpp"
 #include "traj_gv_moments.hpp"
 #include "traj_gvd_plan.hpp"
+#include "traj_gv_sel.hpp"      // GvdPtr / gvd_sel: an array in LDS or in global memory, per instantiation
 
 namespace vcmi {
-
-// an array of the ascent lives in LDS or in global memory, decided per instantiation: the accesses are ds_ / global_
-// instructions, never flat ones
-template <bool LDS>
-struct GvdPtr {
-  typedef gdouble *type;
-};
-template <>
-struct GvdPtr<true> {
-  typedef double *type;
-};
-template <bool LDS>
-__device__ __forceinline__ typename GvdPtr<LDS>::type gvd_sel(double *lds, gdouble *glob) {
-  if constexpr (LDS) return lds;
-  else return glob;
-}
 
 static constexpr int kGvdBatch = 4;   // independent frames a thread has in flight in the epoch: 7 loads each
 

@@ -71,7 +71,7 @@ struct vcmi_trajgv {
   vcmi_traj *t = nullptr;
   vcmi::DevBuf<double> muv, pv;   // (D), (D,D) = inv(Sigma^vv) in the Julia memory image
   std::vector<double> h_muv, h_pv;             // host copies for the device-group replicas
-  bool diag = false;              // made by vcmi_trajgv_create_diag: converts only while t's precision is DIAG (traj_gv_diag.hip)
+  bool diag = false;              // made by vcmi_trajgv_create_diag / _bdiag: converts only while t's precision is DIAG (traj_gv_diag.hip)
   std::vector<vcmi_trajgv *> replicas;
   uint64_t replicas_epoch = 0;
   ~vcmi_trajgv() {
@@ -130,7 +130,8 @@ bool traj_solve_is_big(int D);
 // path), gpad / ypad / gwin where the solver needs them, and uploads the padded descriptors (synchronous).  A reserve that
 // grows a buffer frees the old one, which waits for the device.  A handle in diagonal mode gets n, Tmax, nframes, du, cus, grid and a
 // workspace of gvd_ws_doubles (traj_gvd_plan.hpp: nframes * D doubles, five times that with_gv), its size in ws_stride: no
-// padded copies, no window, no occupancy query.  A handle with three windows gets penta_ws_doubles instead (traj_penta_plan.hpp).
+// padded copies, no window, no occupancy query.  A handle with three windows gets penta_ws_doubles instead (traj_penta_plan.hpp),
+// with_gv gvp_ws_doubles (traj_gvp_plan.hpp).
 int traj_solve_plan(vcmi_traj *t, const std::vector<TrajUtt> &utts, int64_t nframes, int Tmax, bool with_gv, TrajSolvePlan *plan);
 // Solve of the (sorted) utterances [b0, b0 + nb) with the precision table Qs (indexed by mh[t] - 1: t->Q / t->Qpad with t->mhat,
 // or the EM loop's table; in plan.Ds) and the right-hand sides in t->gbuf: gbuf -> gpad where padded, the solver the plan chose,
@@ -164,6 +165,11 @@ int traj_gv_launch(vcmi_traj *t, const TrajSolvePlan &plan, const TrajGV &gv, hi
 // the working set stays in LDS follows traj_gvd_plan.hpp from D and plan.Tmax).  Reads t->mhat, t->gbuf, t->dg_q; workspace: the
 // four (nframes,D) arrays behind the solver's in t->ws (a plan made in diagonal mode with_gv).  Asynchronous on st.
 int traj_gvd_launch(vcmi_traj *t, const TrajSolvePlan &plan, const TrajGV &gv, hipStream_t st);
+// The ascent over a converter with three windows, behind traj_penta_launch (traj_gv_penta.hip: traj_gvp_kernel; how much of the
+// working set stays in LDS follows traj_gvp_plan.hpp from D and plan.Tmax).  Reads t->mhat, t->gbuf, t->dg_q; workspace: five
+// (nframes,D) arrays from the start of t->ws, the first two on the solver's l1 and l2 (a plan made for such a handle with_gv).
+// Asynchronous on st.
+int traj_gvp_launch(vcmi_traj *t, const TrajSolvePlan &plan, const TrajGV &gv, hipStream_t st);
 // the checks of a call on a TrajectoryGVGMMMap (T may be NULL) and the per-call parameters of its GV ascent; no device work
 int trajgv_args(const vcmi_trajgv *h, int64_t n, const int64_t *T, int epochs, TrajGV *gv);
 

@@ -21,7 +21,7 @@ inline int64_t penta_ws_doubles(int64_t nframes, int D) { return kPentaArrays * 
 
 // Workspace of a call over diagonal conditional precisions, in doubles, by the handle's window count: two windows keep
 // gvd_ws_doubles (the tridiagonal solver's one array; five with GV), three windows get the two arrays above and nothing else
-// (no GV ascent over such a handle: refused when the GV handle is made).
+// (a GV call over such a handle -- vcmi_trajgv_create_bdiag -- does not come through here: traj_gvp_plan.hpp).
 inline int64_t traj_diag_ws_doubles(int windows, int64_t nframes, int D, bool with_gv) {
   return windows == 3 ? penta_ws_doubles(nframes, D) : gvd_ws_doubles(nframes, D, with_gv);
 }

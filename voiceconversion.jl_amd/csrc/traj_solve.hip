@@ -3,6 +3,7 @@
 #include "traj_internal.hpp"
 #include "traj_prepare.hpp"
 #include "traj_penta_plan.hpp"
+#include "traj_gvp_plan.hpp"
 #include "traj_blk_prof.hpp"
 #include "hostpipe.hpp"
 #include "lds_dma.hpp"
@@ -476,8 +477,9 @@ int traj_solve_plan(vcmi_traj *t, const std::vector<TrajUtt> &utts, int64_t nfra
     p.du = p.dus = reinterpret_cast<const TrajUtt *>(t->uttbuf.p);
     p.gs = t->gbuf.p;
     p.grid = std::min(n, p.cus);            // workgroups of the GV ascent (traj_gvd_kernel)
-    // the whole reserve, not a stride: traj_gvd_launch checks it (three windows: the pentadiagonal solver's two arrays)
-    p.ws_stride = traj_diag_ws_doubles(t->windows, nframes, D, with_gv);
+    // the whole reserve, not a stride: traj_gvd_launch checks it (three windows: the pentadiagonal solver's two arrays; with GV
+    // the five of traj_gvp_plan.hpp, which traj_gvp_launch checks)
+    p.ws_stride = t->windows == 3 && with_gv ? gvp_ws_doubles(nframes, D, true) : traj_diag_ws_doubles(t->windows, nframes, D, with_gv);
     return t->ws.reserve((size_t)p.ws_stride);
   }
   p.grid = std::min(n, p.cus);

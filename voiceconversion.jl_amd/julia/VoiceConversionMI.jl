@@ -19,7 +19,7 @@ module VoiceConversionMI
 import LinearAlgebra
 
 export DeviceMatrix, FrameByFrameConverter, TrajectoryConverter, GMMMapParam, GMMMap, GMMMapBlockDiag, slopes, TrajectoryGMMMap, TrajectoryGMMMapBlockDiag, TrajectoryGMMMapBlockDiagEM,
-       TrajectoryGVGMMMap, TrajectoryGVGMMMapDiag,
+       TrajectoryGVGMMMap, TrajectoryGVGMMMapDiag, TrajectoryGVGMMMapBlockDiag,
        fvconvert, vc, ncomponents, dim, em_iters, em_iters!, traj_precision, traj_precision!, cond_loglik, em_history,
        VarianceScaling, fvpostf!, fvpostf,
        align, align_mcep, push_delta, GVDataset, sp2mc, mc2sp, mc2b,
@@ -620,15 +620,28 @@ mutable struct TrajectoryGVGMMMap <: TrajectoryConverter
         finalizer(x -> ccall((:vcmi_trajgv_destroy, libvcmi), Cint, (Ptr{Cvoid},), x.h), tgv)
         tgv
     end
+    # over a converter made straight from a cross-diagonal model, two or three windows (vcmi_trajgv_create_bdiag):
+    # TrajectoryGVGMMMapBlockDiag below
+    function TrajectoryGVGMMMap(tgmm::TrajectoryConverter, μᵛ::Vector{Float64}, Σᵛᵛ::Matrix{Float64}, diag::Bool, bdiag::Bool)
+        @assert diag && bdiag && sum(μᵛ .< 0) == 0
+        h = Ref{Ptr{Cvoid}}(C_NULL)
+        check(ccall((:vcmi_trajgv_create_bdiag, libvcmi), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ref{Ptr{Cvoid}}),
+                    tgmm.h, μᵛ, Σᵛᵛ, h))
+        tgv = new(tgmm, μᵛ, Σᵛᵛ, h[])
+        finalizer(x -> ccall((:vcmi_trajgv_destroy, libvcmi), Cint, (Ptr{Cvoid},), x.h), tgv)
+        tgv
+    end
 end
 Base.length(t::TrajectoryGVGMMMap) = length(t.tgmm)
 dim(t::TrajectoryGVGMMMap) = dim(t.tgmm)
+# D: dim(t) / 2, or dim(t) / 3 over a TrajectoryGMMMapBlockDiag(g, T; windows=3)
+static_dim(t::TrajectoryGVGMMMap) = t.tgmm isa TrajectoryGMMMapBlockDiag ? static_dim(t.tgmm) : dim(t) >> 1
 ncomponents(t::TrajectoryGVGMMMap) = ncomponents(t.tgmm)
 Base.size(t::TrajectoryGVGMMMap) = size(t.tgmm)
 
 function fvconvert(tgv::TrajectoryGVGMMMap, X::Matrix{Float64}; epochs::Int=100, α::Float64=1.0e-5, verbose::Bool=false)
     size(X, 1) == dim(tgv) || throw(DimensionMismatch("Inconsistent dimentions."))
-    Y = Matrix{Float64}(undef, dim(tgv) >> 1, size(X, 2))
+    Y = Matrix{Float64}(undef, static_dim(tgv), size(X, 2))
     check(ccall((:vcmi_trajgv_convert, libvcmi), Cint, (Ptr{Cvoid}, Ptr{Float64}, Int64, Cint, Cdouble, Ptr{Float64}),
                 tgv.h, X, size(X, 2), epochs, α, Y))
     Y
@@ -643,13 +656,13 @@ function vc(tgv::TrajectoryGVGMMMap, fm::Matrix{Float64})
     spans = [(b, min(b + limit - 1, T)) for b in 1:limit:T]
     Xs = [fm[2:end, b:e] for (b, e) in spans]
     Ts = Int64[size(x, 2) for x in Xs]
-    Ys = [Matrix{Float64}(undef, dim(tgv) >> 1, k) for k in Ts]
+    Ys = [Matrix{Float64}(undef, static_dim(tgv), k) for k in Ts]
     GC.@preserve Xs Ys begin
         check(ccall((:vcmi_trajgv_convert_batch, libvcmi), Cint,
                     (Ptr{Cvoid}, Int64, Ptr{Ptr{Float64}}, Ptr{Int64}, Cint, Cdouble, Ptr{Ptr{Float64}}),
                     tgv.h, length(Xs), pointer.(Xs), Ts, 100, 1.0e-5, pointer.(Ys)))
     end
-    out = Matrix{Float64}(undef, dim(tgv) >> 1 + 1, T)
+    out = Matrix{Float64}(undef, static_dim(tgv) + 1, T)
     for (k, (b, e)) in enumerate(spans)
         out[2:end, b:e] = Ys[k]
     end
@@ -722,8 +735,8 @@ end
 # length(tgv) is the last chunk's length (src/trajectory_gmmmap.jl:70-72,146)
 function vc(tgv::TrajectoryGVGMMMap, fm::Matrix{Float64}, vs::Union{VarianceScaling,Nothing}; delta::Bool=false,
             epochs::Int=100, α::Float64=1.0e-5)
-    D = dim(tgv) >> 1
-    size(fm, 1) == (delta ? D : 2D) + 1 || throw(DimensionMismatch("Inconsistent dimentions."))
+    D = static_dim(tgv)
+    size(fm, 1) == (delta ? D : dim(tgv)) + 1 || throw(DimensionMismatch("Inconsistent dimentions."))
     σ² = σ²vector(vs, D)
     out = Matrix{Float64}(undef, D + 1, size(fm, 2))
     GC.@preserve σ² begin
@@ -777,8 +790,8 @@ function vc(t::TrajectoryGMMMap, fms::Vector{Matrix{Float64}}, vs::Union{Varianc
 end
 function vc(tgv::TrajectoryGVGMMMap, fms::Vector{Matrix{Float64}}, vs::Union{VarianceScaling,Nothing}=nothing;
             delta::Bool=false, epochs::Int=100, α::Float64=1.0e-5)
-    D = dim(tgv) >> 1
-    all(size(fm, 1) == (delta ? D : 2D) + 1 for fm in fms) || throw(DimensionMismatch("Inconsistent dimentions."))
+    D = static_dim(tgv)
+    all(size(fm, 1) == (delta ? D : dim(tgv)) + 1 for fm in fms) || throw(DimensionMismatch("Inconsistent dimentions."))
     σ² = σ²vector(vs, D)
     T = Int64[size(fm, 2) for fm in fms]
     outs = [Matrix{Float64}(undef, D + 1, k) for k in T]
@@ -827,8 +840,8 @@ function vc(t::TrajectoryGMMMap, fm::DeviceMatrix, out::DeviceMatrix, vs::Union{
 end
 function vc(tgv::TrajectoryGVGMMMap, fm::DeviceMatrix, out::DeviceMatrix, vs::Union{VarianceScaling,Nothing}=nothing;
             delta::Bool=false, epochs::Int=100, α::Float64=1.0e-5, stream::Ptr{Cvoid}=C_NULL)
-    D = dim(tgv) >> 1
-    fm.rows == (delta ? D : 2D) + 1 || throw(DimensionMismatch("Inconsistent dimentions."))
+    D = static_dim(tgv)
+    fm.rows == (delta ? D : dim(tgv)) + 1 || throw(DimensionMismatch("Inconsistent dimentions."))
     (out.rows == D + 1 && out.cols == fm.cols) || throw(DimensionMismatch("out must be (D+1,T)"))
     σ² = σ²vector(vs, D)
     GC.@preserve σ² begin
@@ -873,6 +886,12 @@ end
 # and a TrajectoryGVGMMMap(tgmm, μᵛ, Σᵛᵛ) over the same tgmm keeps refusing while it is).
 TrajectoryGVGMMMapDiag(tgmm::Union{TrajectoryGMMMap,TrajectoryGMMMapBlockDiag}, μᵛ::Vector{Float64}, Σᵛᵛ::Matrix{Float64}) =
     TrajectoryGVGMMMap(tgmm, μᵛ, Σᵛᵛ, true)
+# TrajectoryGVGMMMapBlockDiag(tgmm, μᵛ, Σᵛᵛ): the GV converter over a TrajectoryGMMMapBlockDiag (vcmi_trajgv_create_bdiag).  Two
+# windows: TrajectoryGVGMMMapDiag bit for bit.  windows=3, which TrajectoryGVGMMMapDiag refuses: the five-point stencil of the
+# pentadiagonal system (csrc/traj_gv_penta.hip); fvconvert (X (3D,T)), its batch form and vc(tgv, fm (3D+1,T)) on host and device
+# matrices, with or without a VarianceScaling; vc(...; delta=true) and batch vc stay refused by the library.
+TrajectoryGVGMMMapBlockDiag(tgmm::TrajectoryGMMMapBlockDiag, μᵛ::Vector{Float64}, Σᵛᵛ::Matrix{Float64}) =
+    TrajectoryGVGMMMap(tgmm, μᵛ, Σᵛᵛ, true, true)
 # TrajectoryGMMMapBlockDiagEM(g, T; em_iters=1): a TrajectoryGMMMapBlockDiag with EM re-estimation over all mixtures after the
 # arg-max solution (vcmi_traj_set_em_bdiag, csrc/traj_em_bdiag.hip): the same struct -- every method below applies -- with the
 # setting made; em_iters!(t, n) changes it (0: the plain conversion), cond_loglik(t, X, Y) is the objective the iterations

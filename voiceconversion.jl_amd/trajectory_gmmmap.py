@@ -368,7 +368,8 @@ class BlockDiagTrajectoryGMMMap(TrajectoryGMMMap):
     equations are one pentadiagonal system per static dimension (csrc/traj_penta.hip; include/vcmi.h:
     vcmi_traj_create_bdiag_windows).  fvconvert, fvconvert_batch and vc(c, fm (3D+1,T)) with or without a postfilter, on host
     matrices and (vc) device tensors, convert with it; vc(..., delta=True), vc_batch, BlockDiagTrajectoryEMGMMMap's em_iters > 0 and
-    cond_loglik, and a DiagTrajectoryGVGMMMap over it are refused (VCMIError naming three windows): follow-ups."""
+    cond_loglik, and a DiagTrajectoryGVGMMMap over it are refused (VCMIError naming three windows): follow-ups.  Global variance
+    over three windows: BlockDiagTrajectoryGVGMMMap."""
 
     def __init__(self, g, T, windows=2):
         if not isinstance(g, BlockDiagGMMMap):
@@ -516,3 +517,19 @@ class DiagTrajectoryGVGMMMap(TrajectoryGVGMMMap):
     the switch back); a TrajectoryGVGMMMap over the same converter keeps refusing while the precision is "diag"."""
 
     _create = staticmethod(_lib.lib.vcmi_trajgv_create_diag)
+
+
+class BlockDiagTrajectoryGVGMMMap(DiagTrajectoryGVGMMMap):
+    """BlockDiagTrajectoryGVGMMMap(tgmm, mu^v, Sigma^vv): the global-variance conversion over a BlockDiagTrajectoryGMMMap
+    (TypeError for any other tgmm), through an entry of its own (include/vcmi.h: vcmi_trajgv_create_bdiag).  Two windows: a
+    DiagTrajectoryGVGMMMap bit for bit.  windows=3, which DiagTrajectoryGVGMMMap keeps refusing: the likelihood gradient is the
+    five-point stencil of the pentadiagonal system the converter solves, a Jacobi step per epoch (csrc/traj_gv_penta.hip).
+    fvconvert and fvconvert_batch take X (3D,T); vc takes fm (3D+1,T), host matrix or device tensor, with or without a
+    postfilter.  delta=True and vc_batch over three windows stay refused (VCMIError naming three windows)."""
+
+    _create = staticmethod(_lib.lib.vcmi_trajgv_create_bdiag)
+
+    def __init__(self, tgmm, muv, sigmavv):
+        if not isinstance(tgmm, BlockDiagTrajectoryGMMMap):
+            raise TypeError(f"BlockDiagTrajectoryGVGMMMap: tgmm must be a BlockDiagTrajectoryGMMMap, not a {type(tgmm).__name__}")
+        super().__init__(tgmm, muv, sigmavv)
