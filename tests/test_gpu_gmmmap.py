@@ -1,6 +1,7 @@
 """GPU parity: GMMMap fvconvert / predict_proba / predict / vc through the C-ABI vs the CPU oracle and the
 committed golden vectors.  Tolerance: north_star asks <= 1e-5 relative on converted mel-cepstra; the FP64
-kernels are held to 1e-9 here (observed ~1e-12)."""
+kernels are held to 1e-9 here (observed ~1e-12).  Frames with shared posteriors, relative posterior bounds and derived
+bounds on every kernel path: tests/test_gpu_gmmmap_shared.py."""
 import numpy as np
 import pytest
 

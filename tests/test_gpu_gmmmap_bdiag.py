@@ -84,6 +84,37 @@ def test_parity_with_the_oracle_on_the_expanded_model(vc, D, M, T, swap):
     assert np.array_equal(host(vc.predict_proba(g.px, Xd)), P) and np.array_equal(host(vc.predict(g.px, Xd)), idx)
 
 
+# ------------------------------------------------------------------------------------------- posteriors, relatively
+@pytest.mark.parametrize("D,M", [(40, 7), (128, 256)])
+def test_ladder_posteriors_are_the_weights(vc, D, M):
+    """Mixtures with bit-identical source means and variances and weights proportional to exp(-(47, 0, 1, 20, 45, 300, 700))
+    (repeated up to M): the posterior of every frame is the normalised weight vector itself, from 0.73 / repeats down to
+    7e-305 / repeats, and is held RELATIVELY: |P / w - 1| <= B_tm + max_k B_tk + (M + 16) eps with the log-density bound of
+    tests/gmmmap_bdiag_restatement.py.  (40, 7) runs the kernel's 64-frame tiles, (128, 256) its 32-frame ones."""
+    T = 70
+    gaps = np.array(([47.0, 0.0, 1.0, 20.0, 45.0, 300.0, 700.0] * (-(-M // 7)))[:M])
+    _, mu1, cov1 = eb.bdiag_model(9100 + D, 2 * D, 1)
+    rng = np.random.default_rng(9101 + D)
+    w = np.exp(-gaps) / np.exp(-gaps).sum()
+    mu, cov = np.asfortranarray(np.repeat(mu1, M, axis=1)), np.asfortranarray(np.repeat(cov1, M, axis=1))
+    s = rng.uniform(1.0, 1.3, M)
+    mu[D:] += rng.standard_normal((D, M))
+    cov[D:2 * D] *= s * s                                  # target variances and cross terms scaled: the pair stays positive definite
+    cov[2 * D:] *= s
+    assert all(mu[:D, m].tobytes() == mu[:D, 0].tobytes() and cov[:D, m].tobytes() == cov[:D, 0].tobytes() for m in range(M))
+    X = np.ascontiguousarray(eb.draw(9102 + D, w, mu, cov, T)[:, :D])
+    B = rs.logdens_bound(X, w, mu, cov)
+    R = B + B.max(axis=1, keepdims=True) + (M + 16) * rs.EPS
+    wl = np.asarray(w, dtype=rs.LD)
+    g = vc.BlockDiagGMMMap(w, mu, cov)
+    P = vc.predict_proba(g.px, np.asfortranarray(X.T)).T
+    assert np.all(P > 0) and P.min() < 1e-300
+    f = np.abs(np.log(P.astype(rs.LD) / (wl / wl.sum()))) / R
+    print(f"D={D} M={M}: largest relative posterior error / bound {float(f.max()):.3g}, bounds {R.min():.2e} ... {R.max():.2e}")
+    assert np.all(f <= 1.0), float(f.max())
+    assert np.array_equal(host(vc.predict_proba(g.px, dev(X))).T, P)
+
+
 # ------------------------------------------------------------------------------------ where an expanded form cancels
 def test_centred_log_density_where_the_expanded_form_cancels(vc):
     """Fractions of the bounds used, measured on an MI355X: see the printed line (posterior and y against the longdouble

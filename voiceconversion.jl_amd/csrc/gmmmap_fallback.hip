@@ -258,7 +258,7 @@ logdens_tiled_kernel(const double *__restrict__ U, const double *__restrict__ cz
 // Lanes ACROSS the mixtures of a frame (8, 16, 32 or 64 of them: several frames per wave where M is small), so that a wave
 // reads whole rows of the (T,M) matrix.  (Round 5: one lane per frame walked its row three times with a stride of M doubles
 // between the lanes -- 1.47 ms for 5e5 x 64, fifteen times what the bytes take; tools/efficiency_sweep.py posterior.)
-// Follows src/gmm.jl:28-29 (max-shifted log-sum-exp, exp(l - lse)) and :46 (the FIRST maximum: ties go to the smaller index).
+// Follows src/gmm.jl:28-29 (max-shifted log-sum-exp; exp(l - lse) evaluated as exp(l - max) / sum) and :46 (the FIRST maximum: ties go to the smaller index).
 // ------------------------------------------------------------------------------------------------
 template <int MODE>
 __global__ void __launch_bounds__(256)
@@ -297,9 +297,11 @@ posterior_finish_kernel(double *__restrict__ LP, int M, int64_t T, int64_t *__re
     double s = 0.0;
     for (int m = sl; m < M; m += lpf) s += vc_exp(l[m] - u);
     for (int o = lpf / 2; o >= 1; o >>= 1) s += __shfl_xor(s, o);
-    const double lse = u + log(s);
+    // exp(l - u) / s, not exp(l - (u + log s)): rounding lse = u + log s puts a common relative error of up to |lse| eps on every
+    // posterior of the frame (rows of a 160-dimensional model summed to 1 within 58 eps only), the quotient one of 2 eps
+    const double inv = 1.0 / s;
     if (live)
-      for (int m = sl; m < M; m += lpf) l[m] = vc_exp(l[m] - lse);
+      for (int m = sl; m < M; m += lpf) l[m] = vc_exp(l[m] - u) * inv;
   }
 }
 static inline unsigned posterior_finish_grid(int M, int64_t T) {
