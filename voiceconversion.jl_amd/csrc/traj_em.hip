@@ -61,8 +61,14 @@ traj_em_logprior_kernel(double *__restrict__ LP, int M, int64_t nframes) {
   for (int m = 0; m < M; ++m) l[m] -= lse;
 }
 
-// l_{m,.} of one frame (written by the calling thread itself) -> gamma, lse, flag.  A frame is PURE when 1 - max gamma < 2^-53:
-// it takes that mixture alone (gamma written one-hot, flag = its index); otherwise MIXED (flag -1).
+// l_{m,.} of one frame (written by the calling thread itself) -> gamma, lse, flag.  A frame is PURE when the COMPUTED
+// 1 - exp(mx - lse) is below 2^-53: it takes that mixture alone (gamma written one-hot, flag = its index); otherwise MIXED
+// (flag -1).  That is not "1 - max gamma < 2^-53": with r = sum_{m != best} exp(l_m - l_best) the weight dropped is r / (1 + r),
+// but lse = mx + log(s) absorbs log(s) = log1p(r) as soon as it is below half an ulp of mx, and then exp(mx - lse) is exactly 1.
+// So the line sits at r of about max(1, |l_best|) 2^-53 (up to 2^-52 |l_best| where |l_best| is just above a power of two), not at
+// 2^-53: a frame is certainly mixed from r = 8 max(1, |l_best|) 2^-53 on and certainly pure up to r = 2^-56, either in between
+// -- the dropped weight is then at most 8 |l_best| 2^-53, which the solver's operands do not see.  Pinned by
+// tests/test_gpu_traj_em_terms.py::test_decision_line (band derived in tests/traj_em_restatement.py, "THE FLAG BAND").
 __device__ __forceinline__ void em_finish_frame(double *__restrict__ gl, int M, double *__restrict__ lse_out, int *__restrict__ pure_out) {
   double mx = -INFINITY;
   int mi = 0;
@@ -370,12 +376,14 @@ traj_em_scan_kernel(const TrajUtt *__restrict__ utts, int nu, int M, const int *
 }
 
 // Qbar of the mixed frames: [16 frames x M] . [M x E] on v_mfma_f64_16x16x4, E = (2 Ds)^2 elements of the table the solver
-// reads (Q, or Qpad: sum gamma = 1 keeps the padding's unit diagonal).  A operand: gamma of the tile's 16 frames, four
-// mixtures per k-step; B operand: 16 consecutive elements of those four matrices.  grid (mixed tiles, element chunks), a wave
-// per 16-element column block.  2 M E flop, E doubles written per frame.
+// reads (Q, or Qpad).  A operand: gamma of the tile's 16 frames, four mixtures per k-step; B operand: 16 consecutive elements
+// of those four matrices.  grid (mixed tiles, element chunks), a wave per 16-element column block.  2 M E flop, E doubles
+// written per frame.  Dp != 0: the table is Qpad, (2 Dp)^2 elements with static dimension D padded to Dp; the padding's unit
+// diagonal is written as 1 -- the computed sum of gamma is 1 only to a few ulp (tests/test_gpu_traj_em_terms.py found
+// 1 - 1.8e-15 there), and the padded solver's operands should not depend on the posteriors.
 __global__ void __launch_bounds__(256)
 traj_em_blend_kernel(const double *__restrict__ Qtab, int M, int64_t E, const double *__restrict__ gam_all,
-                     const int *__restrict__ mix, int count, double *__restrict__ out) {
+                     const int *__restrict__ mix, int count, double *__restrict__ out, int D, int Dp) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, lcol = lane & 15, lgrp = lane >> 4;
   const int64_t k0 = (int64_t)blockIdx.x * 16;
   const int fr = (k0 + lcol < count) ? mix[k0 + lcol] : -1;
@@ -391,10 +399,12 @@ traj_em_blend_kernel(const double *__restrict__ Qtab, int M, int64_t E, const do
       const double b = (m < M && el < E) ? Qtab[(size_t)m * E + el] : 0.0;
       acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, acc, 0, 0, 0);
     }
+    const int64_t row = Dp ? el / (2 * Dp) : 0;
+    const bool unit = Dp && row >= D && row < Dp && el == row * (2 * Dp) + row;
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int64_t k = k0 + lgrp + 4 * r;
-      if (k < count && el < E) out[(size_t)k * E + el] = acc[r];
+      if (k < count && el < E) out[(size_t)k * E + el] = unit ? 1.0 : acc[r];
     }
   }
 }
@@ -449,6 +459,37 @@ static int traj_em_estep(vcmi_traj *t, const TrajUtt *du, int nu, int Tmax, int6
   return VCMI_OK;
 }
 
+// Flag scan of the (uploaded) utterances du[0 .. nu), fs frames in all: em_mh, em_mix and the mixed-frame count, which is read
+// back (the 4-byte read that synchronises st).  nframes: the frames of the call, behind which em_mix keeps the count.
+static int traj_em_scan(vcmi_traj *t, const TrajUtt *du, int nu, int64_t nframes, int64_t fs, hipStream_t st, int *count) {
+  int *dcount = t->em_mix.p + nframes;
+  hipLaunchKernelGGL(traj_em_scan_kernel, dim3(1), dim3(1024), 0, st, du, nu, t->M, t->em_pure.p, t->em_mh.p, t->em_mix.p, dcount);
+  VCMI_HIP(hipGetLastError());
+  *count = 0;
+  VCMI_HIP(hipMemcpyAsync(count, dcount, sizeof(int), hipMemcpyDeviceToHost, st));
+  VCMI_HIP(hipStreamSynchronize(st));
+  if (*count < 0 || *count > fs)
+    return fail(VCMI_ERR_HIP, "TrajectoryGMMMap: EM flag scan returned %d mixed frames of %lld", *count, (long long)fs);
+  return VCMI_OK;
+}
+
+// em_table = [the M matrices of the table the solver reads | Qbar of the count mixed frames]: t->Qpad in t->Dpad when padded,
+// else t->Q
+static int traj_em_blend(vcmi_traj *t, bool padded, int count, hipStream_t st) {
+  const int M = t->M, Ds = padded ? t->Dpad : t->D;
+  const int64_t E = (int64_t)4 * Ds * Ds;
+  const double *Qsrc = padded ? t->Qpad.p : t->Q.p;
+  VCMI_TRY(t->em_table.reserve((size_t)(M + count) * (size_t)E));
+  VCMI_HIP(hipMemcpyAsync(t->em_table.p, Qsrc, sizeof(double) * (size_t)M * (size_t)E, hipMemcpyDeviceToDevice, st));
+  if (count > 0) {
+    const unsigned chunks = (unsigned)std::min<int64_t>(((E + 15) / 16 + 3) / 4, 8);
+    hipLaunchKernelGGL(traj_em_blend_kernel, dim3((unsigned)((count + 15) / 16), chunks), dim3(256), 0, st, Qsrc, M, E, t->em_gamma.p,
+                       t->em_mix.p, count, t->em_table.p + (size_t)M * (size_t)E, t->D, padded ? t->Dpad : 0);
+    VCMI_HIP(hipGetLastError());
+  }
+  return VCMI_OK;
+}
+
 // em_iters E/M pairs after the arg-max solve of traj_run.  The table is sized by the mixed-frame count, one 4-byte read per
 // iteration (the only host synchronisation of the loop); the batch (sorted, uploaded at du) starts as ONE slice and is cut into
 // slices of whole utterances only where that count would take the table past kTrajEmTableCapBytes.
@@ -461,7 +502,6 @@ int traj_em_run(vcmi_traj *t, const std::vector<TrajUtt> &utts, const TrajSolveP
   if (nframes > INT32_MAX) return fail(VCMI_ERR_DIM, "TrajectoryGMMMap: too many frames in one call for EM");
   const int M = t->M, iters = t->em_iters;
   const int64_t E = (int64_t)4 * plan.Ds * plan.Ds;
-  const double *Qsrc = plan.padded ? t->Qpad.p : t->Q.p;
   VCMI_TRY(traj_em_prior(t, utts, nframes, contiguous, dX0, st));
   VCMI_TRY(t->em_mh.reserve((size_t)nframes));
   VCMI_TRY(t->em_mix.reserve((size_t)nframes + 1));
@@ -493,13 +533,8 @@ int traj_em_run(vcmi_traj *t, const std::vector<TrajUtt> &utts, const TrajSolveP
       VCMI_TRY(traj_em_estep(t, du + b0, nb, Tmax, nframes, true, st, t->em_time ? ev[1] : nullptr));
       if (t->em_time) VCMI_HIP(hipEventRecord(ev[2], st));
       hipLaunchKernelGGL(traj_em_sum_kernel, dim3((unsigned)nb), dim3(256), 0, st, du + b0, t->em_lse.p, t->em_L.p + (size_t)it * n);
-      int *dcount = t->em_mix.p + nframes;
-      hipLaunchKernelGGL(traj_em_scan_kernel, dim3(1), dim3(1024), 0, st, du + b0, nb, M, t->em_pure.p, t->em_mh.p, t->em_mix.p, dcount);
-      VCMI_HIP(hipGetLastError());
       int count = 0;
-      VCMI_HIP(hipMemcpyAsync(&count, dcount, sizeof(int), hipMemcpyDeviceToHost, st));
-      VCMI_HIP(hipStreamSynchronize(st));
-      if (count < 0 || count > fs) return fail(VCMI_ERR_HIP, "TrajectoryGMMMap: EM flag scan returned %d mixed frames of %lld", count, (long long)fs);
+      VCMI_TRY(traj_em_scan(t, du + b0, nb, nframes, fs, st, &count));
       const size_t table = (size_t)(M + count) * (size_t)E;
       if (table * sizeof(double) > cap && nb > 1) {
         int h = 0;
@@ -508,14 +543,7 @@ int traj_em_run(vcmi_traj *t, const std::vector<TrajUtt> &utts, const TrajSolveP
         VCMI_TRY(run_slice(b0, h, it));
         return run_slice(b0 + h, nb - h, it);
       }
-      VCMI_TRY(t->em_table.reserve(table));
-      VCMI_HIP(hipMemcpyAsync(t->em_table.p, Qsrc, sizeof(double) * (size_t)M * (size_t)E, hipMemcpyDeviceToDevice, st));
-      if (count > 0) {
-        const unsigned chunks = (unsigned)std::min<int64_t>(((E + 15) / 16 + 3) / 4, 8);
-        hipLaunchKernelGGL(traj_em_blend_kernel, dim3((unsigned)((count + 15) / 16), chunks), dim3(256), 0, st, Qsrc, M, E, t->em_gamma.p,
-                           t->em_mix.p, count, t->em_table.p + (size_t)M * (size_t)E);
-        VCMI_HIP(hipGetLastError());
-      }
+      VCMI_TRY(traj_em_blend(t, plan.padded, count, st));
       if (t->em_time) VCMI_HIP(hipEventRecord(ev[3], st));
       VCMI_TRY(traj_solve_launch(t, plan, t->em_table.p, t->em_mh.p, b0, nb, st));
       if (t->em_time) {
@@ -607,6 +635,58 @@ extern "C" int vcmi_debug_traj_em_times(vcmi_traj *t, int enable, double *out) {
 extern "C" int vcmi_debug_traj_em_cap(vcmi_traj *t, size_t bytes) {
   if (!t) return fail(VCMI_ERR_ARG, "vcmi_debug_traj_em_cap: NULL handle");
   t->em_cap_bytes = bytes;
+  return VCMI_OK;
+}
+
+// Test hook (not part of include/vcmi.h; tests/test_gpu_traj_em_terms.py): what one iteration of the loop hands its solver, for
+// one utterance at a caller-given y.  Host pointers X (2D,T), Y (D,T) -> gamma (M,T), lse (T), flag (T; the mixture of a pure
+// frame, -1 for a mixed one), gbar (2D,T), mh (T; table index + 1), *count mixed frames and their blended matrices table
+// (count of them, room for T; E = (2D)^2 elements each from t->Q, or with pad != 0 (2 Dpad)^2 from t->Qpad: the operands of the
+// padded blocked solver).  Runs traj_em_prior, traj_em_estep (which honours DBG_TRAJ_G_SCALAR), traj_em_scan, traj_em_blend; the
+// EM scratch follows traj_em_release's rule on every return.
+extern "C" int vcmi_debug_traj_em_estep(vcmi_traj *t, const double *X, const double *Y, int64_t T, int pad, double *gamma, double *lse,
+                                        int32_t *flag, double *gbar, int64_t *mh, int32_t *count, double *table) {
+  if (!t || !count) return fail(VCMI_ERR_ARG, "vcmi_debug_traj_em_estep: NULL argument");
+  if (t->b) return fail(VCMI_ERR_ARG, "vcmi_debug_traj_em_estep: the converter was made from a cross-diagonal model (vcmi_traj_create_bdiag)");
+  if (t->precision == VCMI_TRAJ_PRECISION_DIAG)
+    return fail(VCMI_ERR_ARG, "vcmi_debug_traj_em_estep: the converter has diagonal conditional precisions (vcmi_traj_set_precision)");
+  if (!t->em_pd) return fail(VCMI_ERR_NOT_PD, "vcmi_debug_traj_em_estep: (Q_m + Q_m')/2 of some mixture is not positive definite");
+  if (pad && !t->Dpad) return fail(VCMI_ERR_ARG, "vcmi_debug_traj_em_estep: the converter has no padded dimension");
+  if (T < 0 || T > INT32_MAX - 1 || (T > 0 && (!X || !Y || !gamma || !lse || !flag || !gbar || !mh || !table)))
+    return fail(VCMI_ERR_ARG, "vcmi_debug_traj_em_estep: bad argument");
+  *count = 0;
+  if (T == 0) return VCMI_OK;
+  const int D2 = t->D2, M = t->M, Ds = pad ? t->Dpad : t->D;
+  const int64_t E = (int64_t)4 * Ds * Ds;
+  const size_t nx = (size_t)T * D2;
+  hipStream_t st = nullptr;
+  TrajEmRelease release{t};                 // the scratch rule on every way out, error returns included
+  VCMI_TRY(t->xbuf.reserve(nx));
+  VCMI_TRY(t->ybuf.reserve((size_t)T * t->D));
+  VCMI_TRY(t->gbuf.reserve(nx));
+  VCMI_TRY(t->uttbuf.reserve(sizeof(TrajUtt)));
+  VCMI_TRY(t->em_mh.reserve((size_t)T));
+  VCMI_TRY(t->em_mix.reserve((size_t)T + 1));
+  VCMI_HIP(hipStreamSynchronize(st));       // (the buffers are shared with the conversion calls)
+  VCMI_TRY(upload_now(t->xbuf.p, X, sizeof(double) * nx));
+  VCMI_TRY(upload_now(t->ybuf.p, Y, sizeof(double) * T * t->D));
+  std::vector<TrajUtt> utts(1, TrajUtt{t->xbuf.p, t->ybuf.p, 0, (int32_t)T, 0});
+  VCMI_TRY(upload_now(t->uttbuf.p, utts.data(), sizeof(TrajUtt)));
+  const TrajUtt *du = reinterpret_cast<const TrajUtt *>(t->uttbuf.p);
+  VCMI_TRY(traj_em_prior(t, utts, T, true, t->xbuf.p, st));
+  VCMI_TRY(traj_em_estep(t, du, 1, (int)T, T, true, st));
+  int n = 0;
+  VCMI_TRY(traj_em_scan(t, du, 1, T, T, st, &n));
+  VCMI_TRY(traj_em_blend(t, pad != 0, n, st));
+  VCMI_HIP(hipStreamSynchronize(st));
+  VCMI_HIP(hipMemcpy(gamma, t->em_gamma.p, sizeof(double) * (size_t)T * M, hipMemcpyDeviceToHost));
+  VCMI_HIP(hipMemcpy(lse, t->em_lse.p, sizeof(double) * (size_t)T, hipMemcpyDeviceToHost));
+  VCMI_HIP(hipMemcpy(flag, t->em_pure.p, sizeof(int32_t) * (size_t)T, hipMemcpyDeviceToHost));
+  VCMI_HIP(hipMemcpy(gbar, t->gbuf.p, sizeof(double) * nx, hipMemcpyDeviceToHost));
+  VCMI_HIP(hipMemcpy(mh, t->em_mh.p, sizeof(int64_t) * (size_t)T, hipMemcpyDeviceToHost));
+  if (n > 0)
+    VCMI_HIP(hipMemcpy(table, t->em_table.p + (size_t)M * (size_t)E, sizeof(double) * (size_t)n * (size_t)E, hipMemcpyDeviceToHost));
+  *count = n;
   return VCMI_OK;
 }
 
