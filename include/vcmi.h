@@ -623,10 +623,10 @@ int vcmi_trajgv_create(vcmi_traj *t, const double *muv, const double *sigmavv, v
  * entry returns VCMI_ERR_ARG before anything runs, and the handle is usable again after the switch back.  A handle of
  * vcmi_trajgv_create over the same t keeps refusing while t is DIAG.
  * With D^-1 = diag(q) the likelihood gradient is a three-point stencil per static dimension, (P y)_t = c0_t y_t +
- * c2_t y_{t-2} + c2_{t+2} y_{t+2} (csrc/traj_gv_diag.hip): O(T D) per epoch, a Jacobi step on two y buffers.  traj_gvd_kernel
+ * c2_t y_{t-2} + c2_{t+2} y_{t+2} (csrc/traj_gv_band.hip): O(T D) per epoch, a Jacobi step on two y buffers.  traj_gvd_kernel
  * runs one workgroup per utterance with all epochs inside; as many of its five (T,D) arrays (y, second y, c2, c0, r) as fit
  * the 160 KB of LDS stay there across the epochs, chosen from D and the longest utterance of the call
- * (csrc/traj_gvd_plan.hpp), the rest is streamed: every T >= 2 converts.  An utterance's result does not depend on the batch
+ * (csrc/traj_band_plan.hpp), the rest is streamed: every T >= 2 converts.  An utterance's result does not depend on the batch
  * it came in.  Scratch on the trajectory handle: 5 D N doubles for the N frames of a call (the solver's D N and four more).
  * D > 512: VCMI_ERR_ARG.  Device groups: an ordinary DIAG converter shards as vcmi_trajgv_create's does; one of
  * vcmi_traj_create_bdiag converts on its own device. */
@@ -636,10 +636,10 @@ int vcmi_trajgv_create_diag(vcmi_traj *t, const double *muv, const double *sigma
  * Sigma^vv: VCMI_ERR_NOT_PD).  Two windows: the handle is the one vcmi_trajgv_create_diag makes, every result bit for bit that
  * one's.  Three windows (vcmi_traj_create_bdiag_windows(b, T, 3), which vcmi_trajgv_create_diag keeps refusing): the likelihood
  * gradient is the five-point stencil of the pentadiagonal system the solver factorises,
- *   (P y)_t = c0_t y_t + c1_t y_{t-1} + c1_{t+1} y_{t+1} + c2_t y_{t-2} + c2_{t+2} y_{t+2}      (csrc/traj_gvp_step.hpp),
- * a Jacobi step on two y buffers in traj_gvp_kernel (csrc/traj_gv_penta.hip): one workgroup per utterance with all epochs
+ *   (P y)_t = c0_t y_t + c1_t y_{t-1} + c1_{t+1} y_{t+1} + c2_t y_{t-2} + c2_{t+2} y_{t+2}      (csrc/traj_gv_band_step.hpp),
+ * a Jacobi step on two y buffers in traj_gvp_kernel (csrc/traj_gv_band.hip): one workgroup per utterance with all epochs
  * inside; as many of its six (T,D) arrays (y, second y, c1, c2, c0, r) as fit the 160 KB of LDS stay there across the epochs,
- * chosen from D and the longest utterance of the call (csrc/traj_gvp_plan.hpp), the rest is streamed: every T >= 2 converts, and
+ * chosen from D and the longest utterance of the call (csrc/traj_band_plan.hpp), the rest is streamed: every T >= 2 converts, and
  * an utterance's result does not depend on the batch it came in.  Scratch on the trajectory handle: 5 D N doubles for the N
  * frames of a call, the first two on the solver's l1 and l2 (dead once the solve has run).  The three-window handle goes to
  * vcmi_trajgv_convert, _batch, _batch_dev (X (3D,T)) and to vcmi_vc_trajgv / vcmi_vc_trajgv_dev with is_static = 0 (fm (3D+1,T)),

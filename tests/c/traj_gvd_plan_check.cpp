@@ -1,12 +1,12 @@
 // traj_gvd_plan_check.cpp -- the launch rule of traj_gvd_kernel and the workspace arithmetic of a GV call over diagonal conditional
-// precisions (csrc/traj_gvd_plan.hpp: host arithmetic, no HIP) on the CPU.  Asserts the rule's invariants over every static
+// precisions (csrc/traj_band_plan.hpp: host arithmetic, no HIP) on the CPU.  Asserts the rule's invariants over every static
 // dimension the kernel takes and utterance lengths up to 2^31 - 1, exact values at the shapes DESIGN 3.5-DIAG names, and prints
 // "rule D T resident lds_bytes" lines, which tests/test_traj_gvd_plan_host.py compares with the rule as Python restates it
 // (tests/gv_diag_restatement.py: gvd_resident).  Built by that test with -fsanitize=address,undefined.
 #include <cstdio>
 #include <cstdint>
 
-#include "../../voiceconversion.jl_amd/csrc/traj_gvd_plan.hpp"
+#include "../../voiceconversion.jl_amd/csrc/traj_band_plan.hpp"
 
 using namespace vcmi;
 

@@ -1,9 +1,12 @@
-// traj_gvp_check.cpp -- the per-element arithmetic of the GV ascent over three windows (csrc/traj_gvp_step.hpp, the header the
-// kernel of csrc/traj_gv_penta.hip is made of, compiled here for the HOST) and its launch rule (csrc/traj_gvp_plan.hpp) on the CPU.
+// traj_gvp_check.cpp -- the per-element arithmetic of the GV ascents over diagonal conditional precisions (csrc/traj_gv_band_step.hpp,
+// the header the kernels of csrc/traj_gv_band.hip are made of, compiled here for the HOST) and the launch rule of the three-window
+// one (csrc/traj_band_plan.hpp) on the CPU.
 //   1. Chains of T = 2, 3, 4, 5, 50, 2000 frames, precisions spread over five decades: the coefficients and a run of Jacobi epochs
 //      driven as the kernel drives them (neighbour rows and neighbour y from addresses clamped into the utterance, two y buffers)
 //      against a long-double evaluation of the assembled pentadiagonal P and r at the chain's own y_n, element by element within
 //      K 2^-53 (|y| + |y'| + alpha (omega (r_abs + |P||y|) + |coef||y - mean|)), K = 16: eleven terms in r - P y, the update.
+//   1b. The same chains through the two-window step (gvd_coefficients, gvd_epoch_step) against the assembled tridiagonal-in-
+//      parity P and r, within the same bar with K = 8 (chains2 says how the roundings are counted).
 //   2. The rule's invariants: never above the LDS limit, monotone in T, fewer than two arrays resident means none, the workspace
 //      covers the five arrays the kernel writes for every utterance of a call and lies on l1 / l2 without exceeding the reserve;
 //      and the table of (D, T, resident) lines that tests/test_gv_penta_restatement_host.py compares with the Python restatement.
@@ -14,8 +17,8 @@
 #include <random>
 #include <vector>
 
-#include "../../voiceconversion.jl_amd/csrc/traj_gvp_plan.hpp"
-#include "../../voiceconversion.jl_amd/csrc/traj_gvp_step.hpp"
+#include "../../voiceconversion.jl_amd/csrc/traj_band_plan.hpp"
+#include "../../voiceconversion.jl_amd/csrc/traj_gv_band_step.hpp"
 
 using namespace vcmi;
 typedef long double ld;
@@ -108,6 +111,84 @@ static void chains() {
   }
 }
 
+// The two-window step, driven as traj_gvd_kernel drives it.  The bar is that of chains() with K counted for this stencil, to
+// first order in u = 2^-53, every rounding relative to a sum of magnitudes that the bar holds (multiplications by 0.25 and 0.5
+// are exact, so c2 is exact; omega, coef, mean and alpha are the same doubles on both sides):
+//   r        2 additions                                              2 u r_abs
+//   P y      c0: 2 additions; c0 y; the two fma                       5 u |P||y|
+//   r - P y  1 subtraction                     -> at most 6 u (r_abs + |P||y|)
+//   omega .  1 multiplication                  -> 7 u omega (r_abs + |P||y|)
+//   y - mean 1 subtraction, then the fma       -> 8 u omega (r_abs + |P||y|) + 2 u |coef| (|y| + |mean|)
+//   the last fma                               -> + u |y'|
+// so K = 8 (the three-window step has 5 roundings in r, 10 in P y and the same 3 behind them: 13, hence its 16).  The stored
+// coefficients: c0 and r within 3 u of their magnitude sums (two roundings and the long-double sum's own), c2 exactly.
+static void chains2() {
+  static const int Ts[] = {2, 3, 4, 5, 50, 2000};
+  std::mt19937_64 rng(20240612);
+  std::uniform_real_distribution<double> u(0.0, 1.0);
+  std::normal_distribution<double> gauss(0.0, 1.0);
+  double worst = 0.0;
+  for (int T : Ts) {
+    for (int rep = 0; rep < 4; ++rep) {
+      std::vector<double> ps(T), pd(T), gs(T), gd(T);
+      const double ls = -2.0 + 3.0 * u(rng), ldl = -2.0 + 3.0 * u(rng);
+      for (int t = 0; t < T; ++t) {
+        ps[t] = std::pow(10.0, ls + 2.0 * u(rng));
+        pd[t] = std::pow(10.0, ldl + 2.0 * u(rng));
+        gs[t] = ps[t] * (std::sin(0.05 * t) + 0.3 * gauss(rng));
+        gd[t] = pd[t] * 0.1 * gauss(rng);
+      }
+      // the prologue: p_d and g_d of frames t-1 and t+1 from clamped addresses
+      std::vector<double> c0(T), c2(T), r(T);
+      std::vector<ld> L0(T), L2(T, 0.0L), Lr(T), Lra(T);
+      for (int t = 0; t < T; ++t) {
+        const int tm = t >= 1 ? t - 1 : t, tp = t + 1 < T ? t + 1 : t;
+        const GvdCoef k = gvd_coefficients(ps[t], pd[tm], pd[tp], gs[t], gd[tm], gd[tp], t, T);
+        c0[t] = k.c0, c2[t] = k.c2, r[t] = k.r;
+        ld d = (ld)ps[t], v = (ld)gs[t], va = fabsl((ld)gs[t]);
+        if (t >= 1) {
+          d += 0.25L * pd[t - 1];
+          v += 0.5L * gd[t - 1];
+          va += 0.5L * fabsl((ld)gd[t - 1]);
+          if (t >= 2) L2[t] = -0.25L * pd[t - 1];
+        }
+        if (t + 1 < T) {
+          d += 0.25L * pd[t + 1];
+          v -= 0.5L * gd[t + 1];
+          va += 0.5L * fabsl((ld)gd[t + 1]);
+        }
+        L0[t] = d, Lr[t] = v, Lra[t] = va;
+        CHECK(fabsl((ld)k.c0 - d) <= 3 * kEps * d && fabsl((ld)k.r - v) <= 3 * kEps * va);
+        CHECK((ld)k.c2 == L2[t] && (t >= 2 || k.c2 == 0.0));
+      }
+      // epochs: Jacobi on two buffers, every load on a clamped address
+      const double omega = 1.0 / (2.0 * T), alpha = 0.3 / (double)(L0[0] * omega), coef = -0.01 * (double)L0[0] * omega;
+      std::vector<double> y(T), yn(T);
+      for (int t = 0; t < T; ++t) y[t] = std::sin(0.05 * t) + 0.3 * gauss(rng);
+      for (int ep = 0; ep < 5; ++ep) {
+        double mean = 0.0;
+        for (int t = 0; t < T; ++t) mean += y[t];
+        mean /= T;
+        for (int t = 0; t < T; ++t) {
+          const int t2m = t >= 2 ? t - 2 : t, t2p = t + 2 < T ? t + 2 : t;
+          yn[t] = gvd_epoch_step(y[t], y[t2m], y[t2p], c0[t], c2[t], c2[t2p], r[t], t, T, omega, coef, mean, alpha);
+          ld py = L0[t] * y[t], pa = L0[t] * fabsl((ld)y[t]);
+          if (t >= 2) py += L2[t] * y[t - 2], pa += fabsl(L2[t] * y[t - 2]);
+          if (t + 2 < T) py += L2[t + 2] * y[t + 2], pa += fabsl(L2[t + 2] * y[t + 2]);
+          const ld ref = (ld)y[t] + (ld)alpha * ((ld)omega * (Lr[t] - py) + (ld)coef * ((ld)y[t] - (ld)mean));
+          const ld mag = fabsl((ld)y[t]) + fabsl(ref) +
+                         (ld)alpha * ((ld)omega * (Lra[t] + pa) + fabsl((ld)coef) * (fabsl((ld)y[t]) + fabsl((ld)mean)));
+          const double ratio = (double)(fabsl((ld)yn[t] - ref) / (8 * kEps * mag));
+          CHECK(std::isfinite(yn[t]) && ratio <= 1.0);
+          if (ratio > worst) worst = ratio;
+        }
+        y.swap(yn);
+      }
+      printf("two-window chain T %d rep %d: worst error / bar so far %.3e\n", T, rep, worst);
+    }
+  }
+}
+
 static void plan() {
   static const int64_t Ns[] = {0, 1, 2, 70, 1000, 512000, (int64_t)1 << 31};
   CHECK(kGvpArrays == 6 && kGvpWsArrays == 5);
@@ -147,6 +228,7 @@ static void plan() {
 
 int main() {
   chains();
+  chains2();
   plan();
   if (bad) {
     printf("traj_gvp_check: %d failures\n", bad);

@@ -1,6 +1,6 @@
 // traj_penta_check.cpp -- the pentadiagonal solver's per-step arithmetic (csrc/traj_penta_step.hpp, the header the kernel of
 // csrc/traj_penta.hip is made of, compiled here for the HOST: 1.0 / x in place of the hardware seed) and its workspace rule
-// (csrc/traj_penta_plan.hpp) on the CPU.
+// (csrc/traj_band_plan.hpp) on the CPU.
 //   1. Chains of T = 1, 2, 3, 4, 5, 50, 2000 frames, precisions spread over five decades: the forward and backward steps, driven
 //      as the kernel drives them (rows of frames past the end taken from the last frame, whole rings of six steps, nothing of a
 //      step past the end stored), against a long-double solve of the explicitly assembled matrix (Gaussian elimination on the
@@ -16,7 +16,7 @@
 #include <random>
 #include <vector>
 
-#include "../../voiceconversion.jl_amd/csrc/traj_penta_plan.hpp"
+#include "../../voiceconversion.jl_amd/csrc/traj_band_plan.hpp"
 #include "../../voiceconversion.jl_amd/csrc/traj_penta_step.hpp"
 
 using namespace vcmi;

@@ -1,5 +1,5 @@
 """numpy.longdouble restatement of ONE EPOCH of the global-variance ascent over DIAGONAL conditional precisions
-(DiagTrajectoryGVGMMMap, vcmi_trajgv_create_diag; csrc/traj_gv_diag.hip: traj_gvd_kernel) -- test infrastructure, numpy only.
+(DiagTrajectoryGVGMMMap, vcmi_trajgv_create_diag; csrc/traj_gv_band.hip: traj_gvd_kernel) -- test infrastructure, numpy only.
 
 Two statements of the same epoch  y <- y + alpha (lik + gv)(y):
 
@@ -50,7 +50,7 @@ MUTANTS = DENSE_MUTANTS + STENCIL_MUTANTS
 
 
 # ------------------------------------------------------------------------------------------------ launch rule
-# csrc/traj_gvd_plan.hpp, restated: of the kernel's five (T,D) arrays (y, second y, c2, c0, r) as many as fit 160 KB - 256 B of
+# csrc/traj_band_plan.hpp, restated: of the kernel's five (T,D) arrays (y, second y, c2, c0, r) as many as fit 160 KB - 256 B of
 # LDS beside the two reduction rows of 512 doubles and mean, var, coef stay resident; fewer than two: none (the streamed form)
 GVD_THREADS = 512
 LDS_LIMIT = 160 * 1024 - 256

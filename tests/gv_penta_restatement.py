@@ -1,6 +1,6 @@
 """numpy.longdouble restatement of ONE EPOCH of the global-variance ascent over a converter with THREE windows (static + delta +
 delta-delta): BlockDiagTrajectoryGVGMMMap over BlockDiagTrajectoryGMMMap(g, T, windows=3), vcmi_trajgv_create_bdiag;
-csrc/traj_gv_penta.hip: traj_gvp_kernel -- test infrastructure, numpy only.
+csrc/traj_gv_band.hip: traj_gvp_kernel -- test infrastructure, numpy only.
 
 Notation of tests/traj_penta_restatement.py: q[mhat_t] = [p_s ; p_d ; p_a], g_t = q[mhat_t] (.) E_t = [g_s ; g_d ; g_a].  Two
 statements of the same epoch  y <- y + alpha (lik + gv)(y),  lik = omega (W'D^-1E - W'D^-1W y),  omega = 1/(2T):
@@ -62,7 +62,7 @@ STENCIL_MUTANTS = ("gauss_seidel", "c1_wrong_neighbour", "c2_wrong_neighbour", "
 MUTANTS = DENSE_MUTANTS + STENCIL_MUTANTS
 
 # ------------------------------------------------------------------------------------------------ launch rule
-# csrc/traj_gvp_plan.hpp, restated: of the kernel's six (T,D) arrays (y, second y, c1, c2, c0, r) as many as fit 160 KB - 256 B of
+# csrc/traj_band_plan.hpp, restated: of the kernel's six (T,D) arrays (y, second y, c1, c2, c0, r) as many as fit 160 KB - 256 B of
 # LDS beside the two reduction rows of 512 doubles and mean, var, coef stay resident; fewer than two: none (the streamed form)
 GVP_THREADS = 512
 LDS_LIMIT = 160 * 1024 - 256

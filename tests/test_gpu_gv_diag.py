@@ -1,4 +1,4 @@
-"""GPU: DiagTrajectoryGVGMMMap -- the GV ascent over diagonal conditional precisions (csrc/traj_gv_diag.hip: traj_gvd_kernel), over
+"""GPU: DiagTrajectoryGVGMMMap -- the GV ascent over diagonal conditional precisions (csrc/traj_gv_band.hip: traj_gvd_kernel), over
 both converter kinds: a BlockDiagTrajectoryGMMMap ("bdiag") and a TrajectoryGMMMap(precision="diag") ("dense").
 
 The step check is tests/test_gpu_gv_steps.py's: for epoch counts n,

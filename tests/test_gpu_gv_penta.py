@@ -1,4 +1,4 @@
-"""GPU: BlockDiagTrajectoryGVGMMMap -- the GV ascent over a converter with three windows (csrc/traj_gv_penta.hip:
+"""GPU: BlockDiagTrajectoryGVGMMMap -- the GV ascent over a converter with three windows (csrc/traj_gv_band.hip:
 traj_gvp_kernel, behind the pentadiagonal solve), and the same class over two windows.
 
 The step check is tests/test_gpu_gv_diag.py's: for epoch counts n,

@@ -11,8 +11,8 @@ stencil) and shows that the inputs of tests/test_gpu_gv_penta.py can see a wrong
   sensitivity  every mutant of gv_penta_restatement.MUTANTS misses the unmutated step by >= 100 bars in some element of some
                checked step of every case (the mutants of the +-2 terms where the utterance has such terms: T >= 3);
   launch rule  the restated rule puts the cases into every form -- 6, 5, 4, 3, 2 resident arrays and streamed -- and equals
-               csrc/traj_gvp_plan.hpp at the edges (the table tests/c/traj_gvp_check.cpp prints);
-  C++          tests/c/traj_gvp_check.cpp: csrc/traj_gvp_step.hpp run on the CPU over chains against a long-double evaluation, and
+               csrc/traj_band_plan.hpp at the edges (the table tests/c/traj_gvp_check.cpp prints);
+  C++          tests/c/traj_gvp_check.cpp: csrc/traj_gv_band_step.hpp run on the CPU over chains against a long-double evaluation, and
                the invariants of the launch rule -- a stand-alone program under ASan + UBSan; nothing is loaded into Python.
 
 Everything here comes from numpy and the restatements: no number is taken from a run of the kernel."""
@@ -167,6 +167,8 @@ def test_step_header_and_launch_rule_under_asan_ubsan():
     assert "ERROR: AddressSanitizer" not in p.stderr and "runtime error" not in p.stderr, p.stderr[-4000:]
     chains = [line.split() for line in p.stdout.splitlines() if line.startswith("chain T ")]
     assert {int(c[2]) for c in chains} == {2, 3, 4, 5, 50, 2000}
+    chains2 = [line.split() for line in p.stdout.splitlines() if line.startswith("two-window chain T ")]     # gvd_epoch_step
+    assert {int(c[3]) for c in chains2} == {2, 3, 4, 5, 50, 2000}
     # the rule equals its Python restatement
     table = [line.split() for line in p.stdout.splitlines() if line.startswith("resident D ")]
     assert len(table) == 7 * 16 and {(12, T) for T in gp.EDGE_TS} <= {(int(t[2]), int(t[4])) for t in table}

@@ -1,5 +1,5 @@
 """CPU: the launch rule of traj_gvd_kernel and the workspace arithmetic of a GV call over diagonal conditional precisions
-(csrc/traj_gvd_plan.hpp, host arithmetic only).  tests/c/traj_gvd_plan_check.cpp is a stand-alone program that asserts the rule's
+(csrc/traj_band_plan.hpp, host arithmetic only).  tests/c/traj_gvd_plan_check.cpp is a stand-alone program that asserts the rule's
 invariants for every static dimension up to 512 and prints the rule at a grid of shapes; here it is built with ASan + UBSan like
 tests/test_traj_diag_host.py's, run, and its table compared with the rule as tests/gv_diag_restatement.py restates it."""
 import os

@@ -3,7 +3,7 @@
      agree within the tolerance on every shape of the GPU tests, and the preconditions of those tests hold on the actual inputs:
      every q > 0 and no frame's arg-max within rounding of a tie.
   2. tests/c/traj_penta_check.cpp: the solver's per-step header (csrc/traj_penta_step.hpp) run on the CPU over chains of
-     T = 1 .. 2000 against a long-double solve, and the invariants of csrc/traj_penta_plan.hpp -- a stand-alone program under
+     T = 1 .. 2000 against a long-double solve, and the invariants of csrc/traj_band_plan.hpp -- a stand-alone program under
      ASan + UBSan, built like tests/test_traj_bdiag_host.py builds its check; nothing is loaded into Python.
   3. push_delta(order=2) and constructW(D, T, windows=3) on the host path against the restatement.
   4. The argument errors that are raised before a device is touched."""

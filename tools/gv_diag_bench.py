@@ -1,4 +1,4 @@
-"""DiagTrajectoryGVGMMMap (the GV ascent over diagonal conditional precisions, csrc/traj_gv_diag.hip) over a
+"""DiagTrajectoryGVGMMMap (the GV ascent over diagonal conditional precisions, csrc/traj_gv_band.hip) over a
 BlockDiagTrajectoryGMMMap, against the only way to GV with a cross-diagonal model before it: the detour
 TrajectoryGVGMMMap(TrajectoryGMMMap(GMMMap(w, mu, expand_block_diag(covars)), T), mu_v, Sigma_vv).  Device-resident.
 
@@ -11,7 +11,7 @@ TrajectoryGVGMMMap(TrajectoryGMMMap(GMMMap(w, mu, expand_block_diag(covars)), T)
   kernels: with --kernels every (shape, path) runs once more in a child process under `rocprofv3 --kernel-trace --stats`
            (tracing only, no counters), a run of its own; the GV kernel's average duration is added, and for traj_gvd_kernel the
            bytes it moves per epoch in the streamed form (four (T,D) arrays read, one written) against --peak-tbs
-  form:    how many of the kernel's five arrays stay in LDS (csrc/traj_gvd_plan.hpp, restated here): 0 = streamed
+  form:    how many of the kernel's five arrays stay in LDS (csrc/traj_band_plan.hpp, restated here): 0 = streamed
   --root:  the tree whose package is imported (a checkout of another commit, with --only detour, measures the baseline there)
 
 Usage: python tools/gv_diag_bench.py [--shapes 40:256:2000,59:256:2000,40:5120:100] [--rounds 5] [--calls 5] [--kernels] [--out FILE]"""
@@ -35,7 +35,7 @@ PATHS = ("diag", "detour")
 
 
 def gvd_resident(D, Tmax):
-    """csrc/traj_gvd_plan.hpp: gvd_resident"""
+    """csrc/traj_band_plan.hpp: band_resident over five arrays"""
     fit = (160 * 1024 - 256 - (2 * 512 + 3 * D) * 8) // (Tmax * D * 8)
     return 5 if fit >= 5 else (int(fit) if fit >= 2 else 0)
 

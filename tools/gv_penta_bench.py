@@ -1,5 +1,5 @@
 """BlockDiagTrajectoryGVGMMMap over BlockDiagTrajectoryGMMMap(g, T, windows=3) (the GV ascent over three windows,
-csrc/traj_gv_penta.hip: traj_gvp_kernel) beside the two-window DiagTrajectoryGVGMMMap (traj_gvd_kernel) on the same tree, in the
+csrc/traj_gv_band.hip: traj_gvp_kernel) beside the two-window DiagTrajectoryGVGMMMap (traj_gvd_kernel) on the same tree, in the
 protocol of tools/gv_diag_bench.py.  Device-resident.
 
   shapes:  M = 64, D = 40, 100 epochs, alpha = 1e-5: 256 x 2000 frames and 5120 x 100 frames -- vc's default chunks
@@ -14,7 +14,7 @@ protocol of tools/gv_diag_bench.py.  Device-resident.
            (tracing only, no counters), a run of its own; the GV kernel's average duration is added, and in the streamed form the
            bytes it moves per epoch (three windows: five (T,D) arrays read, one written, 6 T D 8; two windows: four and one)
            against --peak-tbs
-  form:    how many of the kernel's arrays stay in LDS (csrc/traj_gvp_plan.hpp / traj_gvd_plan.hpp, restated here): 0 = streamed
+  form:    how many of the kernel's arrays stay in LDS (csrc/traj_band_plan.hpp, restated here): 0 = streamed
 
 Usage: python tools/gv_penta_bench.py [--shapes 40:256:2000,40:5120:100] [--rounds 5] [--calls 5] [--kernels] [--out FILE]"""
 import argparse
@@ -37,7 +37,7 @@ ARRAYS = {2: 5, 3: 6}        # (T,D) arrays of the ascent per window count
 
 
 def resident(W, D, Tmax):
-    """csrc/traj_gvd_plan.hpp: gvd_resident (W = 2), csrc/traj_gvp_plan.hpp: gvp_resident (W = 3)"""
+    """csrc/traj_band_plan.hpp: band_resident over five arrays (W = 2) or six (W = 3)"""
     fit = (160 * 1024 - 256 - (2 * 512 + 3 * D) * 8) // (Tmax * D * 8)
     return ARRAYS[W] if fit >= ARRAYS[W] else (int(fit) if fit >= 2 else 0)
 

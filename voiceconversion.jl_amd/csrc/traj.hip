@@ -248,15 +248,12 @@ int traj_run(vcmi_traj *t, std::vector<TrajUtt> &utts, int64_t nframes, bool con
   TrajSolvePlan plan;      // (its host work runs beside the g_t kernel)
   VCMI_TRY(traj_solve_plan(t, utts, nframes, Tmax, gv != nullptr, &plan));
   t->em_run_iters = 0;
-  if (diag) {     // (EM: over a cross-diagonal handle only, vcmi_traj_set_em_bdiag; GV: a handle of vcmi_trajgv_create_diag)
-    if (t->windows == 3) {     // (no EM over such a handle; GV: a handle of vcmi_trajgv_create_bdiag)
-      VCMI_TRY(traj_penta_launch(t, plan, t->dg_q.p, t->mhat.p, st));
-      if (gv && gv->epochs >= 0) VCMI_TRY(traj_gvp_launch(t, plan, *gv, st));
-      return VCMI_OK;
-    }
-    VCMI_TRY(traj_diag_launch(t, plan, t->dg_q.p, t->mhat.p, st));
+  if (diag) {     // the band family, solver and ascent by t->windows
+    VCMI_TRY(traj_band_solve_launch(t, plan, t->dg_q.p, t->mhat.p, st));
+    // (EM: over a cross-diagonal handle with two windows only, vcmi_traj_set_em_bdiag refuses three)
     if (t->b && t->em_iters > 0) VCMI_TRY(traj_em_bdiag_run(t, utts, plan, st));
-    if (gv && gv->epochs >= 0) VCMI_TRY(traj_gvd_launch(t, plan, *gv, st));
+    // (GV: a handle of vcmi_trajgv_create_diag or _bdiag)
+    if (gv && gv->epochs >= 0) VCMI_TRY(traj_band_gv_launch(t, plan, *gv, st));
     return VCMI_OK;
   }
   VCMI_TRY(traj_solve_launch(t, plan, plan.padded ? t->Qpad.p : t->Q.p, t->mhat.p, 0, n, st));

@@ -8,7 +8,8 @@
 //   P[t,t-2] = -p_d(t-1)/4                             (terms with a frame outside the utterance dropped, as W drops them)
 // with p(t) = q[mhat_t] and g_t = q_mhat (.) (A_mhat x_t + b_mhat) from the g_t kernels of traj.hip, run on the images of
 // diag(q_m).  p_s > 0 makes every system strictly diagonally dominant: the Thomas recurrence needs no pivoting and cannot fail.
-// Here: the handle's diagonal model (traj_diag_ensure), the solver and its launch, the setting's two entries.
+// Here: the handle's diagonal model (traj_diag_ensure), the solver, the solve entry of the band family (which hands a handle with
+// three windows to traj_penta.hip), the setting's two entries.
 #include "traj_internal.hpp"
 #include "traj_prepare.hpp"
 #include "hostpipe.hpp"
@@ -147,7 +148,10 @@ traj_diag_solve_kernel(const TrajUtt *__restrict__ utts, int nslab, int D, const
   }
 }
 
-int traj_diag_launch(vcmi_traj *t, const TrajSolvePlan &p, const double *q, const int64_t *mh, hipStream_t st) {
+int traj_penta_launch(vcmi_traj *t, const TrajSolvePlan &p, const double *q, const int64_t *mh, hipStream_t st);     // traj_penta.hip
+
+int traj_band_solve_launch(vcmi_traj *t, const TrajSolvePlan &p, const double *q, const int64_t *mh, hipStream_t st) {
+  if (t->windows == 3) return traj_penta_launch(t, p, q, mh, st);
   const int nslab = (t->D + 31) / 32;
   hipLaunchKernelGGL(traj_diag_solve_kernel, dim3((unsigned)((int64_t)p.n * nslab)), dim3(64), 0, st, p.du, nslab, t->D, q, mh,
                      t->gbuf.p, t->ws.p);

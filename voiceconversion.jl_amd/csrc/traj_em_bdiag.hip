@@ -287,7 +287,7 @@ int traj_em_bdiag_run(vcmi_traj *t, const std::vector<TrajUtt> &utts, const Traj
   for (int it = 0; it < iters; ++it) {
     VCMI_TRY(em_bd_pass(t, plan.du, dj, njobs, false, t->em_lse.p, t->em_table.p, t->gbuf.p, st));
     VCMI_TRY(traj_em_sum_launch(plan.du, n, t->em_lse.p, t->em_L.p + (size_t)it * n, st));
-    VCMI_TRY(traj_diag_launch(t, plan, t->em_table.p, t->em_mh.p, st));
+    VCMI_TRY(traj_band_solve_launch(t, plan, t->em_table.p, t->em_mh.p, st));
   }
   t->em_run_iters = iters;
   t->em_run_n = n;

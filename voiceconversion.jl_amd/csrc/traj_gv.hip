@@ -1,10 +1,10 @@
 // traj_gv.hip -- TrajectoryGVGMMMap (reference src/trajectory_gmmmap.jl:114-189): the handle, the three kernels of the
 // global-variance ascent on solved trajectories (two for 2D <= 96, traj_gvw_kernel above that), and the host function that
-// chooses between them (traj_internal.hpp: traj_gv_launch).  The ascent over diagonal conditional precisions: traj_gv_diag.hip.
+// chooses between them (traj_internal.hpp: traj_gv_launch).  The ascent over diagonal conditional precisions: traj_gv_band.hip.
 #include "traj_internal.hpp"
 #include "traj_blk_prof.hpp"
 #include "traj_gv_moments.hpp"
-#include "traj_gvd_plan.hpp"
+#include "traj_band_plan.hpp"
 #include "host_linalg.hpp"
 #include "hostpipe.hpp"
 
@@ -788,7 +788,7 @@ using namespace vcmi;
 
 // ---- TrajectoryGVGMMMap, src/trajectory_gmmmap.jl:114-189 ----------------------------------------
 // bdiag: vcmi_trajgv_create_bdiag -- a cross-diagonal converter only, with two windows (the handle of vcmi_trajgv_create_diag) or
-// three (traj_gv_penta.hip)
+// three (traj_gv_band.hip)
 static int trajgv_create(vcmi_traj *t, const double *muv, const double *sigmavv, bool diag, vcmi_trajgv **out, bool bdiag = false) {
   const char *who = bdiag ? "vcmi_trajgv_create_bdiag" : diag ? "vcmi_trajgv_create_diag" : "vcmi_trajgv_create";
   if (!t || !muv || !sigmavv || !out) return fail(VCMI_ERR_ARG, "%s: NULL argument", who);
@@ -836,13 +836,13 @@ extern "C" int vcmi_trajgv_create(vcmi_traj *t, const double *muv, const double 
   return trajgv_create(t, muv, sigmavv, false, out);
 }
 
-// ... over a converter with diagonal conditional precisions (vcmi_traj_set_precision, vcmi_traj_create_bdiag): traj_gv_diag.hip
+// ... over a converter with diagonal conditional precisions (vcmi_traj_set_precision, vcmi_traj_create_bdiag): traj_gv_band.hip
 extern "C" int vcmi_trajgv_create_diag(vcmi_traj *t, const double *muv, const double *sigmavv, vcmi_trajgv **out) {
   return trajgv_create(t, muv, sigmavv, true, out);
 }
 
 // ... over a converter made straight from a cross-diagonal model, with two windows (the handle above, bit for bit) or three
-// (traj_gv_penta.hip: traj_gvp_kernel)
+// (traj_gv_band.hip: traj_gvp_kernel)
 extern "C" int vcmi_trajgv_create_bdiag(vcmi_traj *t, const double *muv, const double *sigmavv, vcmi_trajgv **out) {
   return trajgv_create(t, muv, sigmavv, true, out, true);
 }

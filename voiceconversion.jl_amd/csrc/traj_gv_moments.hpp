@@ -1,5 +1,5 @@
 // traj_gv_moments.hpp -- the two-pass, fixed-order moments of a trajectory, shared by the kernels of the global-variance ascent
-// (traj_gv.hip, traj_gv_diag.hip).  Device code, included by the files that launch those kernels.
+// (traj_gv.hip, traj_gv_band.hpp).  Device code, included by the files that launch those kernels.
 #pragma once
 
 namespace vcmi {

@@ -1,5 +1,6 @@
-// traj_internal.hpp -- what crosses traj.hip, traj_solve.hip, traj_diag.hip, traj_gv.hip, traj_em.hip and traj_vc.cpp: the two handles, the
-// per-call descriptors and HOST functions (no relocatable device code: a kernel is launched by the file that defines it).
+// traj_internal.hpp -- what crosses traj.hip, traj_solve.hip, the band family (traj_diag.hip, traj_penta.hip, traj_gv_band.hip),
+// traj_gv.hip, traj_em.hip, traj_em_bdiag.hip and traj_vc.cpp: the two handles, the per-call descriptors and HOST functions (no
+// relocatable device code: a kernel is launched by the file that defines it).
 #pragma once
 #include "vcmi_common.hpp"
 #include "gmmmap_handle.hpp"
@@ -71,7 +72,7 @@ struct vcmi_trajgv {
   vcmi_traj *t = nullptr;
   vcmi::DevBuf<double> muv, pv;   // (D), (D,D) = inv(Sigma^vv) in the Julia memory image
   std::vector<double> h_muv, h_pv;             // host copies for the device-group replicas
-  bool diag = false;              // made by vcmi_trajgv_create_diag / _bdiag: converts only while t's precision is DIAG (traj_gv_diag.hip)
+  bool diag = false;              // made by vcmi_trajgv_create_diag / _bdiag: converts only while t's precision is DIAG (traj_gv_band.hip)
   std::vector<vcmi_trajgv *> replicas;
   uint64_t replicas_epoch = 0;
   ~vcmi_trajgv() {
@@ -126,33 +127,32 @@ struct TrajSolvePlan {
 bool traj_solve_is_big(int D);
 // The plan of a call over `utts` (sorted longest first, ALREADY uploaded to t->uttbuf; t->gbuf reserved; traj_run calls it after
 // the g_t launch, so this host work overlaps that kernel); with_gv: the workspace
-// also holds the GV ascent's V, r and perm (in diagonal mode: its four (nframes,D) arrays).  Host work only, nothing goes to a stream: reserves ws (the one reserve of the solve
+// also holds the GV ascent's V, r and perm (in diagonal mode: its (nframes,D) arrays).  Host work only, nothing goes to a stream: reserves ws (the one reserve of the solve
 // path), gpad / ypad / gwin where the solver needs them, and uploads the padded descriptors (synchronous).  A reserve that
 // grows a buffer frees the old one, which waits for the device.  A handle in diagonal mode gets n, Tmax, nframes, du, cus, grid and a
-// workspace of gvd_ws_doubles (traj_gvd_plan.hpp: nframes * D doubles, five times that with_gv), its size in ws_stride: no
-// padded copies, no window, no occupancy query.  A handle with three windows gets penta_ws_doubles instead (traj_penta_plan.hpp),
-// with_gv gvp_ws_doubles (traj_gvp_plan.hpp).
+// workspace of band_ws_doubles (traj_band_plan.hpp: one (nframes,D) array over two windows, two over three, five with_gv), its
+// size in ws_stride: no padded copies, no window, no occupancy query.
 int traj_solve_plan(vcmi_traj *t, const std::vector<TrajUtt> &utts, int64_t nframes, int Tmax, bool with_gv, TrajSolvePlan *plan);
 // Solve of the (sorted) utterances [b0, b0 + nb) with the precision table Qs (indexed by mh[t] - 1: t->Q / t->Qpad with t->mhat,
 // or the EM loop's table; in plan.Ds) and the right-hand sides in t->gbuf: gbuf -> gpad where padded, the solver the plan chose,
 // ypad -> the utterances' Y after a padded solve.  Asynchronous on st, in launch order; t->status must have been zeroed on st.
 int traj_solve_launch(vcmi_traj *t, const TrajSolvePlan &plan, const double *Qs, const int64_t *mh, int b0, int nb, hipStream_t st);
 
-// ---- traj_diag.hip ----
+// ---- the band family: diagonal conditional precisions (traj_diag.hip, traj_penta.hip, traj_gv_band.hip) ----
 // The diagonal model of the handle on the current device (traj_prepare_diag + upload), once; VCMI_ERR_NOT_PD from the host
 // arithmetic.  Synchronous.
 int traj_diag_ensure(vcmi_traj *t);
-// Solve of the plan's utterances with diagonal conditional precisions: right-hand sides in t->gbuf (made with the diagonal
-// images), the precision table q [.][2D] indexed by the low 32 bits of mh[t] - 1 (t->dg_q with t->mhat, or the cross-diagonal
-// EM loop's per-frame table with its identity index); workspace t->ws, nframes * D doubles indexed by frame0 (a plan made in
-// diagonal mode).  Asynchronous on st; never writes t->status.
-int traj_diag_launch(vcmi_traj *t, const TrajSolvePlan &plan, const double *q, const int64_t *mh, hipStream_t st);
-
-// ---- traj_penta.hip ----
-// The same solve for a handle with three windows (t->windows == 3): right-hand sides t->gbuf [frame][3D], the precision table q
-// [.][3D] with its 1-based index as above; workspace t->ws, the two (nframes,D) arrays of traj_penta_plan.hpp (a plan made for
-// such a handle).  Asynchronous on st; never writes t->status.
-int traj_penta_launch(vcmi_traj *t, const TrajSolvePlan &plan, const double *q, const int64_t *mh, hipStream_t st);
+// Solve of the plan's utterances with diagonal conditional precisions, by t->windows: the tridiagonal solver of traj_diag.hip (2)
+// or the pentadiagonal one of traj_penta.hip (3).  Right-hand sides in t->gbuf [frame][windows D] (made with the diagonal images),
+// the precision table q [.][windows D] indexed by the low 32 bits of mh[t] - 1 (t->dg_q with t->mhat, or the cross-diagonal EM
+// loop's per-frame table with its identity index); workspace t->ws, the solver's (nframes,D) arrays of traj_band_plan.hpp indexed
+// by frame0 (a plan made in diagonal mode).  Asynchronous on st; never writes t->status.
+int traj_band_solve_launch(vcmi_traj *t, const TrajSolvePlan &plan, const double *q, const int64_t *mh, hipStream_t st);
+// The GV ascent behind that solve, by t->windows: traj_gvd_kernel (2) or traj_gvp_kernel (3) of traj_gv_band.hip; how much of the
+// working set stays in LDS follows traj_band_plan.hpp from D and plan.Tmax.  Reads t->mhat, t->gbuf, t->dg_q; workspace: the
+// (nframes,D) arrays of the ascent in t->ws, behind the tridiagonal solver's array or on the pentadiagonal solver's two (a plan
+// made in diagonal mode with_gv).  Asynchronous on st.
+int traj_band_gv_launch(vcmi_traj *t, const TrajSolvePlan &plan, const TrajGV &gv, hipStream_t st);
 // VCMI_ERR_ARG for a handle with three windows at an entry that has no three-window form (`what` names it in the message)
 int traj_two_windows_only(const vcmi_traj *t, const char *who, const char *what);
 
@@ -161,15 +161,6 @@ int traj_two_windows_only(const vcmi_traj *t, const char *who, const char *what)
 // the longest fits LDS, else the one-team kernel; traj_gvw_kernel for more than six row tiles, 2D > 96).  Reads t->mhat, t->gbuf,
 // t->Qfrag; workspace: t->ws with plan.ws_stride (a plan made with_gv).  Asynchronous on st, behind the solve.
 int traj_gv_launch(vcmi_traj *t, const TrajSolvePlan &plan, const TrajGV &gv, hipStream_t st);
-// The same ascent over diagonal conditional precisions, behind traj_diag_launch (traj_gv_diag.hip: traj_gvd_kernel; how much of
-// the working set stays in LDS follows traj_gvd_plan.hpp from D and plan.Tmax).  Reads t->mhat, t->gbuf, t->dg_q; workspace: the
-// four (nframes,D) arrays behind the solver's in t->ws (a plan made in diagonal mode with_gv).  Asynchronous on st.
-int traj_gvd_launch(vcmi_traj *t, const TrajSolvePlan &plan, const TrajGV &gv, hipStream_t st);
-// The ascent over a converter with three windows, behind traj_penta_launch (traj_gv_penta.hip: traj_gvp_kernel; how much of the
-// working set stays in LDS follows traj_gvp_plan.hpp from D and plan.Tmax).  Reads t->mhat, t->gbuf, t->dg_q; workspace: five
-// (nframes,D) arrays from the start of t->ws, the first two on the solver's l1 and l2 (a plan made for such a handle with_gv).
-// Asynchronous on st.
-int traj_gvp_launch(vcmi_traj *t, const TrajSolvePlan &plan, const TrajGV &gv, hipStream_t st);
 // the checks of a call on a TrajectoryGVGMMMap (T may be NULL) and the per-call parameters of its GV ascent; no device work
 int trajgv_args(const vcmi_trajgv *h, int64_t n, const int64_t *T, int epochs, TrajGV *gv);
 
@@ -192,7 +183,7 @@ int traj_em_sum_launch(const TrajUtt *du, int n, const double *lse, double *L, h
 
 // ---- traj_em_bdiag.hip ----
 // t->em_iters E/M pairs over a cross-diagonal handle (t->b) after the arg-max solve of traj_run, on st behind it: per iteration
-// the fused E-step + M-step sums, traj_em_sum_launch and traj_diag_launch on the per-frame table.  Nothing is read back inside
+// the fused E-step + M-step sums, traj_em_sum_launch and traj_band_solve_launch on the per-frame table.  Nothing is read back inside
 // the loop; the job list is uploaded once (synchronous) before it.  utts: the sorted list the plan was made for.
 int traj_em_bdiag_run(vcmi_traj *t, const std::vector<TrajUtt> &utts, const TrajSolvePlan &plan, hipStream_t st);
 

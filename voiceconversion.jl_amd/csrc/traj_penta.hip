@@ -4,9 +4,9 @@
 // With a delta-delta window the even and odd frames of traj_diag.hip no longer decouple: per utterance and static dimension the
 // normal equations are ONE symmetric pentadiagonal system over all frames, positive definite and not diagonally dominant.
 // Statement, the L D L' recurrence and its per-step arithmetic: traj_penta_step.hpp (shared with the host check).  Here: the
-// kernel around those steps and its launch; the workspace rule: traj_penta_plan.hpp.
+// kernel around those steps and its launch; the workspace rule: traj_band_plan.hpp.
 #include "traj_internal.hpp"
-#include "traj_penta_plan.hpp"
+#include "traj_band_plan.hpp"
 #include "traj_penta_step.hpp"
 
 namespace vcmi {

@@ -2,8 +2,7 @@
 // pad / unpad kernels, and the one dispatch behind traj_run and the EM loop (traj_internal.hpp: traj_solve_plan / _launch).
 #include "traj_internal.hpp"
 #include "traj_prepare.hpp"
-#include "traj_penta_plan.hpp"
-#include "traj_gvp_plan.hpp"
+#include "traj_band_plan.hpp"
 #include "traj_blk_prof.hpp"
 #include "hostpipe.hpp"
 #include "lds_dma.hpp"
@@ -472,14 +471,13 @@ int traj_solve_plan(vcmi_traj *t, const std::vector<TrajUtt> &utts, int64_t nfra
   int dev = 0;
   (void)hipGetDevice(&dev);
   (void)hipDeviceGetAttribute(&p.cus, hipDeviceAttributeMultiprocessorCount, dev);
-  if (t->precision == VCMI_TRAJ_PRECISION_DIAG) {   // traj_diag.hip: one double per frame and dimension, indexed by frame0; nothing else
+  if (t->precision == VCMI_TRAJ_PRECISION_DIAG) {   // the band family: (nframes,D) arrays indexed by frame0; nothing else
     p.Ds = D;
     p.du = p.dus = reinterpret_cast<const TrajUtt *>(t->uttbuf.p);
     p.gs = t->gbuf.p;
-    p.grid = std::min(n, p.cus);            // workgroups of the GV ascent (traj_gvd_kernel)
-    // the whole reserve, not a stride: traj_gvd_launch checks it (three windows: the pentadiagonal solver's two arrays; with GV
-    // the five of traj_gvp_plan.hpp, which traj_gvp_launch checks)
-    p.ws_stride = t->windows == 3 && with_gv ? gvp_ws_doubles(nframes, D, true) : traj_diag_ws_doubles(t->windows, nframes, D, with_gv);
+    p.grid = std::min(n, p.cus);            // workgroups of the GV ascent (traj_gvd_kernel, traj_gvp_kernel)
+    // the whole reserve, not a stride: traj_band_gv_launch checks it
+    p.ws_stride = band_ws_doubles(t->windows, nframes, D, with_gv);
     return t->ws.reserve((size_t)p.ws_stride);
   }
   p.grid = std::min(n, p.cus);

@@ -881,14 +881,14 @@ mutable struct TrajectoryGMMMapBlockDiag <: TrajectoryConverter
 end
 # TrajectoryGVGMMMapDiag(tgmm, μᵛ, Σᵛᵛ): the GV converter over DIAGONAL conditional precisions -- tgmm a TrajectoryGMMMap with
 # traj_precision :diag, or a TrajectoryGMMMapBlockDiag.  The likelihood gradient of the ascent is a three-point stencil per static
-# dimension, O(T D) per epoch (csrc/traj_gv_diag.hip).  A TrajectoryGVGMMMap in every other respect: fvconvert, vc and their
+# dimension, O(T D) per epoch (csrc/traj_gv_band.hip).  A TrajectoryGVGMMMap in every other respect: fvconvert, vc and their
 # batch and device forms are the methods above.  It converts only while tgmm's precision is :diag (the library refuses otherwise,
 # and a TrajectoryGVGMMMap(tgmm, μᵛ, Σᵛᵛ) over the same tgmm keeps refusing while it is).
 TrajectoryGVGMMMapDiag(tgmm::Union{TrajectoryGMMMap,TrajectoryGMMMapBlockDiag}, μᵛ::Vector{Float64}, Σᵛᵛ::Matrix{Float64}) =
     TrajectoryGVGMMMap(tgmm, μᵛ, Σᵛᵛ, true)
 # TrajectoryGVGMMMapBlockDiag(tgmm, μᵛ, Σᵛᵛ): the GV converter over a TrajectoryGMMMapBlockDiag (vcmi_trajgv_create_bdiag).  Two
 # windows: TrajectoryGVGMMMapDiag bit for bit.  windows=3, which TrajectoryGVGMMMapDiag refuses: the five-point stencil of the
-# pentadiagonal system (csrc/traj_gv_penta.hip); fvconvert (X (3D,T)), its batch form and vc(tgv, fm (3D+1,T)) on host and device
+# pentadiagonal system (csrc/traj_gv_band.hip); fvconvert (X (3D,T)), its batch form and vc(tgv, fm (3D+1,T)) on host and device
 # matrices, with or without a VarianceScaling; vc(...; delta=true) and batch vc stay refused by the library.
 TrajectoryGVGMMMapBlockDiag(tgmm::TrajectoryGMMMapBlockDiag, μᵛ::Vector{Float64}, Σᵛᵛ::Matrix{Float64}) =
     TrajectoryGVGMMMap(tgmm, μᵛ, Σᵛᵛ, true, true)

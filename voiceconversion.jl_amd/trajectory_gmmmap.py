@@ -511,7 +511,7 @@ class TrajectoryGVGMMMap(TrajectoryConverter):
 class DiagTrajectoryGVGMMMap(TrajectoryGVGMMMap):
     """DiagTrajectoryGVGMMMap(tgmm, mu^v, Sigma^vv): the global-variance conversion of TrajectoryGVGMMMap over a converter with
     DIAGONAL conditional precisions -- a TrajectoryGMMMap(precision="diag") or a BlockDiagTrajectoryGMMMap.  The likelihood
-    gradient of the ascent is then a three-point stencil per static dimension, O(T D) per epoch (csrc/traj_gv_diag.hip;
+    gradient of the ascent is then a three-point stencil per static dimension, O(T D) per epoch (csrc/traj_gv_band.hip;
     include/vcmi.h: vcmi_trajgv_create_diag).  fvconvert, fvconvert_batch, vc and vc_batch are TrajectoryGVGMMMap's.  The
     converter must have precision "diag" when this is made and whenever it converts (VCMIError otherwise; usable again after
     the switch back); a TrajectoryGVGMMMap over the same converter keeps refusing while the precision is "diag"."""
@@ -523,7 +523,7 @@ class BlockDiagTrajectoryGVGMMMap(DiagTrajectoryGVGMMMap):
     """BlockDiagTrajectoryGVGMMMap(tgmm, mu^v, Sigma^vv): the global-variance conversion over a BlockDiagTrajectoryGMMMap
     (TypeError for any other tgmm), through an entry of its own (include/vcmi.h: vcmi_trajgv_create_bdiag).  Two windows: a
     DiagTrajectoryGVGMMMap bit for bit.  windows=3, which DiagTrajectoryGVGMMMap keeps refusing: the likelihood gradient is the
-    five-point stencil of the pentadiagonal system the converter solves, a Jacobi step per epoch (csrc/traj_gv_penta.hip).
+    five-point stencil of the pentadiagonal system the converter solves, a Jacobi step per epoch (csrc/traj_gv_band.hip).
     fvconvert and fvconvert_batch take X (3D,T); vc takes fm (3D+1,T), host matrix or device tensor, with or without a
     postfilter.  delta=True and vc_batch over three windows stay refused (VCMIError naming three windows)."""
 
